@@ -15,24 +15,32 @@ as contiguous point-balanced ranges (dist.plan_shards) — no colle
 The total job is fixed per config ("scaling": "strong").  --frames F [--points n] instead runs F
 frames per GPU of a longer run (weak scaling, the round-1 default).
 
-After the timed steps (outside the timed region): the rank's output is spot-checked against the
+A plain run does only what the headline needs: set-up, the untimed spin-up and order tuning of the
+headline mode, the warmup steps, the K timed steps, and the JSON line.  ``--dump-outputs DIR`` also
+writes what the last timed step left in the output batch (a fixed, seeded sample of whole frames,
+``DIR/deskewed.npy``: float32 (n, 4) x, y, z, intensity rows, frames in ascending order; the frame
+ids are in the line's ``dump_outputs``); the inputs are the same from run to run.  Everything below
+runs only with ``--full``.
+
+--full, after the timed steps (outside the timed region): the rank's output is spot-checked against the
 oracle (N = 1), or, at N > 1, the merged cloud is gathered to rank 0 over RCCL (LMC:887-889), timed,
 and sampled frames of every rank's shard are checked against the oracle (``gather.parity``).  A
 failed or hung gather or a parity miss exits non-zero after the JSON line.
 
-Beside the headline (same line, never part of ``value``): the other two modes, the stager pair,
+--full, beside the headline (same line, never part of ``value``): the other two modes, the stager pair,
 scan_environment, the LVX / PCD writers after a fresh deskew and cold (``codecs``), and at N = 1 the
 reference's host-array calling convention at config-2 scale (``host_path``: run_alignment on numpy
 frames, against the box's PCIe DMA rates) and the simulate_frames -> save_results sequence
 (``simulate_save``); the reference's op sequence on the box's cores (``cpu_baseline``).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mode pose_slerp|frame|imu] [--config C]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N ... bench.py --gpus N   (one process per GPU, RCCL over xGMI)
 
 ``python bench.py --gpus N`` (N > 1) without a torchrun environment launches the N rank processes
 itself (launch_ranks: child processes, never exec; the parent loads no HIP library), forwards rank
-0's line and fails if any rank fails.  At N > 1 rank 0 also times the same whole job on its own GPU
-alone after the sharded run (``single_gpu_same_job``, ``speedup_vs_1gpu``).
+0's line and fails if any rank fails.  With --full at N > 1 rank 0 also times the same whole job on
+its own GPU alone after the sharded run (``single_gpu_same_job``, ``speedup_vs_1gpu``).
 """
 from __future__ import annotations
 
@@ -174,6 +182,43 @@ def check_frames(batch, mode, tr, times, imu, counts, local_frames, global_ids):
                               "note": "the gate: |a-b|/|b| per coordinate <= 1e-5 (north_star), |b| floored at "
                                       "1e-9 * (|p|+|t|); float64 arithmetic in the kernels, one float32 rounding "
                                       "on the store"}}
+
+
+# ---------------------------------------------------------------------------------------------
+# --dump-outputs (after the timed steps, outside the timed region)
+# ---------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 48 << 20   # float32 rows over all ranks: the dump stays well below 64 MB
+
+
+def dump_outputs(batch, directory, rank, world, frame_lo):
+    """What the last timed step left in ``batch`` (the rank's output batch: the x, y, z, intensity
+    columns a caller of Context.deskew / deskew_steps receives), as a fixed sample of whole frames: a
+    seeded permutation of the rank's frames, taken while they fit the rank's share of
+    DUMP_BUDGET_BYTES, written in ascending frame order as float32 (n, 4) rows (the batch's own
+    float32 values, unrounded).  If not even the first frame fits, its leading rows are written.
+    Returns the line's ``dump_outputs`` entry."""
+    budget_rows = DUMP_BUDGET_BYTES // max(world, 1) // 16
+    picked, rows, head = [], 0, None
+    for f in np.random.default_rng(0).permutation(batch.n_frames):
+        n = int(batch.counts[f])
+        if n == 0:
+            continue
+        if rows + n > budget_rows:
+            if not picked:
+                picked, rows, head = [int(f)], budget_rows, budget_rows
+            break
+        picked.append(int(f))
+        rows += n
+    picked.sort()
+    parts = [batch.download_frames(f, f + 1)[:head].astype(np.float32) for f in picked]
+    out = np.concatenate(parts) if parts else np.zeros((0, 4), np.float32)
+    os.makedirs(directory, exist_ok=True)
+    name = "deskewed" if world == 1 else f"deskewed_rank{rank}"
+    np.save(os.path.join(directory, name + ".npy"), out)
+    return {"file": name + ".npy", "dtype": "float32", "shape": list(out.shape), "bytes": int(out.nbytes),
+            "columns": ["x", "y", "z", "intensity"], "frames": [frame_lo + f for f in picked],
+            "what": "the output batch after the last timed step: whole frames (global ids in `frames`, "
+                    "ascending), a seeded sample of the rank's frames"}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1084,7 +1129,17 @@ def main():
                     help="self-launch (--gpus N > 1 without torchrun): kill every rank after this many seconds")
     ap.add_argument("--no-single-gpu", action="store_true", help="N > 1: skip rank 0's same-job 1-GPU run")
     ap.add_argument("--no-tune", action="store_true", help="keep each mode's default sub-tile order (no mc_tune_order)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the last step's output frames to "
+                         "DIR/deskewed.npy (float32 x, y, z, intensity rows)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: CPU baselines, the other modes, stager, scan, "
+                         "codecs, the oracle check, the host-array legs, and at N > 1 the gather and the 1-GPU run "
+                         "(the --no-* options pick among these)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu = args.no_extra_modes = args.no_host_path = args.no_gather = args.no_check = True
+        args.no_single_gpu = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:], args.launch_timeout))
     if args.control_plane_only:
@@ -1108,15 +1163,22 @@ def main():
     devices = rdv.allgather(ctx.pci_bus_id())
     n_devices = len(set(devices))
 
-    b_in = ctx.batch(counts, with_time=True)
+    modes = [args.mode] + ([] if args.no_extra_modes else [m for m in BYTES_PER_POINT if m != args.mode])
+    # the input batches the run's modes read (--full: both, the stager pair converts b_xyz)
+    b_in = b_xyz = None
+    if args.full or args.mode != "frame":
+        b_in = ctx.batch(counts, with_time=True)
     b_out = ctx.batch(counts)
-    b_in.synth(seed=0, frame_id_base=1000 + lo)
-    # frame mode deskews the reference's (N,4) points (LMC:772-776): no t_ns column, 4 per block
-    b_xyz = ctx.batch(counts)
-    b_xyz.synth(seed=0, frame_id_base=1000 + lo)
-    b_xyz.set_frame_times(times)
-    b_in.set_frame_times(times)
-    b_in.set_frame_starts((times * 1e9).astype(np.int64))
+    if b_in is not None:
+        b_in.synth(seed=0, frame_id_base=1000 + lo)
+    if args.full or args.mode == "frame":
+        # frame mode deskews the reference's (N,4) points (LMC:772-776): no t_ns column, 4 per block
+        b_xyz = ctx.batch(counts)
+        b_xyz.synth(seed=0, frame_id_base=1000 + lo)
+        b_xyz.set_frame_times(times)
+    if b_in is not None:
+        b_in.set_frame_times(times)
+        b_in.set_frame_starts((times * 1e9).astype(np.int64))
     ctx.set_trajectory(tr["time"], tr["position_gps"], tr["orientation_imu"])
     ts_imu, gyro = mc.trajectory.imu_from_trajectory(tr, 200.0)
     ctx.set_imu(ts_imu, gyro)
@@ -1124,10 +1186,10 @@ def main():
     n_total = int(counts_all.sum())
     src_of = {m: (b_xyz if m == "frame" else b_in) for m in BYTES_PER_POINT}
 
-    modes = [args.mode] + ([] if args.no_extra_modes else [m for m in BYTES_PER_POINT if m != args.mode])
     results = {}
     tuned = {}
     every = 10
+    dumped = None
     for mode in modes:
         steps = args.steps if mode == args.mode else max(10, args.steps // 4)
         spun = 0.0
@@ -1143,6 +1205,8 @@ def main():
                                 live=not args.events_after, issue=args.issue)
         if mode == args.mode:
             every = ev
+            if args.dump_outputs:   # before anything else writes b_out
+                dumped = dump_outputs(b_out, args.dump_outputs, rank, world, lo)
         wall_max = rdv.max(wall)
         events_avg_s = tm["main_ms"] / max(tm["main_launches"], 1) / 1e3
         spans = tm.get("main_span_us")
@@ -1156,7 +1220,7 @@ def main():
                          "achieved_GBs": achieved,
                          "value": n_total * steps / wall_max / 1e6}
 
-    stager = measure_stager(ctx, b_xyz, b_out, n_rank, min(args.steps, 50)) if n_rank else None
+    stager = measure_stager(ctx, b_xyz, b_out, n_rank, min(args.steps, 50)) if args.full and n_rank else None
     scan = codecs = None
     if not args.no_extra_modes and n_rank:
         scan = measure_scan(ctx, cfg, tr, 10, 0.0 if (args.no_cpu or world > 1) else 3.0)
@@ -1203,6 +1267,9 @@ def main():
         line = assemble_line(args, cid, label, scen, lo, hi, world, n_devices, n_rank, n_total, counts_all,
                              results, spinup_ms, every, tuned, stager, scan, codecs, parity, gather, hung, single)
         ok = line["ok"]
+        line["full"] = bool(args.full)
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if host is not None:
             line["host_path"] = host
             line["simulate_save"] = save

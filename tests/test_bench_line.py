@@ -58,6 +58,41 @@ def test_n8_line_carries_kernel_value_gather_and_single_gpu_denominator(bench):
     assert line["roofline"]["frac"] == pytest.approx(line["roofline"]["achieved"] / 8000.0)
 
 
+class _FakeBatch:
+    """Stands in for a device batch: frame f holds counts[f] rows of the value f + row / 2**20."""
+
+    def __init__(self, counts):
+        self.counts = np.asarray(counts, np.int64)
+        self.n_frames = len(self.counts)
+
+    def download_frames(self, f0, f1):
+        assert f1 == f0 + 1
+        n = int(self.counts[f0])
+        return np.repeat((f0 + np.arange(n) / 2**20)[:, None], 4, axis=1)
+
+
+def test_dump_outputs_is_a_fixed_sample_of_whole_frames_within_the_budget(bench, tmp_path):
+    counts = np.full(600, 100_000, np.int64)
+    counts[7] = 0
+    a = bench.dump_outputs(_FakeBatch(counts), str(tmp_path / "a"), 0, 1, 0)
+    b = bench.dump_outputs(_FakeBatch(counts), str(tmp_path / "b"), 0, 1, 0)
+    assert a == b and a["file"] == "deskewed.npy"
+    got = np.load(tmp_path / "a" / "deskewed.npy")
+    assert got.dtype == np.float32 and got.shape == tuple(a["shape"]) and got.shape[1] == 4
+    assert np.array_equal(got, np.load(tmp_path / "b" / "deskewed.npy"))
+    assert 0 < got.nbytes <= bench.DUMP_BUDGET_BYTES < 64_000_000
+    frames = a["frames"]
+    assert frames == sorted(set(frames)) and 7 not in frames and len(frames) * 100_000 == len(got)
+    assert np.array_equal(got[::100_000, 0], np.asarray(frames, np.float32))   # whole frames, ascending
+    # a rank of a sharded run: its own file, global frame ids, its share of the budget
+    r = bench.dump_outputs(_FakeBatch(counts[:75]), str(tmp_path / "a"), 3, 8, 225)
+    assert r["file"] == "deskewed_rank3.npy" and all(225 <= f < 300 for f in r["frames"])
+    assert r["bytes"] <= bench.DUMP_BUDGET_BYTES // 8
+    # one frame larger than the whole budget: its leading rows
+    big = bench.dump_outputs(_FakeBatch([4_000_000]), str(tmp_path / "c"), 0, 1, 0)
+    assert big["frames"] == [0] and big["bytes"] == bench.DUMP_BUDGET_BYTES
+
+
 def test_shared_device_and_failed_gather_are_flagged(bench):
     line = _line(bench, 2, 1, {"error": "ncclCommInitRank: invalid usage"}, {"error": "skipped"})
     assert "NOT a scaling result" in line["scaling"]

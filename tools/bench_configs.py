@@ -35,7 +35,7 @@ def main():
     args = ap.parse_args()
     res = {}
     for name, extra in CONFIGS.items():
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--no-cpu"] + extra
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(args.steps), "--no-cpu"] + extra
         p = subprocess.run(["timeout", "-k", "10", "300"] + cmd, capture_output=True, text=True, cwd=ROOT)
         if p.returncode != 0:
             res[name] = {"error": p.returncode, "stderr": p.stderr[-2000:]}

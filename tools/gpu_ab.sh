@@ -22,7 +22,7 @@ cat "$OUT/ab_$TAG.log"
 
 if [ "${SKIP_MULTI:-0}" = "0" ]; then
   MCDESKEW_DEVICE=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 20 --no-extra-modes \
+    --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --full --steps 20 --no-extra-modes \
     > "$OUT/bench2_$TAG.json" 2> "$OUT/bench2_$TAG.err"
   stop_if_fault $? bench2
   cat "$OUT/bench2_$TAG.json"; tail -3 "$OUT/bench2_$TAG.err"

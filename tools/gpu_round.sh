@@ -28,13 +28,13 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smo
 stop_if_fault $? smoke
 cat "$OUT/smoke_$TAG.log"
 
-timeout -k 10 600 python bench.py --steps "$STEPS" --warmup 5 > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
+timeout -k 10 600 python bench.py --full --steps "$STEPS" --warmup 5 > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err"
 stop_if_fault $? bench
 cat "$OUT/bench_$TAG.json"
 
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o run \
-  -- python3 "$ROOT/bench.py" --steps "$STEPS" --no-cpu > "$OUT/prof_bench_$TAG.json" 2> "$OUT/prof_$TAG.err"
+  -- python3 "$ROOT/bench.py" --full --steps "$STEPS" --no-cpu > "$OUT/prof_bench_$TAG.json" 2> "$OUT/prof_$TAG.err"
 stop_if_fault $? rocprof
 find "$OUT/prof_$TAG" -name "*kernel_stats*" -exec cp {} "$OUT/kernel_stats_$TAG.csv" \;
 # the bench line's roofline kernel time recomputed from the same run's kernel trace (timed window only)

@@ -4,7 +4,7 @@
 #   tests   python -m pytest tests -m gpu ($PYTEST_ARGS, e.g. "-k slerp")
 #   smoke   __graft_entry__.smoke()
 #   ab      tools/ab.py $AB_ARGS (interleaved A/B of build/variants/lib_*.so)
-#   bench   bench.py with the driver's flags ($BENCH_ARGS)
+#   bench   bench.py --full with the driver's flags ($BENCH_ARGS)
 #   abc     tools/ab_codecs.py $ABC_ARGS (interleaved A/B of the codec kernels across libraries)
 #   abf     tools/ab_pcd_fused.py $ABF_ARGS (interleaved A/B of the fused deskew -> PCD pipeline)
 #   pcdpmc  tools/pcd_pmc.sh (SQ instruction counters of the codec / stager kernels)
@@ -47,7 +47,7 @@ for step in $STEPS; do
       cp gpurun_out/ab.json "$OUT/ab.json" 2>/dev/null
       cat "$OUT/ab.log" ;;
     bench)
-      timeout -k 10 600 python bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+      timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
       stop_if_fault $? bench
       cat "$OUT/bench.json"; tail -3 "$OUT/bench.err" ;;
     abc)
@@ -75,7 +75,7 @@ for step in $STEPS; do
       python -c "import json,sys; d=json.load(open(sys.argv[1])); print({k: d[k] for k in d if k != 'mc_deskew_per_call'})" "$OUT/latency.json" ;;
     prof)
       ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --steps 20 --warmup 5 --no-cpu ${BENCH_ARGS:-} \
+          -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 5 --no-cpu ${BENCH_ARGS:-} \
           > "$OUT/prof_bench.json" 2> "$OUT/prof.err" )
       stop_if_fault $? prof
       find "$OUT/prof" -name "*kernel_stats*" -exec cp {} "$OUT/kernel_stats.csv" \;

@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 PMC=${PMC_SET:-"SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_VALU SQ_ACTIVE_INST_LDS"}
 timeout -s KILL 120 rocprofv3 --pmc $PMC --output-format csv -d "$OUT/sq" -o run \
-  -- python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu --spinup-ms 0 ${BENCH_ARGS:-} > "$OUT/sq_bench.log" 2>&1 || exit 1
+  -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu --spinup-ms 0 ${BENCH_ARGS:-} > "$OUT/sq_bench.log" 2>&1 || exit 1
 python3 - "$OUT/sq" <<'PY' | tee "$OUT/sq_modes.log"
 import csv, glob, sys, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
