@@ -530,12 +530,15 @@ __device__ __forceinline__ void span_end(unsigned long long* span) {
 // ---- k_prep's searches: one load round from an interpolation guess ----------------------------
 // The per-step prep is a chain of dependent memory round trips per frame wave (frame record ->
 // search rounds -> the records' samples -> math), and its latency is step time: the deskew kernel
-// waits for it.  Every table here is a uniform or near-uniform grid (pose samples at gps_rate, IMU
+// waits for it.  The usual table is a uniform or near-uniform grid (pose samples at gps_rate, IMU
 // at its rate), so the wave loads the 64 consecutive entries around the interpolation guess for
 // the frame, together with each entry's pose / IMU sample, in ONE round: the search is a ballot
 // over the lanes (exact whenever the answer lies inside the window, checked; otherwise the full
 // wave-cooperative search), and the samples the records need are shuffled from the lanes that
 // hold them (a sample outside the window is loaded).  Frame: 2 memory round trips instead of 5-6.
+// Any non-decreasing table is valid (mc_set_trajectory / mc_set_imu): on a non-uniform one, or in
+// a run of equal timestamps longer than the window, the guess misses and the frame takes the full
+// search (wave_count / wave_count2), covered by tests/test_gpu_table_search.py.
 
 // first index of the 64-entry window [base, base + 64) around the guess for x in a[0..n)
 template <typename T>
@@ -657,7 +660,9 @@ __device__ __forceinline__ void prep_body(const PrepArgs& a, int64_t block) {
       if (pi < a.T) pv = load_pose(a.time, a.pos, a.rpy, pi);
       int64_t idx = probe_count<true>(pv.t, base, a.T, tf);
       if (idx < 0) idx = wave_count<true>(a.time, a.T, tf);   // searchsorted 'left'
-      if (idx > a.T - 1) idx = a.T - 1;
+      // a NaN frame time compares false with every entry (count 0), but sorts last in numpy: past
+      // the end, then clamped, as rot.cpp frame_poses has it
+      if (tf != tf || idx > a.T - 1) idx = a.T - 1;
       ps = fetch_pose(pv, base, idx, a);
     }
     if (lane < 3) {   // lane i writes row i of R and t_i
