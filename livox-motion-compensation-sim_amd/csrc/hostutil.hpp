@@ -4,6 +4,8 @@
 #include "../../include/mcdeskew.h"
 #include "internal.hpp"
 
+#include <algorithm>
+#include <cstring>
 #include <vector>
 
 using mcimpl::fail;
@@ -47,6 +49,63 @@ static inline int ctx_stage(mc_ctx* c, size_t bytes, void** out) {
   return MC_OK;
 }
 
+// pinned, device-mapped host scratch of at least `bytes` (the zero-copy path of the single calls)
+static inline int ctx_pin(mc_ctx* c, size_t bytes, void** out) {
+  if (bytes > c->pin_bytes) {
+    if (c->h_pin) { (void)hipStreamSynchronize(c->stream); (void)hipHostFree(c->h_pin); c->h_pin = nullptr; }
+    c->pin_bytes = 0;
+    HIPCHK(hipHostMalloc(&c->h_pin, bytes, hipHostMallocMapped | hipHostMallocCoherent));
+    c->pin_bytes = bytes;
+  }
+  *out = c->h_pin;
+  return MC_OK;
+}
+
+// Scratch of one host float64 row call: sections of 8-byte words back to back.  Below kZeroCopyRows
+// rows it is pinned, device-mapped host memory (the kernel reads and writes host memory: no DMA round
+// trips for the reference's per-frame calls), from there on the device staging buffer with DMA on
+// the main stream.  The host source of a put() must stay alive until fetch(), the call's one sync.
+constexpr int64_t kZeroCopyRows = 1 << 15;
+constexpr int kRowBlock = 256;   // threads per workgroup of the row kernels (= mc::kBlock)
+struct RowScratch {
+  hipStream_t s = nullptr;
+  void* base = nullptr;
+  bool zero_copy = false;
+  int open(mc_ctx* c, int64_t n_rows, size_t words) {
+    s = c->stream;
+    zero_copy = n_rows < kZeroCopyRows;
+    return zero_copy ? ctx_pin(c, words * 8, &base) : ctx_stage(c, words * 8, &base);
+  }
+  template <typename T = char>
+  T* at(size_t word) const { return reinterpret_cast<T*>(static_cast<char*>(base) + 8 * word); }
+  int put(size_t word, const void* host, size_t n_words) {
+    if (zero_copy) std::memcpy(at(word), host, 8 * n_words);
+    else HIPCHK(hipMemcpyAsync(at(word), host, 8 * n_words, hipMemcpyHostToDevice, s));
+    return MC_OK;
+  }
+  int fetch(void* host, size_t word, size_t n_words) {
+    if (!zero_copy) HIPCHK(hipMemcpyAsync(host, at(word), 8 * n_words, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (zero_copy) std::memcpy(host, at(word), 8 * n_words);
+    return MC_OK;
+  }
+  int grid(int64_t n) const {   // workgroups of a grid-stride row kernel over n rows (fewer over PCIe)
+    return (int)std::min<int64_t>((n + kRowBlock - 1) / kRowBlock, zero_copy ? 1024 : 65536);
+  }
+};
+
+// doff[f] = rows before frame f (F + 1 entries); also(f) != MC_OK fails frame f after its size check
+static inline int frame_offsets(const int64_t* counts, int32_t F, std::vector<int64_t>* doff,
+                                const std::function<int(int32_t)>& also = nullptr) {
+  doff->assign((size_t)F + 1, 0);
+  for (int32_t f = 0; f < F; ++f) {
+    CHECK_ARG(counts[f] >= 0, "negative frame size at frame %d", f);
+    if (also) if (int r = also(f)) return r;
+    (*doff)[f + 1] = (*doff)[f] + counts[f];
+  }
+  return MC_OK;
+}
+
 struct DeviceGuard {
   int prev = -1;
   explicit DeviceGuard(int dev) {
@@ -63,9 +122,15 @@ static inline hipEvent_t ev_take(mc_ctx* c) {
   if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return nullptr;
   return e;
 }
+using EventPairs = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+// the pairs of v back into the pool
+static inline void ev_recycle(mc_ctx* c, EventPairs& v) {
+  for (auto& p : v) { c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }
+  v.clear();
+}
 struct TimedRegion {
-  mc_ctx* c; std::vector<std::pair<hipEvent_t, hipEvent_t>>* v; hipStream_t s; hipEvent_t e0 = nullptr;
-  TimedRegion(mc_ctx* c_, std::vector<std::pair<hipEvent_t, hipEvent_t>>* v_, hipStream_t s_) : c(c_), v(v_), s(s_) {
+  mc_ctx* c; EventPairs* v; hipStream_t s; hipEvent_t e0 = nullptr;
+  TimedRegion(mc_ctx* c_, EventPairs* v_, hipStream_t s_) : c(c_), v(v_), s(s_) {
     if (c->timing) { e0 = ev_take(c); if (e0) (void)hipEventRecord(e0, s); }
   }
   ~TimedRegion() {
@@ -88,20 +153,20 @@ struct LaunchEvents {
     e1 = e0 ? ev_take(c) : nullptr;
     if (e0 && !e1) { c->ev_pool.push_back(e0); e0 = nullptr; }
   }
-  void keep(std::vector<std::pair<hipEvent_t, hipEvent_t>>* v) {
+  void keep(EventPairs* v) {
     if (e0) v->emplace_back(e0, e1);
     e0 = e1 = nullptr;
   }
 };
 
-// both streams idle (before reallocating tables a pipelined prep may still read or write)
+// both streams idle (before reallocating anything queued work may still read or write)
 static inline int sync_all(mc_ctx* c) {
-  HIPCHK(hipStreamSynchronize(c->side));
+  HIPCHK(hipStreamSynchronize(c->row_d2h));
   HIPCHK(hipStreamSynchronize(c->stream));
   return MC_OK;
 }
 
-static inline int sum_events(mc_ctx* c, std::vector<std::pair<hipEvent_t, hipEvent_t>>& v, double* ms, int64_t* n) {
+static inline int sum_events(mc_ctx* c, EventPairs& v, double* ms, int64_t* n) {
   double tot = 0.0;
   for (auto& p : v) {
     float m = 0.f;
@@ -110,7 +175,6 @@ static inline int sum_events(mc_ctx* c, std::vector<std::pair<hipEvent_t, hipEve
   }
   if (ms) *ms = tot;
   if (n) *n = (int64_t)v.size();
-  for (auto& p : v) { c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }
-  v.clear();
+  ev_recycle(c, v);
   return MC_OK;
 }

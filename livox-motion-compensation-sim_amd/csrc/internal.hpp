@@ -76,13 +76,15 @@ class HostPool {
 
 struct mc_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;   // main stream: staging + the deskew kernels
-  hipStream_t side = nullptr;     // per-step pose prep, pipelined one step ahead of `stream`
-  // per-step tables are double-buffered: prep of step i+1 (side) overlaps the kernel of step i
+  hipStream_t stream = nullptr;   // main stream: staging, k_prep and the deskew kernels (one queue)
+  hipStream_t row_d2h = nullptr;  // the row pipeline's D2H copies, beside its H2D + kernel on `stream`
+  // per-step tables come in two halves: the next step's prep writes half `buf` while the previous
+  // step's deskew kernel still reads the other (see mc_deskew)
   int buf = 0;
-  // true until the next k_prep must wait for everything queued before it (an ordinary, barrier
-  // launch): set by async writers of the prep's inputs (t_ns spans) and by step-graph replays;
-  // cleared by mc_deskew, whose deskew kernel then ends the queue (see mc_deskew)
+  // true while the next k_prep must wait for everything queued before it (an ordinary, barrier
+  // launch): set by whatever leaves work queued that the prep must not overtake (t_ns spans, the
+  // stagers, table uploads, a speculative launch writing the same half); cleared by mc_deskew, whose
+  // deskew kernel then ends the queue, so the next prep may run any-order beside it (see mc_deskew)
   bool prep_fence = true;
   // Per-call speculation (mc_deskew): a call whose inputs equal the previous call's launches its
   // deskew fused with the prep of an identical next call into the other table half (the pipelined
@@ -108,9 +110,6 @@ struct mc_ctx {
     int32_t order = -1;
   };
   OrderTune order_tune[3];
-  hipEvent_t ev_main_done[2] = {nullptr, nullptr};
-  hipEvent_t ev_prep_done[2] = {nullptr, nullptr};
-  hipEvent_t ev_order = nullptr;  // orders side-stream prep after async main-stream staging
   // trajectory (LMC:361-428): time, position_gps, orientation_imu; host copies for the float64
   // paths' per-frame poses (rot.cpp frame_poses)
   int64_t T = 0, T_cap = 0;

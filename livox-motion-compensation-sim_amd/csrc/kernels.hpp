@@ -859,7 +859,6 @@ __device__ __forceinline__ float xf_row(const FrameRow& r, float x, float y, flo
   return (float)fma(r.x, (double)x, fma(r.y, (double)y, fma(r.z, (double)z, t)));
 }
 
-template <bool kW>
 __device__ __forceinline__ void deskew_frame_body(const DeskewArgs& a) {
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const Tile tl = ldu(a.tiles + tile);
@@ -888,9 +887,9 @@ __device__ __forceinline__ void deskew_frame_body(const DeskewArgs& a) {
         float4 X = vx[it], Y = vy[it], Z = vz[it], W = vi[it];
         float4 ox4, oy4, oz4;
 #define MC_XF(c)                                                  \
-  ox4.c = xf_row<kW>(r0, X.c, Y.c, Z.c, W.c);                     \
-  oy4.c = xf_row<kW>(r1, X.c, Y.c, Z.c, W.c);                     \
-  oz4.c = xf_row<kW>(r2, X.c, Y.c, Z.c, W.c);
+  ox4.c = xf_row<true>(r0, X.c, Y.c, Z.c, W.c);                   \
+  oy4.c = xf_row<true>(r1, X.c, Y.c, Z.c, W.c);                   \
+  oz4.c = xf_row<true>(r2, X.c, Y.c, Z.c, W.c);
         MC_XF(x) MC_XF(y) MC_XF(z) MC_XF(w)
 #undef MC_XF
         float* o = ox + (int64_t)(g >> 6) * a.out_C * kBlkPts + 4 * (g & 63);
@@ -1092,7 +1091,7 @@ __global__ __launch_bounds__(kBlock) void k_affine_rows_f64(const double* __rest
 }
 
 // CSIM coordinate transforms with matrices per frame on the f32 batch columns (mc_transform_affine)
-__global__ __launch_bounds__(kBlock) void k_affine_w(const DeskewArgs a) { deskew_frame_body<true>(a); }
+__global__ __launch_bounds__(kBlock) void k_affine_w(const DeskewArgs a) { deskew_frame_body(a); }
 
 // ---------------------------------------------------------------------------------------------
 // float64 per-point math.  Every per-point quantity (alpha, the interpolated quaternion / gyro, the

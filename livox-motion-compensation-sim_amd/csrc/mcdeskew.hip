@@ -23,6 +23,7 @@
 #include <functional>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace mc;
@@ -106,6 +107,25 @@ static int compute_trange(mc_batch* b) {
   return MC_OK;
 }
 
+// One launch of kernel K with optional hipExtLaunchKernel timing events (e0/e1 null: untimed) and
+// AQL flags: through hipExtLaunchKernelGGL with either, or when `ext` says so (the PCD and the fused
+// next-prep launches always), else through hipLaunchKernelGGL.  The two entries' launch overheads
+// have not been measured against each other, so a change must not move a launch between them.
+template <auto K, typename... Args>
+static void launch(bool ext, uint32_t grid, hipStream_t s, hipEvent_t e0, hipEvent_t e1, unsigned flags,
+                   const Args&... args) {
+  if (!ext && !e0 && !flags) hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), 0, s, args...);
+  else hipExtLaunchKernelGGL(K, dim3(grid), dim3(kBlock), 0, s, e0, e1, flags, args...);
+}
+
+// f(std::integral_constant<int, MODE>) for a plan's kernel
+template <typename F>
+static void with_mode(int mode, F&& f) {
+  if (mode == MC_MODE_FRAME) f(std::integral_constant<int, MC_MODE_FRAME>{});
+  else if (mode == MC_MODE_POSE_SLERP) f(std::integral_constant<int, MC_MODE_POSE_SLERP>{});
+  else f(std::integral_constant<int, MC_MODE_IMU>{});
+}
+
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -130,6 +150,23 @@ int mc_device_pci_bus_id(int device, char* out, int len) {
 constexpr int32_t kSpanSlots = 64;
 constexpr size_t kSpanWords = 1 + kSpanTail;
 
+// frees everything the context owns, then the context: mc_destroy, and mc_create's failure path,
+// where the handles not yet created are still null
+static void ctx_release(mc_ctx* c) {
+  dev_free(c->d_time); dev_free(c->d_pos); dev_free(c->d_rpy); dev_free(c->d_pose_seg);
+  dev_free(c->d_imu_ts); dev_free(c->d_gyro); dev_free(c->d_imu_seg);
+  dev_free(c->d_env); dev_free(c->d_scan_pose); dev_free(c->d_scan_tcount);
+  dev_free(c->d_scan_toff); dev_free(c->d_scan_nvis); dev_free(c->d_scan_bits);
+  dev_free(c->d_codec_err); dev_free(c->d_pcd_len); dev_free(c->d_span);
+  for (void* p : {c->d_codec, c->d_seg64, c->d_pipe, c->d_stage}) if (p) (void)hipFree(p);
+  for (void* p : {c->h_pin, c->h_pipe}) if (p) (void)hipHostFree(p);
+  for (EventPairs* v : {&c->codec_ev, &c->main_ev, &c->scan_ev, &c->prep_ev, &c->layout_ev}) ev_recycle(c, *v);
+  for (auto e : c->ev_pool) (void)hipEventDestroy(e);
+  if (c->row_d2h) (void)hipStreamDestroy(c->row_d2h);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+}
+
 int mc_create(int device, mc_ctx** out) {
   CHECK_ARG(out, "out is NULL");
   *out = nullptr;
@@ -145,20 +182,12 @@ int mc_create(int device, mc_ctx** out) {
   mc_ctx* c = new mc_ctx();
   c->device = device;
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
-  for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-    // stream-ordering events between two queues of the same device: device-scope release only
-    const unsigned fl = hipEventDisableTiming | hipEventReleaseToDevice;
-    e = hipEventCreateWithFlags(&c->ev_main_done[i], fl);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_prep_done[i], fl);
-  }
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming | hipEventReleaseToDevice);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->row_d2h, hipStreamNonBlocking);
   // the launch-span pool (span_take), zeroed
   if (e == hipSuccess) e = hipMalloc(&c->d_span, kSpanSlots * kSpanWords * sizeof(unsigned long long));
   if (e == hipSuccess) e = hipMemset(c->d_span, 0, kSpanSlots * kSpanWords * sizeof(unsigned long long));
   if (e != hipSuccess) {
-    if (c->d_span) (void)hipFree(c->d_span);
-    delete c;
+    ctx_release(c);
     return fail(MC_ERR_HIP, "stream/event creation: %s", hipGetErrorString(e));
   }
   *out = c;
@@ -169,30 +198,7 @@ int mc_destroy(mc_ctx* c) {
   if (!c) return MC_OK;
   DeviceGuard g(c->device);
   (void)sync_all(c);
-  dev_free(c->d_time); dev_free(c->d_pos); dev_free(c->d_rpy); dev_free(c->d_pose_seg);
-  dev_free(c->d_imu_ts); dev_free(c->d_gyro); dev_free(c->d_imu_seg);
-  dev_free(c->d_env); dev_free(c->d_scan_pose); dev_free(c->d_scan_tcount);
-  dev_free(c->d_scan_toff); dev_free(c->d_scan_nvis); dev_free(c->d_scan_bits);
-  if (c->d_codec) (void)hipFree(c->d_codec);
-  if (c->d_span) (void)hipFree(c->d_span);
-  dev_free(c->d_codec_err);
-  dev_free(c->d_pcd_len);
-  if (c->d_seg64) (void)hipFree(c->d_seg64);
-  if (c->h_pin) (void)hipHostFree(c->h_pin);
-  if (c->h_pipe) (void)hipHostFree(c->h_pipe);
-  if (c->d_pipe) (void)hipFree(c->d_pipe);
-  for (auto& p : c->codec_ev) { c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }
-  if (c->d_stage) (void)hipFree(c->d_stage);
-  for (auto& p : c->main_ev) { c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }
-  for (auto& p : c->scan_ev) { c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }
-  for (auto& p : c->prep_ev) { c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }
-  for (auto& p : c->layout_ev) { c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }
-  for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  for (int i = 0; i < 2; ++i) { (void)hipEventDestroy(c->ev_main_done[i]); (void)hipEventDestroy(c->ev_prep_done[i]); }
-  (void)hipEventDestroy(c->ev_order);
-  (void)hipStreamDestroy(c->side);
-  (void)hipStreamDestroy(c->stream);
-  delete c;
+  ctx_release(c);
   return MC_OK;
 }
 
@@ -666,7 +672,7 @@ int deskew_check(mc_ctx* c, const mc_batch* in, const mc_batch* out, int mode, i
 }
 
 // Everything one step launches, for table half h: k_prep's and the deskew kernel's arguments and
-// grids.  Plain old data, zero-filled first, so two plans compare bytewise (the graph cache key).
+// grids.  Plain old data, zero-filled first: a mode leaves the fields it does not use at zero.
 struct StepPlan {
   PrepArgs pa;
   DeskewArgs da;
@@ -749,50 +755,52 @@ unsigned long long* span_take(mc_ctx* c) {
   return c->d_span + (size_t)c->span_used++ * kSpanWords;
 }
 
-// Launches with optional hipExtLaunchKernel timing events (e0/e1 null: untimed) and AQL flags.
 void launch_prep(const StepPlan& sp, hipStream_t sd, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr,
                  unsigned flags = 0) {
-  if (!e0 && !flags) hipLaunchKernelGGL(k_prep, dim3(sp.prep_blocks), dim3(kBlock), 0, sd, sp.pa);
-  else hipExtLaunchKernelGGL(k_prep, dim3(sp.prep_blocks), dim3(kBlock), 0, sd, e0, e1, flags, sp.pa);
+  launch<k_prep>(false, sp.prep_blocks, sd, e0, e1, flags, sp.pa);
 }
 
 void launch_main(const StepPlan& sp, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr) {
-  const dim3 grid(sp.grid), block(kBlock);
-  if (sp.da.pcd_len) {   // mc_deskew_pcd
-    if (sp.kernel == MC_MODE_FRAME) hipExtLaunchKernelGGL(k_deskew_frame_pcd, grid, block, 0, s, e0, e1, 0u, sp.da);
-    else if (sp.kernel == MC_MODE_POSE_SLERP)
-      hipExtLaunchKernelGGL((k_deskew_points<1, false, true>), grid, block, 0, s, e0, e1, 0u, sp.da, sp.pa, 0u);
-    else hipExtLaunchKernelGGL((k_deskew_points<2, false, true>), grid, block, 0, s, e0, e1, 0u, sp.da, sp.pa, 0u);
-    return;
-  }
-  if (!e0) {
-    if (sp.kernel == MC_MODE_FRAME) hipLaunchKernelGGL(k_deskew_frame, grid, block, 0, s, sp.da);
-    else if (sp.kernel == MC_MODE_POSE_SLERP) hipLaunchKernelGGL((k_deskew_points<1>), grid, block, 0, s, sp.da, sp.pa, 0u);
-    else hipLaunchKernelGGL((k_deskew_points<2>), grid, block, 0, s, sp.da, sp.pa, 0u);
-    return;
-  }
-  if (sp.kernel == MC_MODE_FRAME) hipExtLaunchKernelGGL(k_deskew_frame, grid, block, 0, s, e0, e1, 0u, sp.da);
-  else if (sp.kernel == MC_MODE_POSE_SLERP)
-    hipExtLaunchKernelGGL((k_deskew_points<1>), grid, block, 0, s, e0, e1, 0u, sp.da, sp.pa, 0u);
-  else hipExtLaunchKernelGGL((k_deskew_points<2>), grid, block, 0, s, e0, e1, 0u, sp.da, sp.pa, 0u);
+  const bool pcd = sp.da.pcd_len != nullptr;   // mc_deskew_pcd
+  with_mode(sp.kernel, [&](auto mode) {
+    constexpr int M = decltype(mode)::value;
+    if constexpr (M == MC_MODE_FRAME) {
+      if (pcd) launch<k_deskew_frame_pcd>(true, sp.grid, s, e0, e1, 0u, sp.da);
+      else launch<k_deskew_frame>(false, sp.grid, s, e0, e1, 0u, sp.da);
+    } else {
+      if (pcd) launch<k_deskew_points<M, false, true>>(true, sp.grid, s, e0, e1, 0u, sp.da, sp.pa, 0u);
+      else launch<k_deskew_points<M>>(false, sp.grid, s, e0, e1, 0u, sp.da, sp.pa, 0u);
+    }
+  });
 }
 
 // This step's deskew (sp) with the NEXT step's prep (nx) in the first workgroups of the same launch
 // (k_deskew_points<MODE, true> / k_deskew_frame_next): pre = nx's prep workgroups rounded up to the
 // XCD count.  sp reads one table half, nx writes the other.
 void launch_fused(const StepPlan& sp, const StepPlan& nx, hipStream_t s, hipEvent_t e0, hipEvent_t e1) {
-  const uint32_t pre = (nx.prep_blocks + kXcds - 1) / kXcds * kXcds;
-  const dim3 grid(sp.grid + pre), block(kBlock);
-  if (sp.kernel == MC_MODE_FRAME)
-    hipExtLaunchKernelGGL(k_deskew_frame_next, grid, block, 0, s, e0, e1, 0u, sp.da, nx.pa, pre);
-  else if (sp.kernel == MC_MODE_POSE_SLERP)
-    hipExtLaunchKernelGGL((k_deskew_points<1, true>), grid, block, 0, s, e0, e1, 0u, sp.da, nx.pa, pre);
-  else hipExtLaunchKernelGGL((k_deskew_points<2, true>), grid, block, 0, s, e0, e1, 0u, sp.da, nx.pa, pre);
+  const uint32_t pre = (nx.prep_blocks + kXcds - 1) / kXcds * kXcds, grid = sp.grid + pre;
+  with_mode(sp.kernel, [&](auto mode) {
+    constexpr int M = decltype(mode)::value;
+    if constexpr (M == MC_MODE_FRAME) launch<k_deskew_frame_next>(true, grid, s, e0, e1, 0u, sp.da, nx.pa, pre);
+    else launch<k_deskew_points<M, true>>(true, grid, s, e0, e1, 0u, sp.da, nx.pa, pre);
+  });
 }
 
-// frame time spans derived lazily from t_ns (queued on the main stream)
-int ensure_trange(mc_batch* in, int mode) {
-  if (mode != MC_MODE_FRAME && !in->trange_valid) return compute_trange(in);
+// What mc_deskew, mc_deskew_steps and mc_tune_order do before their first launch: the frame time
+// spans, derived lazily from t_ns, are queued on the main stream if stale (the prep is then ordered
+// after them); plan[i] is planned for table half h0 ^ i (plan[1] only if `both`); out is about to be
+// written.
+int begin_steps(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select, int h0, bool both,
+                StepPlan* plan) {
+  if (mode != MC_MODE_FRAME && !in->trange_valid) {
+    if (int r = compute_trange(const_cast<mc_batch*>(in))) return r;
+    c->prep_fence = true;
+  }
+  for (int i = 0; i <= (both ? 1 : 0); ++i) deskew_plan(c, in, out, mode, pose_select, h0 ^ i, &plan[i]);
+  // a per-point deskew that carries t_ns into another batch rewrites that batch's time column:
+  // its cached [min, max] spans no longer describe it
+  if (plan[0].da.copy_t) out->trange_valid = false;
+  out->wrote(false);
   return MC_OK;
 }
 }  // namespace
@@ -814,24 +822,15 @@ int mcimpl::deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, 
   if (int r = deskew_check(c, in, out, mode, pose_select)) return r;
   if (in->F == 0) return MC_OK;
   if (!pcd_len) pcd_len = out->d_pcd_len;   // MC_BATCH_WITH_PCD_LEN: the *_pcd kernels keep its sums
-  out->wrote(false);
   DeviceGuard g(c->device);
   hipStream_t s = c->stream;
-  if (mode != MC_MODE_FRAME && !in->trange_valid) {
-    // the spans are queued on the main stream: order the prep after them
-    if (int r = ensure_trange(const_cast<mc_batch*>(in), mode)) return r;
-    c->prep_fence = true;
-  }
   // Per-step tables come in two halves: this step's prep writes half h, which the deskew kernel
   // two calls back read; the previous call's kernel reads the other half.
   const int h = c->buf;
+  StepPlan sp;   // (the other half is planned only when this call speculates)
+  if (int r = begin_steps(c, in, out, mode, pose_select, h, false, &sp)) return r;
   c->buf ^= 1;
-  StepPlan sp;
-  deskew_plan(c, in, out, mode, pose_select, h, &sp);
   sp.da.pcd_len = pcd_len;
-  // a per-point deskew that carries t_ns into another batch rewrites that batch's time column:
-  // its cached [min, max] spans no longer describe it
-  if (sp.kernel >= 0 && sp.da.copy_t) out->trange_valid = false;
   // Speculation (see mc_ctx::PrepKey): h is the half the previous call's launch prepared for this
   // key, if it did; then this call needs no k_prep at all.
   const mc_ctx::PrepKey key{in->uid, c->traj_ver, c->imu_ver, in->prep_ver, mode, pose_select};
@@ -845,9 +844,9 @@ int mcimpl::deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, 
     // kernel (prep_fence clear): the packets before it are then that kernel — still reading the
     // other half — and, before it, work the kernel's barrier already waited for.  Everything else
     // that could precede it either finished before its API call returned (trajectory / IMU / frame
-    // tables are uploaded synchronously) or set the fence (t_ns spans queued above, graph replays,
-    // a speculative launch whose prep workgroups write this very half).  The deskew kernel's own
-    // packet keeps the barrier bit, so it waits for this prep, and anything queued after it waits
+    // tables are uploaded synchronously) or set the fence (t_ns spans queued by begin_steps, the
+    // stagers, a speculative launch whose prep workgroups write this very half).  The deskew kernel's
+    // own packet keeps the barrier bit, so it waits for this prep, and anything queued after it waits
     // for both.  With no kernel to follow (no tiles) the prep is ordinary.
     const unsigned fl = (!c->prep_fence && sp.kernel >= 0) ? hipExtAnyOrderLaunch : 0u;
     {
@@ -882,7 +881,7 @@ int mcimpl::deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, 
   }
   // No event records here: a marker packet between this kernel and the next step's any-order prep
   // would hold that prep until this kernel completes.  Everything is on one queue, so the stream
-  // order is the only ordering the halves need (a graph replay forks its prep branch from s).
+  // order is the only ordering the halves need.
   return MC_OK;
 }
 
@@ -894,9 +893,8 @@ namespace {
 // Every `every`-th step's kernel (and prep) is timed.
 // last_pcd: the last step's launch also writes the output blocks' PCD text bytes there (its output is
 // what the batch keeps; the launches before it have no PCD variant of the fused next-prep kernel).
-void issue_steps(mc_ctx* c, const StepPlan* plan, int mode, int32_t n_steps, int32_t every, int32_t* last_pcd) {
+void issue_steps(mc_ctx* c, const StepPlan* plan, int32_t n_steps, int32_t every, int32_t* last_pcd) {
   hipStream_t s = c->stream;
-  (void)mode;
   auto sampled = [&](int32_t i) { return every > 0 && i % every == every / 2; };
   for (int32_t i = 0; i < n_steps; ++i) {
     if (i == 0) {
@@ -925,17 +923,10 @@ void issue_steps(mc_ctx* c, const StepPlan* plan, int mode, int32_t n_steps, int
 int deskew_steps_pipelined(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select,
                            int32_t n_steps, int32_t every) {
   forget_speculation(c);
-  if (mode != MC_MODE_FRAME && !in->trange_valid) {
-    if (int r = ensure_trange(const_cast<mc_batch*>(in), mode)) return r;
-    c->prep_fence = true;
-  }
   const int h0 = c->buf;
   StepPlan plan[2];
-  deskew_plan(c, in, out, mode, pose_select, h0, &plan[0]);
-  deskew_plan(c, in, out, mode, pose_select, h0 ^ 1, &plan[1]);
-  if (plan[0].da.copy_t) out->trange_valid = false;
-  out->wrote(false);
-  issue_steps(c, plan, mode, n_steps, every, plan[0].kernel >= 0 ? out->d_pcd_len : nullptr);
+  if (int r = begin_steps(c, in, out, mode, pose_select, h0, true, plan)) return r;
+  issue_steps(c, plan, n_steps, every, plan[0].kernel >= 0 ? out->d_pcd_len : nullptr);
   HIPCHK(hipGetLastError());
   if (plan[0].kernel >= 0 && n_steps > 0) out->wrote(true);
   c->buf = h0 ^ (n_steps & 1);   // the half the last launch did not read
@@ -963,15 +954,11 @@ int mc_tune_order(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
   }
   DeviceGuard g(c->device);
   hipStream_t s = c->stream;
-  if (int r = ensure_trange(const_cast<mc_batch*>(in), mode)) return r;
-  forget_speculation(c);
-  // the candidates run as the steps of mc_deskew_steps do (issue_steps: fused next-step launches)
-  const int h0 = c->buf;
+  // the candidates run as the steps of mc_deskew_steps do (issue_steps: fused next-step launches);
+  // plain kernels only: any PCD text sums of out go stale
   StepPlan plan[2];
-  deskew_plan(c, in, out, mode, pose_select, h0, &plan[0]);
-  deskew_plan(c, in, out, mode, pose_select, h0 ^ 1, &plan[1]);
-  if (plan[0].da.copy_t) out->trange_valid = false;
-  out->wrote(false);      // plain kernels only: any PCD text sums of out go stale
+  if (int r = begin_steps(c, in, out, mode, pose_select, c->buf, true, plan)) return r;
+  forget_speculation(c);
   c->prep_fence = true;   // the first prep is an ordinary packet: waits for everything queued before it
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIPCHK(hipEventCreate(&e0));
@@ -987,10 +974,10 @@ int mc_tune_order(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
       // the previous round's last launch may read either half (odd `launches`): the warm-up's first
       // prep is an ordinary packet, so it waits for that launch
       c->prep_fence = true;
-      issue_steps(c, plan, mode, 2, 0, nullptr);   // untimed: this order's own steady state
+      issue_steps(c, plan, 2, 0, nullptr);   // untimed: this order's own steady state
       c->prep_fence = false;
       e = hipEventRecord(e0, s);
-      issue_steps(c, plan, mode, launches, 0, nullptr);
+      issue_steps(c, plan, launches, 0, nullptr);
       if (e == hipSuccess) e = hipEventRecord(e1, s);
       if (e == hipSuccess) e = hipEventSynchronize(e1);
       float ms = 0.f;
@@ -1037,23 +1024,11 @@ int mc_deskew_steps(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int 
 
 constexpr int64_t kPipeRows = 1 << 21;                                 // 64 MB of (n,4) float64 (max chunk)
 constexpr size_t kPipeBytes = (size_t)kPipeRows * 4 * sizeof(double);
-constexpr int64_t kZeroCopyRows = 1 << 15;                             // below: zero-copy kernels
 constexpr int kPoolThreads = 16;                                       // the box's CPU share per GPU
 constexpr int64_t kJobRows = 8192;                                     // rows per host copy job (256 KB)
+static_assert(kRowBlock == kBlock, "RowScratch::grid counts workgroups of kBlock rows");
 static int row_pipeline(mc_ctx* c, const double* const* frames, const int64_t* lds, const std::vector<int64_t>& doff,
                         const int64_t* d_doff, const double* d_pose, double* const* outs);
-
-// pinned, device-mapped host scratch of at least `bytes` (the zero-copy path of the single calls)
-static int ctx_pin(mc_ctx* c, size_t bytes, char** out) {
-  if (bytes > c->pin_bytes) {
-    if (c->h_pin) { (void)hipStreamSynchronize(c->stream); (void)hipHostFree(c->h_pin); c->h_pin = nullptr; }
-    c->pin_bytes = 0;
-    HIPCHK(hipHostMalloc(&c->h_pin, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    c->pin_bytes = bytes;
-  }
-  *out = static_cast<char*>(c->h_pin);
-  return MC_OK;
-}
 
 // Frames of host float64 rows through k_align_rows_f64 with the per-frame poses pose12 (F x 12,
 // host): below kZeroCopyRows rows the kernel reads and writes pinned, device-mapped host memory
@@ -1062,40 +1037,33 @@ static int align_host_rows(mc_ctx* c, const double* const* frames, const int64_t
                            const std::vector<double>& pose12, double* const* outs) {
   const int32_t F = (int32_t)doff.size() - 1;
   const int64_t n = doff[F];
-  if (n >= kZeroCopyRows) {
-    void* st = nullptr;
-    const size_t tab_b = doff.size() * sizeof(int64_t) + pose12.size() * sizeof(double);
-    if (int r = ctx_stage(c, tab_b, &st)) return r;
-    int64_t* d_doff = static_cast<int64_t*>(st);
-    double* d_pose = reinterpret_cast<double*>(d_doff + doff.size());
-    HIPCHK(hipMemcpyAsync(d_doff, doff.data(), doff.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_pose, pose12.data(), pose12.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    return row_pipeline(c, frames, lds, doff, d_doff, d_pose, outs);
-  }
-  // pinned [doff (F+1) | poses (12 F) | rows (n, 4) | out (n, 4)], 8-byte words
+  // scratch: [doff (F+1) | poses (12 F) | rows (n, 4) | out (n, 4)]; when it is not pinned the tables
+  // alone, and the rows travel through the row pipeline's own buffers
   const size_t w_pose = doff.size(), w_rows = w_pose + pose12.size(), w_out = w_rows + 4 * (size_t)n;
-  char* base = nullptr;
-  if (int r = ctx_pin(c, (w_out + 4 * (size_t)n) * 8, &base)) return r;
-  double* pin = reinterpret_cast<double*>(base);
-  std::memcpy(pin, doff.data(), doff.size() * 8);
-  std::memcpy(pin + w_pose, pose12.data(), pose12.size() * 8);
+  RowScratch sc;
+  if (int r = sc.open(c, n, n < kZeroCopyRows ? w_out + 4 * (size_t)n : w_rows)) return r;
+  if (int r = sc.put(0, doff.data(), doff.size())) return r;
+  if (int r = sc.put(w_pose, pose12.data(), pose12.size())) return r;
+  if (!sc.zero_copy)
+    return row_pipeline(c, frames, lds, doff, sc.at<const int64_t>(0), sc.at<const double>(w_pose), outs);
+  // pinned: the frames' rows are compacted straight into it and copied straight out of it
   for (int32_t f = 0; f < F; ++f) {
     const int64_t m = doff[f + 1] - doff[f], ld = lds[f];
-    double* dst = pin + w_rows + 4 * doff[f];
+    double* dst = sc.at<double>(w_rows) + 4 * doff[f];
     if (ld == 4) std::memcpy(dst, frames[f], (size_t)m * 4 * sizeof(double));
     else for (int64_t i = 0; i < m; ++i) std::memcpy(dst + 4 * i, frames[f] + i * ld, 4 * sizeof(double));
   }
   {
     TimedRegion tr(c, &c->main_ev, c->stream);
-    const int grid = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, 1024);
-    hipLaunchKernelGGL(k_align_rows_f64, dim3(grid), dim3(kBlock), 0, c->stream, pin + w_rows, (int64_t)4, n,
-                       (int64_t)0, reinterpret_cast<const int64_t*>(pin), F, pin + w_pose, pin + w_out);
+    hipLaunchKernelGGL(k_align_rows_f64, dim3(sc.grid(n)), dim3(kBlock), 0, c->stream, sc.at<const double>(w_rows),
+                       (int64_t)4, n, (int64_t)0, sc.at<const int64_t>(0), F, sc.at<const double>(w_pose),
+                       sc.at<double>(w_out));
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int32_t f = 0; f < F; ++f)
     if (doff[f + 1] > doff[f])
-      std::memcpy(outs[f], pin + w_out + 4 * doff[f], (size_t)(doff[f + 1] - doff[f]) * 4 * sizeof(double));
+      std::memcpy(outs[f], sc.at<double>(w_out) + 4 * doff[f], (size_t)(doff[f + 1] - doff[f]) * 4 * sizeof(double));
   return MC_OK;
 }
 
@@ -1129,11 +1097,8 @@ int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, 
   CHECK_ARG(F >= 0, "n_frames must be >= 0");
   CHECK_ARG(F == 0 || counts, "counts is NULL");
   if (ld < 3) return fail(MC_ERR_INDEX, "points need at least 3 columns (x, y, z); got %lld", (long long)ld);
-  std::vector<int64_t> doff((size_t)F + 1, 0);
-  for (int32_t f = 0; f < F; ++f) {
-    CHECK_ARG(counts[f] >= 0, "negative frame size at frame %d", f);
-    doff[f + 1] = doff[f] + counts[f];
-  }
+  std::vector<int64_t> doff;
+  if (int r = frame_offsets(counts, F, &doff)) return r;
   if (mode == MC_MODE_POSE_SLERP) {
     if (c->T < 1) return fail(MC_ERR_STATE, "no trajectory uploaded (mc_set_trajectory)");
     CHECK_ARG(F == 0 || frame_times, "frame times are NULL");
@@ -1175,53 +1140,34 @@ int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, 
     c->seg64_mode = mode;
     c->seg64_ver = ver;
   }
-  // scratch: [doff (F+1) | per-frame value (F) | t_ns (n) | points (n, ld) | out (n, 4)], 8-byte words;
-  // pinned and device-mapped below kZeroCopyRows rows (the kernel reads and writes host memory: no
-  // DMA round trips for the reference's per-frame calls), a device staging buffer above
+  // scratch: [doff (F+1) | per-frame value (F) | t_ns (n) | points (n, ld) | out (n, 4)]
   const size_t w_doff = 0, w_fv = (size_t)F + 1, w_t = w_fv + (size_t)F, w_pts = w_t + (size_t)n,
                w_out = w_pts + (size_t)n * (size_t)ld, words = w_out + 4 * (size_t)n;
-  const bool zero_copy = n < kZeroCopyRows;
-  char* base = nullptr;
-  if (zero_copy) {
-    if (int r = ctx_pin(c, words * 8, &base)) return r;
-    std::memcpy(base + 8 * w_doff, doff.data(), doff.size() * 8);
-    std::memcpy(base + 8 * w_fv, mode == MC_MODE_POSE_SLERP ? static_cast<const void*>(frame_times)
-                                                            : static_cast<const void*>(frame_start_ns), (size_t)F * 8);
-    std::memcpy(base + 8 * w_t, t_ns, (size_t)n * 8);
-    std::memcpy(base + 8 * w_pts, points, (size_t)n * (size_t)ld * 8);
-  } else {
-    void* st = nullptr;
-    if (int r = ctx_stage(c, words * 8, &st)) return r;
-    base = static_cast<char*>(st);
-    HIPCHK(hipMemcpyAsync(base + 8 * w_doff, doff.data(), doff.size() * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(base + 8 * w_fv, mode == MC_MODE_POSE_SLERP ? static_cast<const void*>(frame_times)
-                                                                      : static_cast<const void*>(frame_start_ns),
-                          (size_t)F * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(base + 8 * w_t, t_ns, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(base + 8 * w_pts, points, (size_t)n * (size_t)ld * 8, hipMemcpyHostToDevice, s));
-  }
+  RowScratch sc;
+  if (int r = sc.open(c, n, words)) return r;
+  if (int r = sc.put(w_doff, doff.data(), doff.size())) return r;
+  if (int r = sc.put(w_fv, mode == MC_MODE_POSE_SLERP ? static_cast<const void*>(frame_times)
+                                                      : static_cast<const void*>(frame_start_ns), (size_t)F)) return r;
+  if (int r = sc.put(w_t, t_ns, (size_t)n)) return r;
+  if (int r = sc.put(w_pts, points, (size_t)n * (size_t)ld)) return r;
   PointsF64Args a;
   std::memset(&a, 0, sizeof(a));
-  a.pts = reinterpret_cast<const double*>(base + 8 * w_pts); a.ld = ld; a.n = n;
-  a.t_ns = reinterpret_cast<const int64_t*>(base + 8 * w_t);
-  a.doff = reinterpret_cast<const int64_t*>(base + 8 * w_doff); a.F = F;
-  a.ftime = reinterpret_cast<const double*>(base + 8 * w_fv);
-  a.fstart = reinterpret_cast<const int64_t*>(base + 8 * w_fv);
+  a.pts = sc.at<const double>(w_pts); a.ld = ld; a.n = n;
+  a.t_ns = sc.at<const int64_t>(w_t);
+  a.doff = sc.at<const int64_t>(w_doff); a.F = F;
+  a.ftime = sc.at<const double>(w_fv);
+  a.fstart = sc.at<const int64_t>(w_fv);
   a.pose_time = c->d_time; a.pose_seg = static_cast<const PoseSeg*>(c->d_seg64); a.nseg = nseg;
   a.imu_ts = c->d_imu_ts; a.imu_seg = static_cast<const ImuSeg*>(c->d_seg64);
   a.ntab = mode == MC_MODE_POSE_SLERP ? c->T : c->M;
-  a.out = reinterpret_cast<double*>(base + 8 * w_out);
-  const int grid = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, zero_copy ? 1024 : 65536);
+  a.out = sc.at<double>(w_out);
   {
     TimedRegion tr(c, &c->main_ev, s);
-    if (mode == MC_MODE_POSE_SLERP) hipLaunchKernelGGL(k_points_f64<1>, dim3(grid), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL(k_points_f64<2>, dim3(grid), dim3(kBlock), 0, s, a);
+    if (mode == MC_MODE_POSE_SLERP) hipLaunchKernelGGL(k_points_f64<1>, dim3(sc.grid(n)), dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL(k_points_f64<2>, dim3(sc.grid(n)), dim3(kBlock), 0, s, a);
   }
   HIPCHK(hipGetLastError());
-  if (!zero_copy) HIPCHK(hipMemcpyAsync(out, a.out, (size_t)n * 32, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (zero_copy) std::memcpy(out, a.out, (size_t)n * 32);
-  return MC_OK;
+  return sc.fetch(out, w_out, 4 * (size_t)n);
 }
 
 // ---- host arrays <-> device: the row pipeline ------------------------------------------------
@@ -1241,7 +1187,7 @@ static void host_rows(mc_ctx* c, const std::vector<int64_t>& doff, int64_t r0, i
   c->pool->run((int64_t)jobs.size(), [&](int64_t j) { seg((int32_t)jobs[j][0], jobs[j][1], jobs[j][2]); });
 }
 
-// Chunk k's H2D (main stream) runs beside chunk k-1's D2H (side stream), and the host pool copies
+// Chunk k's H2D (main stream) runs beside chunk k-1's D2H (row_d2h stream), and the host pool copies
 // chunk k into pinned memory, and chunk k-1's rows out of it, while the DMA engines move the chunks
 // around them.  For 600 x 100k rows (profiles/round6/s04, s06, s18): one stream for both directions
 // 79-84 ms, two streams 58-66 ms into an already-faulted output (3.84 GB over PCIe; both directions
@@ -1266,13 +1212,13 @@ static int row_pipeline(mc_ctx* c, const double* const* frames, const int64_t* l
     pin[k] = reinterpret_cast<double*>(static_cast<char*>(c->h_pipe) + k * kPipeBytes);
     dev[k] = reinterpret_cast<double*>(static_cast<char*>(c->d_pipe) + k * kPipeBytes);
   }
-  hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr};
-  for (int b = 0; b < 2; ++b) {
-    HIPCHK(hipEventCreateWithFlags(&ev_in[b], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ev_out[b], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ev_k[b], hipEventDisableTiming));
-  }
-  hipStream_t s = c->stream, so = c->side;   // H2D + kernel | D2H
+  struct Events {   // destroyed on every return
+    hipEvent_t e[6] = {};
+    ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+  } ev;
+  hipEvent_t *ev_in = ev.e, *ev_out = ev.e + 2, *ev_k = ev.e + 4;   // per chunk parity
+  for (hipEvent_t& x : ev.e) HIPCHK(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+  hipStream_t s = c->stream, so = c->row_d2h;   // H2D + kernel | D2H
   auto copy_out = [&](int64_t k) {
     const double t0 = now();
     const int64_t r0 = k * rows_per, r1 = std::min(n, r0 + rows_per);
@@ -1305,7 +1251,7 @@ static int row_pipeline(mc_ctx* c, const double* const* frames, const int64_t* l
     t_in += now() - t0;
     hipError_t e = hipMemcpyAsync(dev[b], pin[b], (size_t)m * 32, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipEventRecord(ev_in[b], s);
-    // dev[2 + b] is free once chunk k-2's D2H (side stream) has finished
+    // dev[2 + b] is free once chunk k-2's D2H (row_d2h stream) has finished
     if (e == hipSuccess && k >= 2) e = hipStreamWaitEvent(s, ev_out[b], 0);
     if (e == hipSuccess) {
       TimedRegion tr(c, &c->main_ev, s);
@@ -1334,9 +1280,6 @@ static int row_pipeline(mc_ctx* c, const double* const* frames, const int64_t* l
   }
   (void)hipStreamSynchronize(so);
   (void)hipStreamSynchronize(s);
-  for (int b = 0; b < 2; ++b) {
-    (void)hipEventDestroy(ev_in[b]); (void)hipEventDestroy(ev_out[b]); (void)hipEventDestroy(ev_k[b]);
-  }
   if (trace)
     std::fprintf(stderr, "rowpipe rows %lld chunks %lld: total %.2f ms, copy-in %.2f, copy-out %.2f, wait-in %.2f, "
                  "wait-out %.2f ms\n", (long long)rows_per, (long long)K,
@@ -1353,14 +1296,13 @@ int mc_align_frames_host_f64(mc_ctx* c, int32_t F, const double* const* frames, 
   if (pose_select == MC_POSE_DIRECT && c->T != F)
     return fail(MC_ERR_INVALID, "MC_POSE_DIRECT needs one pose per frame (T=%lld, frames=%d)", (long long)c->T, F);
   CHECK_ARG(pose_select == MC_POSE_DIRECT || F == 0 || frame_times, "frame times are NULL");
-  std::vector<int64_t> doff((size_t)F + 1, 0);
-  for (int32_t f = 0; f < F; ++f) {
-    CHECK_ARG(counts[f] >= 0, "negative frame size at frame %d", f);
-    if (counts[f] > 0 && lds[f] < 4)
-      return fail(MC_ERR_INDEX, "index 3 is out of bounds for axis 1 with size %lld", (long long)lds[f]);
-    CHECK_ARG(counts[f] == 0 || (frames[f] && outs[f]), "NULL frame pointer at frame %d", f);
-    doff[f + 1] = doff[f] + counts[f];
-  }
+  std::vector<int64_t> doff;
+  if (int r = frame_offsets(counts, F, &doff, [&](int32_t f) {
+        if (counts[f] > 0 && lds[f] < 4)
+          return fail(MC_ERR_INDEX, "index 3 is out of bounds for axis 1 with size %lld", (long long)lds[f]);
+        CHECK_ARG(counts[f] == 0 || (frames[f] && outs[f]), "NULL frame pointer at frame %d", f);
+        return (int)MC_OK;
+      })) return r;
   const int64_t n = doff[F];
   if (n == 0) return MC_OK;
   DeviceGuard g(c->device);
@@ -1379,49 +1321,29 @@ int mc_affine_rows_f64(mc_ctx* c, int32_t F, const int64_t* counts, const double
   CHECK_ARG(ld == 3 || ld == 4, "rows need 3 or 4 columns (got %lld)", (long long)ld);
   CHECK_ARG(n_mats == 1 || n_mats == F, "need 1 or n_frames matrices (got %d for %d frames)", n_mats, F);
   CHECK_ARG(per_row >= MC_AFFINE_PER_FRAME && per_row <= MC_AFFINE_TRANSLATE, "unknown per_row mode %d", per_row);
-  std::vector<int64_t> doff((size_t)F + 1, 0);
-  for (int32_t f = 0; f < F; ++f) {
-    CHECK_ARG(counts[f] >= 0, "negative frame size at frame %d", f);
-    doff[f + 1] = doff[f] + counts[f];
-  }
+  std::vector<int64_t> doff;
+  if (int r = frame_offsets(counts, F, &doff)) return r;
   const int64_t n = doff[F];
   if (n == 0) return MC_OK;
   CHECK_ARG(rows && out, "NULL rows / out");
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
-  // [doff (F+1) | mats (12 n_mats) | rows (n, ld) | out (n, 3)] in 8-byte words: pinned and
-  // device-mapped below kZeroCopyRows rows, device staging with DMA above
+  // scratch: [doff (F+1) | mats (12 n_mats) | rows (n, ld) | out (n, 3)]
   const size_t w_mat = doff.size(), w_rows = w_mat + 12 * (size_t)n_mats, w_out = w_rows + (size_t)n * ld,
                words = w_out + 3 * (size_t)n;
-  const bool zero_copy = n < kZeroCopyRows;
-  char* base = nullptr;
-  hipStream_t s = c->stream;
-  if (zero_copy) {
-    if (int r = ctx_pin(c, words * 8, &base)) return r;
-    std::memcpy(base, doff.data(), doff.size() * 8);
-    std::memcpy(base + 8 * w_mat, mats, 12 * (size_t)n_mats * 8);
-    std::memcpy(base + 8 * w_rows, rows, (size_t)n * ld * 8);
-  } else {
-    void* st = nullptr;
-    if (int r = ctx_stage(c, words * 8, &st)) return r;
-    base = static_cast<char*>(st);
-    HIPCHK(hipMemcpyAsync(base, doff.data(), doff.size() * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(base + 8 * w_mat, mats, 12 * (size_t)n_mats * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(base + 8 * w_rows, rows, (size_t)n * ld * 8, hipMemcpyHostToDevice, s));
-  }
-  double* d_out = reinterpret_cast<double*>(base + 8 * w_out);
+  RowScratch sc;
+  if (int r = sc.open(c, n, words)) return r;
+  if (int r = sc.put(0, doff.data(), doff.size())) return r;
+  if (int r = sc.put(w_mat, mats, 12 * (size_t)n_mats)) return r;
+  if (int r = sc.put(w_rows, rows, (size_t)n * ld)) return r;
   {
-    TimedRegion tr(c, &c->main_ev, s);
-    const int grid = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, zero_copy ? 1024 : 65536);
-    hipLaunchKernelGGL(k_affine_rows_f64, dim3(grid), dim3(kBlock), 0, s,
-                       reinterpret_cast<const double*>(base + 8 * w_rows), ld, n, reinterpret_cast<const int64_t*>(base),
-                       F, reinterpret_cast<const double*>(base + 8 * w_mat), n_mats, per_row, d_out);
+    TimedRegion tr(c, &c->main_ev, c->stream);
+    hipLaunchKernelGGL(k_affine_rows_f64, dim3(sc.grid(n)), dim3(kBlock), 0, c->stream, sc.at<const double>(w_rows),
+                       ld, n, sc.at<const int64_t>(0), F, sc.at<const double>(w_mat), n_mats, per_row,
+                       sc.at<double>(w_out));
   }
   HIPCHK(hipGetLastError());
-  if (!zero_copy) HIPCHK(hipMemcpyAsync(out, d_out, (size_t)n * 24, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (zero_copy) std::memcpy(out, d_out, (size_t)n * 24);
-  return MC_OK;
+  return sc.fetch(out, w_out, 3 * (size_t)n);
 }
 
 int mc_transform_affine(mc_ctx* c, const mc_batch* in, mc_batch* out, int32_t n_mats, const double* mats,
@@ -1434,7 +1356,7 @@ int mc_transform_affine(mc_ctx* c, const mc_batch* in, mc_batch* out, int32_t n_
   DeviceGuard g(c->device);
   hipStream_t s = c->stream;
   // the frame table half not used by the last mc_deskew; main-stream order protects the previous
-  // reader of this half, the event hands it back to the next pipelined prep
+  // reader of this half, and the fence (queued_async) keeps the next prep behind this call's kernel
   const int h = c->buf;
   c->buf ^= 1;
   forget_speculation(c);   // half h is overwritten below
@@ -1461,7 +1383,6 @@ int mc_transform_affine(mc_ctx* c, const mc_batch* in, mc_batch* out, int32_t n_
     else hipLaunchKernelGGL(k_deskew_frame, grid, block, 0, s, da);
   }
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(c->ev_main_done[h], s));
   // the host table must outlive the (possibly pageable-staged) copy
   HIPCHK(hipStreamSynchronize(s));
   return MC_OK;
@@ -1640,8 +1561,9 @@ int mc_scan_count(mc_ctx* c, int32_t F, const double* frame_times, int pose_sele
 static int scan_emit(mc_ctx* c, mc_batch* out, const double* noise, double* d_local, double* d_aligned) {
   if (!c->scan_valid || c->scan_env_ver != c->env_ver)
     return fail(MC_ERR_STATE, "no mc_scan_count for the current scene (mc_set_environment since the count?)");
-  int64_t N = 0;
-  for (int64_t k : c->scan_counts) N += k;
+  std::vector<int64_t> doff;
+  if (int r = frame_offsets(c->scan_counts.data(), c->scan_F, &doff)) return r;
+  const int64_t N = doff[c->scan_F];
   if (c->scan_F == 0 || N == 0 || c->scan_tiles == 0) return MC_OK;
   DeviceGuard g(c->device);
   // staging: [noise (N, 3) | doff (F + 1)] (the rows path has no batch offsets of its own)
@@ -1651,8 +1573,6 @@ static int scan_emit(mc_ctx* c, mc_batch* out, const double* noise, double* d_lo
   double* d_noise = noise ? static_cast<double*>(st) : nullptr;
   int64_t* d_doff = reinterpret_cast<int64_t*>(static_cast<double*>(st) + noise_w);
   if (noise) HIPCHK(hipMemcpyAsync(d_noise, noise, noise_w * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  std::vector<int64_t> doff((size_t)c->scan_F + 1, 0);
-  for (int32_t f = 0; f < c->scan_F; ++f) doff[f + 1] = doff[f] + c->scan_counts[f];
   if (!out) HIPCHK(hipMemcpyAsync(d_doff, doff.data(), doff.size() * 8, hipMemcpyHostToDevice, c->stream));
   ScanEmitArgs ea;
   std::memset(&ea, 0, sizeof(ea));

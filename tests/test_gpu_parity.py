@@ -812,6 +812,69 @@ def test_host_array_paths_zero_copy_and_pipeline(mc, gpu_ctx):
         np.testing.assert_allclose(g, R.transform_pointcloud(s, p), rtol=0, atol=1e-9)
 
 
+def test_host_row_calls_agree_across_the_zero_copy_threshold(mc, gpu_ctx):
+    """The single host float64 row calls pick their memory by row count: pinned, device-mapped
+    scratch below 1 << 15 rows, device staging (or the row pipeline) from there on.  Per-row math
+    does not depend on that choice, so a frame of exactly that many rows and the same frame less its
+    last row agree bit for bit on the rows they share."""
+    N = 1 << 15   # kZeroCopyRows (csrc/hostutil.hpp): this test moves with the constant
+    rng = np.random.default_rng(33)
+    xyz = rng.uniform(-90, 90, (N, 3))
+    rows4 = np.column_stack([xyz, rng.uniform(0, 1, N)])
+    ends = [0, N - 2]
+
+    def same_bits(a, b):
+        return np.array_equal(np.ascontiguousarray(a).view(np.uint64), np.ascontiguousarray(b).view(np.uint64))
+
+    sim = mc.LiDARMotionSimulator(context=gpu_ctx)
+    pose = {"translation": rng.normal(0, 500, 3), "rotation": rng.uniform(-np.pi, np.pi, 3)}
+    big, small = sim.transform_pointcloud(rows4, pose), sim.transform_pointcloud(rows4[:N - 1], pose)
+    assert big.shape == (N, 4) and small.shape == (N - 1, 4)
+    assert same_bits(big[:N - 1], small)
+    assert_scaled_close(small[ends, :3], R.transform_pointcloud(rows4[ends], pose)[:, :3],
+                        scale_of(xyz[ends], pose["translation"]), what="transform_pointcloud")
+
+    ts = np.arange(0, 2_000_000_000, 5_000_000, dtype=np.int64)
+    gyro = rng.normal(0, 0.8, (len(ts), 3))
+    gpu_ctx.set_imu(ts, gyro)
+    T = 200
+    tr = {"time": np.linspace(0, 20, T), "position_gps": np.cumsum(rng.normal(0, 0.5, (T, 3)), axis=0),
+          "orientation_imu": np.cumsum(rng.normal(0, 0.1, (T, 3)), axis=0)}
+    gpu_ctx.set_trajectory(tr["time"], tr["position_gps"], tr["orientation_imu"])
+    t_rel = rng.integers(0, 100_000_000, N)
+    start, ftime = 500_000_000, 7.25
+    for mode, kw in (("imu", {"frame_start_ns": [start]}), ("pose_slerp", {"frame_times": [ftime]})):
+        big = mc.runtime.deskew_points_f64(gpu_ctx, mode, [N], xyz, t_rel, **kw)
+        small = mc.runtime.deskew_points_f64(gpu_ctx, mode, [N - 1], xyz[:N - 1], t_rel[:N - 1], **kw)
+        assert big.shape == (N, 4) and small.shape == (N - 1, 4)
+        assert same_bits(big[:N - 1], small), mode
+        if mode == "imu":
+            ref, sc = R.compensate_arrays(xyz[ends], start + t_rel[ends], start, ts, gyro), scale_of(xyz[ends])
+        else:
+            ref = R.deskew_pose_slerp(xyz[ends], t_rel[ends], ftime, tr)
+            _, p = R.slerp_pose(tr["time"], tr["position_gps"], tr["orientation_imu"], ftime + t_rel[ends] * 1e-9)
+            sc = scale_of(xyz[ends], p)
+        assert_scaled_close(big[ends, :3], ref, sc, what=mode)
+
+    mats = np.concatenate([rng.normal(0, 1, (2, 3, 3)), rng.normal(0, 100, (2, 3, 1))], axis=2)
+    for rows in (xyz, np.column_stack([xyz, np.ones(N)])):
+        cols = rows.shape[1]
+        big = gpu_ctx.affine_rows([N], rows, mats[0])
+        small = gpu_ctx.affine_rows([N - 1], rows[:N - 1], mats[0])
+        assert big.shape == (N, 3) and small.shape == (N - 1, 3)
+        assert same_bits(big[:N - 1], small), cols
+        ref = xyz[ends] @ mats[0][:, :3].T + mats[0][:, 3]
+        assert_scaled_close(small[ends], ref, scale_of(xyz[ends], mats[0][:, 3]), what=f"affine_rows {cols}")
+        # two frames, one matrix each, N and N - 1 rows in all: the offsets and the second matrix are
+        # found in either memory (the last frame's five rows are the same inputs in both runs)
+        big = gpu_ctx.affine_rows([N - 5, 5], rows, mats)
+        small = gpu_ctx.affine_rows([N - 6, 5], np.concatenate([rows[:N - 6], rows[N - 5:]]), mats)
+        assert same_bits(big[N - 5:], small[N - 6:]), cols
+        assert same_bits(big[:N - 6], small[:N - 6]), cols
+        ref = xyz[N - 5:] @ mats[1][:, :3].T + mats[1][:, 3]
+        assert_scaled_close(small[N - 6:], ref, scale_of(xyz[N - 5:], mats[1][:, 3]), what=f"affine_rows {cols} x2")
+
+
 @pytest.mark.parametrize("mode", ["pose_slerp", "frame"])
 def test_launch_spans_match_events(mc, gpu_ctx, mode):
     """mc_timing_read_spans: every timed deskew launch's own workgroup span (the bench line's
