@@ -430,6 +430,17 @@ __device__ __forceinline__ PoseWin make_pose_win(const PoseSeg& s, double tf) {
   return w;
 }
 
+// The time of a point as the reference forms it, t_frame + t_ns * 1e-9: the product rounded, then
+// the sum.  Contraction is switched off here by pragma: __dmul_rn / __dadd_rn are a plain * and + in
+// the HIP headers, which the compiler fused into one fma in some instantiations of the deskew kernel
+// and not in others; the single rounding moves the time by an ulp (alpha by ~1e-13 .. 1e-12) on a few
+// per cent of the points of a frame that spans seconds (tests/test_gpu_rounding.py).
+__device__ __forceinline__ double slerp_time(double tf, double t_ns) {
+#pragma clang fp contract(off)
+  const double dt = t_ns * 1e-9;
+  return tf + dt;
+}
+
 // smallest integer n with tf + n*1e-9 >= t_abs (segment boundary in frame-relative ns)
 __device__ __forceinline__ int64_t rel_ns_ceil(double t_abs, double tf) {
   double v = ceil((t_abs - tf) * 1e9);
@@ -696,7 +707,7 @@ __device__ __forceinline__ void prep_body(const PrepArgs& a, int64_t block) {
   if (has) {
     int64_t c0 = -1, c1 = -1;
     if (MODE == 1) {
-      const double x0 = tf + (double)tr.x * 1e-9, x1 = tf + (double)tr.y * 1e-9;
+      const double x0 = slerp_time(tf, (double)tr.x), x1 = slerp_time(tf, (double)tr.y);
       c0 = probe_count<false>(pv.t, base, a.T, x0);
       c1 = probe_count<false>(pv.t, base, a.T, x1);
       if (c0 < 0 || c1 < 0) wave_count2<false>(a.time, a.T, x0, x1, &c0, &c1);
@@ -1204,8 +1215,6 @@ __device__ __forceinline__ void slerp_core(const PoseWin& w, const P& poly, doub
   y = (V)fma(2.0, cy, fma(al, w.dp[1], Y) + w.p0[1]);
   z = (V)fma(2.0, cz, fma(al, w.dp[2], Z) + w.p0[2]);
 }
-// the time formed as the reference forms it, t_frame + t_ns * 1e-9 (no contraction)
-__device__ __forceinline__ double slerp_time(double tf, double t_ns) { return __dadd_rn(tf, __dmul_rn(t_ns, 1e-9)); }
 template <typename P>
 __device__ __forceinline__ void slerp_point(const PoseWin& w, const P& poly, int t, float& x, float& y, float& z) {
   slerp_core(w, poly, slerp_time(w.tf, (double)t), x, y, z);
@@ -1498,7 +1507,7 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
         const double tf = a.frame_time[f];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          int64_t k = upper_bound(a.pose_time, a.ntab, __dadd_rn(tf, __dmul_rn((double)i4c(Tq, c), 1e-9))) - 1;
+          int64_t k = upper_bound(a.pose_time, a.ntab, slerp_time(tf, (double)i4c(Tq, c))) - 1;
           k = k > a.nseg - 1 ? a.nseg - 1 : (k < 0 ? 0 : k);
           seg[c] = act ? (int)k : -1;
         }

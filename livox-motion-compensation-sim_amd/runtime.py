@@ -25,6 +25,14 @@ def _f64(a, shape_tail=None):
     return a
 
 
+def _release(fn, ctx, *args):
+    """Finalizer of an object that lives in a context (a batch, a device buffer): ``fn(*args)``.
+    ``ctx`` is held by the finalizer itself, so the context is destroyed after everything in it even
+    when both become unreachable in one garbage cycle (frames kept by a traceback), where finalizers
+    run in no particular order and mc_batch_destroy / mc_device_free would touch a freed context."""
+    fn(*args)
+
+
 class Context:
     """One device + stream.  ``device`` defaults to $MCDESKEW_DEVICE, else $LOCAL_RANK modulo the
     visible devices (a launcher that gives each rank its own HIP_VISIBLE_DEVICES leaves every rank
@@ -345,7 +353,7 @@ class DeviceBuffer:
         p = c_void_p()
         check(self.lib.mc_device_alloc(ctx.handle, self.nbytes, ctypes.byref(p)), "device_alloc")
         self.ptr = p
-        self._fin = weakref.finalize(self, self.lib.mc_device_free, ctx.handle, p)
+        self._fin = weakref.finalize(self, _release, self.lib.mc_device_free, ctx, ctx.handle, p)
 
     def close(self):
         self._fin()
@@ -381,7 +389,7 @@ class Batch:
         check(self.lib.mc_batch_create(ctx.handle, len(self.counts), ptr(self.counts, c_int64), flags,
                                        ctypes.byref(h)), "batch_create")
         self.handle = h
-        self._fin = weakref.finalize(self, self.lib.mc_batch_destroy, h)
+        self._fin = weakref.finalize(self, _release, self.lib.mc_batch_destroy, ctx, h)
         n, p = c_int64(), c_int64()
         f, t = c_int32(), c_int32()
         check(self.lib.mc_batch_info(h, ctypes.byref(n), ctypes.byref(p), ctypes.byref(f), ctypes.byref(t)))

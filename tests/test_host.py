@@ -241,3 +241,38 @@ def test_host_pool_recycles_blocks_only_after_every_view_dies():
     assert pool.idle_bytes() == 32_000 + 9_600
     pool.clear()
     assert pool.idle_bytes() == 0
+
+
+def test_a_context_outlives_its_batches_in_one_garbage_cycle():
+    """A batch's and a device buffer's finalizer call into their context (mc_batch_destroy syncs its
+    stream).  When context and batches become unreachable together, in one reference cycle (the frames
+    of a failed test's traceback hold both), finalizers run in no particular order: each batch and
+    buffer must keep its context alive until its own finalizer has run.  A recording stand-in for the
+    library, no GPU."""
+    import ctypes
+    import gc
+    import weakref
+    rt = pkg().runtime
+    log = []
+
+    class Lib:
+        def mc_batch_create(self, *a): return 0
+        def mc_batch_info(self, *a): return 0
+        def mc_device_alloc(self, *a): return 0
+        def mc_batch_destroy(self, h): log.append("batch"); return 0
+        def mc_device_free(self, c, p): log.append("buffer"); return 0
+        def mc_destroy(self, h): log.append("context"); return 0
+
+    for order in range(12):
+        del log[:]
+        ctx = rt.Context.__new__(rt.Context)
+        ctx.lib, ctx.handle, ctx.device = Lib(), ctypes.c_void_p(), 0
+        ctx._fin = weakref.finalize(ctx, ctx.lib.mc_destroy, ctx.handle)     # as Context.__init__ registers it
+        things = [rt.Batch(ctx, [3, 0, 5]), rt.DeviceBuffer(ctx, 64), rt.Batch(ctx, [1], with_time=True)]
+        cycle = {"things": things[order % 3:] + things[:order % 3]}
+        if order % 2:
+            cycle["ctx"] = ctx
+        cycle["self"] = cycle
+        del ctx, things, cycle
+        gc.collect()
+        assert sorted(log[:3]) == ["batch", "batch", "buffer"] and log[3:] == ["context"], (order, log)
