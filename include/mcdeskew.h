@@ -26,6 +26,8 @@
  *                                                              on a device batch
  *     _interpolate_imu_data                    CSIM:1482-1516    (per-point gyro LERP in-kernel)
  *     _create_rotation_matrix                  CSIM:1518-1536    (R_xyz(theta)^T in-kernel)
+ *   LiDARSimulator.simulate_scan / _raycast    CSIM:1011-1146  mc_set_ray_scene + mc_ray_count +
+ *     (per frame of _simulate_lidar_frames     CSIM:2028-2084)   mc_ray_emit / mc_ray_emit_f64
  *   (build-added)                          mc_deskew(MC_MODE_POSE_SLERP)
  *
  * LMC = lidar_motion_compensation.py, CSIM = livox_mid70_complete_simulator.py.
@@ -176,6 +178,36 @@ int mc_scan_emit(mc_ctx* ctx, mc_batch* out, const double* noise);
  * accumulates as numpy's matmul does.  Synchronous. */
 int mc_scan_emit_f64(mc_ctx* ctx, const double* noise, double* d_local, double* d_aligned);
 int mc_timing_read_scan(mc_ctx* ctx, double* ms_total, int64_t* launches);
+
+/* ---- LiDARSimulator.simulate_scan, the ray-march scanner behind Path B's frames (CSIM:1011-1146) -- */
+/* The scene of _raycast (CSIM:1108-1146): n_objects point objects in list order, counts[o] rows each
+ * (0 allowed: the reference skips empty objects, CSIM:1126), their rows (sum(counts), ld >= 4) float64
+ * [x, y, z, intensity, ...] back to back; an object without an intensity column carries the
+ * reference's 100 (CSIM:1140) in column 3.  Copied to the device; replaces any previous ray scene. */
+int mc_set_ray_scene(mc_ctx* ctx, int32_t n_objects, const int64_t* counts, const double* rows, int64_t ld);
+/* Pass 1 for F frames of n_rays rays each (simulate_scan's loop CSIM:1021-1031 over every frame of
+ * _simulate_lidar_frames, CSIM:2037-2060, in one launch): origins (F, 3) sensor positions, R (F, 3, 3)
+ * = R_z R_y R_x of the sensor orientation (CSIM:1105), dirs (n_rays, 3) the sensor-frame directions
+ * (CSIM:1083-1086), steps[n_steps] = np.arange(range_min, range_max, step_size) (CSIM:1121) and
+ * step_size, the march step and hit radius (CSIM:1118, 1131).  Every ray's first hit as the reference
+ * decides it (first step with a point closer than step_size; first object in list order; closest
+ * point, lowest index on ties).  counts_out[F] = hits per frame.  Synchronous. */
+int mc_ray_count(mc_ctx* ctx, int32_t n_frames, const double* origins, const double* R, int32_t n_rays,
+                 const double* dirs, int32_t n_steps, const double* steps, double step_size, int64_t* counts_out);
+/* The last mc_ray_count's discrete result: hits_out (n_frames * n_rays, 3) int32 = step, object,
+ * point index within the object (CSIM:1134-1135), or -1, -1, -1 for a miss. */
+int mc_ray_hits(mc_ctx* ctx, int32_t* hits_out);
+/* Pass 2 (CSIM:1033-1053): per hit, in frame and ray order, sensor_point = R_inv (hit_point -
+ * position) with R_inv (F, 3, 3) = R_x(-roll) R_y(-pitch) R_z(-yaw) (CSIM:1170) plus noise, and the
+ * hit's intensity plus noise clipped to [0, 255].  noise (sum(counts_out), 4) float64 = the three
+ * range draws and the intensity draw of each hit (CSIM:1038-1039), or NULL for none.  mc_ray_emit
+ * writes a batch created with counts_out as frame counts: float32 x, y, z, intensity and, with
+ * MC_BATCH_WITH_TIME, t_ns = 1000 * ray index (CSIM:1048).  mc_ray_emit_f64 writes host rows
+ * (sum(counts_out), 5) float64 = x, y, z, intensity (not yet truncated by int(), CSIM:1047), ray
+ * index.  MC_ERR_STATE when the ray scene changed since the count.  Synchronous. */
+int mc_ray_emit(mc_ctx* ctx, mc_batch* out, const double* R_inv, const double* noise);
+int mc_ray_emit_f64(mc_ctx* ctx, const double* R_inv, const double* noise, double* rows_out);
+int mc_timing_read_ray(mc_ctx* ctx, double* ms_total, int64_t* launches);
 
 /* ---- output codecs, encoded from a device (N, ld) float64 AoS cloud whose
  * frames lie back to back (counts[f] rows each): the array layout the reference hands its writers.

@@ -84,6 +84,12 @@ _SIGS = {
     "mc_scan_emit": (c_int, [c_void_p, c_void_p, _pd]),
     "mc_scan_emit_f64": (c_int, [c_void_p, _pd, c_void_p, c_void_p]),
     "mc_timing_read_scan": (c_int, [c_void_p, _pd, _pi64]),
+    "mc_set_ray_scene": (c_int, [c_void_p, c_int32, _pi64, _pd, c_int64]),
+    "mc_ray_count": (c_int, [c_void_p, c_int32, _pd, _pd, c_int32, _pd, c_int32, _pd, c_double, _pi64]),
+    "mc_ray_hits": (c_int, [c_void_p, _pi32]),
+    "mc_ray_emit": (c_int, [c_void_p, c_void_p, _pd, _pd]),
+    "mc_ray_emit_f64": (c_int, [c_void_p, _pd, _pd, _pd]),
+    "mc_timing_read_ray": (c_int, [c_void_p, _pd, _pi64]),
     "mc_lvx_layout": (c_int, [c_int32, _pi64, _pi64]),
     "mc_lvx_encode": (c_int, [c_void_p, c_void_p, c_int64, c_int32, _pi64, POINTER(c_uint64), POINTER(c_uint64),
                               POINTER(ctypes.c_uint8), c_void_p, c_int64]),

@@ -141,6 +141,24 @@ struct mc_ctx {
   uint64_t env_ver = 0, scan_env_ver = 0;
   bool scan_valid = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> scan_ev;
+  // ray-march scanner state (CSIM:1011-1146, raymarch.hpp): the scene of point objects as columns
+  // plus each point's object, then what the last mc_ray_count left for its emit
+  int64_t ray_E = 0;
+  double* d_ray_scene = nullptr;            // x, y, z, intensity columns
+  int32_t* d_ray_obj = nullptr;             // object (list position) of every scene point
+  std::vector<int64_t> ray_obj_start;       // first scene index of every object (n_objects + 1)
+  uint64_t ray_scene_ver = 0, ray_count_ver = 0;
+  bool ray_valid = false;
+  int32_t ray_F = 0, ray_n = 0, ray_K = 0;
+  double* d_ray_frame = nullptr;            // per frame: origin (3), R (9)
+  double* d_ray_dirs = nullptr;
+  double* d_ray_steps = nullptr;
+  void* d_ray_part = nullptr;               // per-chunk keys of the count pass
+  size_t ray_part_bytes = 0;
+  void* d_ray_hit = nullptr;                // RayHit per (frame, ray)
+  std::vector<int64_t> ray_counts;          // hits per frame of the last mc_ray_count
+  std::vector<int32_t> ray_hits;            // (F * n_rays, 3): step, object, point index in the object
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ray_ev;
   // output codecs: per-call frame / unit tables carved from one scratch buffer, error flag
   void* d_codec = nullptr;
   size_t codec_bytes = 0;

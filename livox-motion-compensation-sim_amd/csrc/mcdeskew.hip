@@ -7,6 +7,7 @@
 #include "kernels.hpp"
 #include <hip/hip_ext.h>
 #include "scan.hpp"
+#include "raymarch.hpp"
 #include "internal.hpp"
 #include "hostutil.hpp"
 #include "plan.hpp"
@@ -158,9 +159,12 @@ static void ctx_release(mc_ctx* c) {
   dev_free(c->d_env); dev_free(c->d_scan_pose); dev_free(c->d_scan_tcount);
   dev_free(c->d_scan_toff); dev_free(c->d_scan_nvis); dev_free(c->d_scan_bits);
   dev_free(c->d_codec_err); dev_free(c->d_pcd_len); dev_free(c->d_span);
-  for (void* p : {c->d_codec, c->d_seg64, c->d_pipe, c->d_stage}) if (p) (void)hipFree(p);
+  dev_free(c->d_ray_scene); dev_free(c->d_ray_obj); dev_free(c->d_ray_frame); dev_free(c->d_ray_dirs);
+  dev_free(c->d_ray_steps);
+  for (void* p : {c->d_codec, c->d_seg64, c->d_pipe, c->d_stage, c->d_ray_part, c->d_ray_hit}) if (p) (void)hipFree(p);
   for (void* p : {c->h_pin, c->h_pipe}) if (p) (void)hipHostFree(p);
-  for (EventPairs* v : {&c->codec_ev, &c->main_ev, &c->scan_ev, &c->prep_ev, &c->layout_ev}) ev_recycle(c, *v);
+  for (EventPairs* v : {&c->codec_ev, &c->main_ev, &c->scan_ev, &c->ray_ev, &c->prep_ev, &c->layout_ev})
+    ev_recycle(c, *v);
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);
   if (c->row_d2h) (void)hipStreamDestroy(c->row_d2h);
   if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1618,6 +1622,209 @@ int mc_timing_read_scan(mc_ctx* c, double* ms, int64_t* n) {
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
   return sum_events(c, c->scan_ev, ms, n);
+}
+
+// ---- LiDARSimulator.simulate_scan, the ray-march scanner (CSIM:1011-1146) --------------------
+int mc_set_ray_scene(mc_ctx* c, int32_t n_objects, const int64_t* counts, const double* rows, int64_t ld) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(n_objects >= 0 && (n_objects == 0 || counts), "object counts are NULL");
+  if (ld < 4) return fail(MC_ERR_INDEX, "scene rows need 4 columns (x, y, z, intensity); got %lld", (long long)ld);
+  std::vector<int64_t> start;
+  if (int r = frame_offsets(counts, n_objects, &start)) return r;
+  const int64_t n = start[n_objects];
+  CHECK_ARG(n == 0 || rows, "scene pointer is NULL");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  ++c->ray_scene_ver;        // any earlier mc_ray_count's result is now stale
+  c->ray_valid = false;
+  dev_free(c->d_ray_scene); dev_free(c->d_ray_obj);
+  c->ray_E = 0;
+  if (int r = dev_alloc(&c->d_ray_scene, std::max<size_t>(scene_words(n), 1))) return r;
+  if (int r = dev_alloc(&c->d_ray_obj, std::max<size_t>((size_t)n, 1))) return r;
+  if (n > 0) {
+    std::vector<double> h(scene_words(n));
+    std::vector<int32_t> ho((size_t)n);
+    for (int32_t o = 0; o < n_objects; ++o)
+      for (int64_t i = start[o]; i < start[o + 1]; ++i) {
+        const double* q = rows + i * ld;
+        h[i] = q[0]; h[n + i] = q[1]; h[2 * n + i] = q[2]; h[3 * n + i] = q[3];
+        ho[i] = o;
+      }
+    HIPCHK(hipMemcpyAsync(c->d_ray_scene, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_ray_obj, ho.data(), ho.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  c->ray_obj_start = std::move(start);
+  c->ray_E = n;
+  return MC_OK;
+}
+
+int mc_ray_count(mc_ctx* c, int32_t F, const double* origins, const double* R, int32_t n_rays, const double* dirs,
+                 int32_t n_steps, const double* steps, double step_size, int64_t* counts_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(F >= 0 && n_rays >= 0 && n_steps >= 0, "negative size");
+  CHECK_ARG(F == 0 || (origins && R && counts_out), "NULL frame argument");
+  CHECK_ARG(n_rays == 0 || dirs, "ray directions are NULL");
+  CHECK_ARG(n_steps == 0 || steps, "step table is NULL");
+  CHECK_ARG(step_size > 0.0, "step size must be positive");
+  CHECK_ARG(n_rays <= 2000000, "at most 2000000 rays per frame (t_ns = 1000 i is an int32)");
+  const int64_t NR = (int64_t)F * n_rays;
+  const int64_t units = (NR + kBlock - 1) / kBlock;   // workgroups of kBlock consecutive rays
+  CHECK_ARG(units <= (1 << 22), "too many rays for one launch");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  c->ray_valid = false;
+  dev_free(c->d_ray_frame); dev_free(c->d_ray_dirs); dev_free(c->d_ray_steps);
+  if (c->d_ray_hit) { (void)hipFree(c->d_ray_hit); c->d_ray_hit = nullptr; }
+  if (int r = dev_alloc(&c->d_ray_frame, 12 * (size_t)std::max(F, 1))) return r;
+  if (int r = dev_alloc(&c->d_ray_dirs, 3 * (size_t)std::max(n_rays, 1))) return r;
+  if (int r = dev_alloc(&c->d_ray_steps, (size_t)std::max(n_steps, 1))) return r;
+  HIPCHK(hipMalloc(&c->d_ray_hit, std::max<size_t>((size_t)NR, 1) * sizeof(RayHit)));
+  c->ray_F = F; c->ray_n = n_rays; c->ray_K = n_steps;
+  c->ray_counts.assign(F, 0);
+  c->ray_hits.assign(3 * (size_t)NR, -1);
+  c->ray_count_ver = c->ray_scene_ver;
+  for (int32_t f = 0; f < F; ++f) counts_out[f] = 0;
+  const int32_t n_tiles = (int32_t)((c->ray_E + kRayTile - 1) / kRayTile);
+  if (NR == 0 || n_steps == 0 || n_tiles == 0) {   // nothing to march or nothing to hit: all misses
+    c->ray_valid = true;
+    return MC_OK;
+  }
+  std::vector<double> frame(12 * (size_t)F);
+  for (int32_t f = 0; f < F; ++f) {
+    std::memcpy(&frame[12 * (size_t)f], origins + 3 * (size_t)f, 3 * sizeof(double));
+    std::memcpy(&frame[12 * (size_t)f + 3], R + 9 * (size_t)f, 9 * sizeof(double));
+  }
+  HIPCHK(hipMemcpyAsync(c->d_ray_frame, frame.data(), frame.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_ray_dirs, dirs, 3 * (size_t)n_rays * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(c->d_ray_steps, steps, (size_t)n_steps * 8, hipMemcpyHostToDevice, c->stream));
+  // scene chunks: enough workgroups to fill the device (or mc_set_launch's cap); the merged result does
+  // not depend on the choice
+  const int64_t target = c->max_grid > 0 ? c->max_grid : 8192;
+  int32_t n_chunks = (int32_t)std::min<int64_t>(n_tiles, std::max<int64_t>(1, target / units));
+  const int32_t chunk_tiles = (n_tiles + n_chunks - 1) / n_chunks;
+  n_chunks = (n_tiles + chunk_tiles - 1) / chunk_tiles;
+  const size_t part_bytes = (size_t)NR * n_chunks * sizeof(RayKey);
+  if (part_bytes > c->ray_part_bytes) {
+    if (c->d_ray_part) { (void)hipFree(c->d_ray_part); c->d_ray_part = nullptr; }
+    c->ray_part_bytes = 0;
+    HIPCHK(hipMalloc(&c->d_ray_part, part_bytes));
+    c->ray_part_bytes = part_bytes;
+  }
+  RayCountArgs a;
+  a.scene = c->d_ray_scene; a.E = c->ray_E; a.obj = c->d_ray_obj;
+  a.frame = c->d_ray_frame; a.dirs = c->d_ray_dirs; a.n_rays = n_rays;
+  a.steps = c->d_ray_steps; a.m = make_ray_march(steps, n_steps, step_size);
+  a.F = F; a.n_groups = (int32_t)units; a.n_chunks = n_chunks;
+  a.chunk_pts = (int64_t)chunk_tiles * kRayTile;
+  a.partial = static_cast<RayKey*>(c->d_ray_part);
+  {
+    TimedRegion tr(c, &c->ray_ev, c->stream);
+    hipLaunchKernelGGL(k_ray_count, dim3((uint32_t)(units * n_chunks)), dim3(kBlock), 0, c->stream, a);
+    hipLaunchKernelGGL(k_ray_merge, dim3((uint32_t)((NR + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       a.partial, NR, n_chunks, static_cast<RayHit*>(c->d_ray_hit));
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<RayHit> hit((size_t)NR);
+  HIPCHK(hipMemcpyAsync(hit.data(), c->d_ray_hit, hit.size() * sizeof(RayHit), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int32_t f = 0; f < F; ++f) {
+    int64_t n = 0;
+    for (int32_t i = 0; i < n_rays; ++i) {
+      const RayHit& h = hit[(size_t)f * n_rays + i];
+      if (h.step < 0) continue;
+      ++n;
+      int32_t* q = &c->ray_hits[3 * ((size_t)f * n_rays + i)];
+      q[0] = h.step; q[1] = h.obj; q[2] = (int32_t)(h.idx - c->ray_obj_start[h.obj]);
+    }
+    c->ray_counts[f] = n;
+    counts_out[f] = n;
+  }
+  c->ray_valid = true;
+  return MC_OK;
+}
+
+int mc_ray_hits(mc_ctx* c, int32_t* hits_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  if (!c->ray_valid) return fail(MC_ERR_STATE, "no mc_ray_count result");
+  CHECK_ARG(c->ray_hits.empty() || hits_out, "output pointer is NULL");
+  if (!c->ray_hits.empty()) std::memcpy(hits_out, c->ray_hits.data(), c->ray_hits.size() * sizeof(int32_t));
+  return MC_OK;
+}
+
+// pass 2 of the last mc_ray_count: a batch's float32 columns (out != nullptr) or host float64 rows
+static int ray_emit(mc_ctx* c, mc_batch* out, const double* rinv, const double* noise, double* rows_out) {
+  if (!c->ray_valid || c->ray_count_ver != c->ray_scene_ver)
+    return fail(MC_ERR_STATE, "no mc_ray_count for the current scene (mc_set_ray_scene since the count?)");
+  const int32_t F = c->ray_F;
+  std::vector<int64_t> doff;
+  if (int r = frame_offsets(c->ray_counts.data(), F, &doff)) return r;
+  const int64_t H = doff[F];
+  if (H == 0) return MC_OK;
+  CHECK_ARG(rinv, "R_inv is NULL");
+  CHECK_ARG(out || rows_out, "output pointer is NULL");
+  DeviceGuard g(c->device);
+  // staging: [R_inv (F, 9) | doff (F + 1) | noise (H, 4) | rows (H, 5)]
+  const size_t w_rinv = 9 * (size_t)F, w_doff = (size_t)F + 1, w_noise = noise ? 4 * (size_t)H : 0;
+  const size_t w_rows = out ? 0 : 5 * (size_t)H;
+  void* st = nullptr;
+  if (int r = ctx_stage(c, (w_rinv + w_doff + w_noise + w_rows) * 8, &st)) return r;
+  double* d_rinv = static_cast<double*>(st);
+  int64_t* d_doff = reinterpret_cast<int64_t*>(d_rinv + w_rinv);
+  double* d_noise = d_rinv + w_rinv + w_doff;
+  double* d_rows = d_noise + w_noise;
+  HIPCHK(hipMemcpyAsync(d_rinv, rinv, w_rinv * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_doff, doff.data(), w_doff * 8, hipMemcpyHostToDevice, c->stream));
+  if (noise) HIPCHK(hipMemcpyAsync(d_noise, noise, w_noise * 8, hipMemcpyHostToDevice, c->stream));
+  RayEmitArgs ea;
+  std::memset(&ea, 0, sizeof(ea));
+  ea.scene = c->d_ray_scene; ea.E = c->ray_E;
+  ea.frame = c->d_ray_frame; ea.rinv = d_rinv; ea.dirs = c->d_ray_dirs; ea.n_rays = c->ray_n;
+  ea.steps = c->d_ray_steps; ea.hit = static_cast<const RayHit*>(c->d_ray_hit);
+  ea.noise = noise ? d_noise : nullptr;
+  ea.doff = d_doff;
+  if (out) {
+    ea.poff = out->d_poff; ea.cols = out->d_cols; ea.C = out->C;
+    out->wrote(false);
+    ea.pcd_len = out->d_pcd_len;   // MC_BATCH_WITH_PCD_LEN: per-point atomic adds into zeroed slots
+    if (ea.pcd_len) HIPCHK(hipMemsetAsync(ea.pcd_len, 0, (size_t)(out->P / kBlkPts) * sizeof(int32_t), c->stream));
+  } else {
+    ea.rows = d_rows;
+  }
+  {
+    TimedRegion tr(c, &c->ray_ev, c->stream);
+    if (out) hipLaunchKernelGGL(k_ray_emit<false>, dim3((uint32_t)F), dim3(kBlock), 0, c->stream, ea);
+    else hipLaunchKernelGGL(k_ray_emit<true>, dim3((uint32_t)F), dim3(kBlock), 0, c->stream, ea);
+  }
+  HIPCHK(hipGetLastError());
+  if (!out) HIPCHK(hipMemcpyAsync(rows_out, d_rows, w_rows * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (out) {
+    out->wrote(true);
+    if (out->has_t()) if (int r = compute_trange(out)) return r;   // the t_ns column was written
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return MC_OK;
+}
+
+int mc_ray_emit(mc_ctx* c, mc_batch* out, const double* R_inv, const double* noise) {
+  CHECK_ARG(c && out, "NULL argument");
+  CHECK_ARG(out->ctx == c, "batch belongs to another context");
+  if (c->ray_valid && out->counts != c->ray_counts)
+    return fail(MC_ERR_INVALID, "output batch frame counts differ from the last mc_ray_count");
+  return ray_emit(c, out, R_inv, noise, nullptr);
+}
+
+int mc_ray_emit_f64(mc_ctx* c, const double* R_inv, const double* noise, double* rows_out) {
+  CHECK_ARG(c, "ctx is NULL");
+  return ray_emit(c, nullptr, R_inv, noise, rows_out);
+}
+
+int mc_timing_read_ray(mc_ctx* c, double* ms, int64_t* n) {
+  CHECK_ARG(c, "ctx is NULL");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  return sum_events(c, c->ray_ev, ms, n);
 }
 
 int mc_timing_read_layout(mc_ctx* c, double* ms, int64_t* n) {
