@@ -12,14 +12,14 @@ CSIM paths is 3e-15 * scale, here scale = |origin| 
 of the terms that are summed.  The same absolute bar holds for the sensor-frame point R_inv (hit -
 position), a rotation of that difference.
 """
-import ctypes
-from ctypes import c_double, c_int32, c_int64
+from ctypes import c_double, c_int64
 
 import numpy as np
 import pytest
 
 import raymarch as RM
 from conftest import golden
+from raymarch import abi_count, abi_rows, ptr as _p
 
 pytestmark = pytest.mark.gpu
 BAR = 3e-15
@@ -33,37 +33,6 @@ def gold():
 @pytest.fixture(scope="module")
 def frames():
     return RM.golden_frames()
-
-
-def _p(a, t):
-    return a.ctypes.data_as(ctypes.POINTER(t))
-
-
-def abi_count(mc, ctx, cfg, positions, orientations, objects, set_scene=True):
-    """mc_set_ray_scene + mc_ray_count + mc_ray_hits; returns (counts, hits (F, n, 3), R_inv)."""
-    lib = ctx.lib
-    ctx._ray_scene_last = None      # the Python layer's upload cache does not see this direct call
-    if set_scene:
-        counts, rows = mc.raymarch.scene_rows(objects)
-        mc._lib.check(lib.mc_set_ray_scene(ctx.handle, len(counts), _p(counts, c_int64), _p(rows, c_double), 4))
-    pos = np.ascontiguousarray(np.atleast_2d(positions), dtype=np.float64)
-    rot = [RM.rotations(o) for o in np.atleast_2d(orientations)]
-    R = np.ascontiguousarray([r[0] for r in rot])
-    Rinv = np.ascontiguousarray([r[1] for r in rot])
-    dirs, steps = RM.directions(cfg), np.ascontiguousarray(RM.steps_of(cfg))
-    n = np.zeros(len(pos), np.int64)
-    mc._lib.check(lib.mc_ray_count(ctx.handle, len(pos), _p(pos, c_double), _p(R, c_double), len(dirs),
-                                   _p(dirs, c_double), len(steps), _p(steps, c_double), RM.STEP, _p(n, c_int64)))
-    hits = np.zeros((len(pos) * len(dirs), 3), np.int32)
-    mc._lib.check(lib.mc_ray_hits(ctx.handle, _p(hits, c_int32)))
-    return n, hits.reshape(len(pos), len(dirs), 3), Rinv
-
-
-def abi_rows(mc, ctx, Rinv, noise, n_hits):
-    rows = np.zeros((n_hits, 5), np.float64)
-    mc._lib.check(ctx.lib.mc_ray_emit_f64(ctx.handle, _p(Rinv, c_double), None if noise is None else _p(noise, c_double),
-                                          _p(rows, c_double)))
-    return rows
 
 
 def scales(cfg, position, steps_hit):
