@@ -33,6 +33,7 @@ constexpr int kScanRounds = 4;                       // scene points per thread 
 constexpr int kScanTile = kScanRounds * kBlock;      // 1024 scene points per workgroup
 constexpr int kScanFrames = 8;                       // frames per workgroup
 
+// SCAN_CORE_BEGIN
 struct ScanParams {
   double range_min, range_max_sq, half_fov_h, half_fov_v;
   int64_t cap;         // points_per_frame
@@ -110,6 +111,7 @@ __device__ __forceinline__ bool scan_visible(const double* __restrict__ P, doubl
   s = fmin(fmax(s, -1.0), 1.0);
   return scan_fov_exact(lx, ly, s, az_in, el_in, sp.half_fov_h, sp.half_fov_v);
 }
+// SCAN_CORE_END
 
 // the scene columns x, y, z, intensity (float64) in one allocation of scene_words(E) doubles
 inline size_t scene_words(int64_t E) { return 4 * (size_t)E; }
