@@ -28,6 +28,9 @@
  *     _create_rotation_matrix                  CSIM:1518-1536    (R_xyz(theta)^T in-kernel)
  *   LiDARSimulator.simulate_scan / _raycast    CSIM:1011-1146  mc_set_ray_scene + mc_ray_count +
  *     (per frame of _simulate_lidar_frames     CSIM:2028-2084)   mc_ray_emit / mc_ray_emit_f64
+ *   LivoxLVXWriter.write_lvx_file              CSIM:235-374    mc_csim_lvx_layout + mc_csim_lvx_encode /
+ *     (lvx, lvx2, lvx3)                                          mc_csim_lvx_encode_batch
+ *   DataExporter._export_pcd / _xyz / _csv     CSIM:1643-1715  mc_csim_text_encode / mc_csim_text_encode_batch
  *   (build-added)                          mc_deskew(MC_MODE_POSE_SLERP)
  *
  * LMC = lidar_motion_compensation.py, CSIM = livox_mid70_complete_simulator.py.
@@ -247,6 +250,52 @@ int mc_pcd_encode_batch(mc_ctx* ctx, const mc_batch* b, void* d_out, int64_t out
 int mc_deskew_pcd(mc_ctx* ctx, const mc_batch* in, mc_batch* out, int mode, int pose_select, void* d_out,
                   int64_t out_bytes, int64_t* body_pos);
 int mc_timing_read_codec(mc_ctx* ctx, double* ms_total, int64_t* launches);
+
+/* ---- CSIM exports: LivoxLVXWriter.write_lvx_file (CSIM:235-374) and DataExporter's PCD / XYZ / CSV
+ * (CSIM:1603-1715), byte-identical.  Source: device rows (N, ld >= 5) float64 = x, y, z, intensity,
+ * timestamp (the points_array of CSIM:1627) with frames back to back, or a MC_BATCH_WITH_TIME batch
+ * whose frame starts are set; the row of a batch point is defined as [x, y, z, trunc(intensity),
+ * frame_start_ns[f] + t_ns] with the float32 values widened exactly (the LiDARPoint of CSIM:1040-1050),
+ * so the *_batch encoders give the bytes of the row encoders applied to those rows.  ld < 5 ->
+ * MC_ERR_INDEX; a batch without time or frame starts -> MC_ERR_STATE.  Synchronous; timed under
+ * mc_timing_read_codec. ------------------------------------------------------------------------- */
+#define MC_CSIM_LVX_LEGACY 1 /* "lvx":  _write_lvx_legacy, float32 records            CSIM:256-267, 295-321 */
+#define MC_CSIM_LVX2 2       /* "lvx2": _write_lvx2, int32 mm records                 CSIM:269-287, 323-374 */
+#define MC_CSIM_LVX3 3       /* "lvx3": the bytes of lvx2                             CSIM:289-293          */
+#define MC_CSIM_PCD 0        /* _export_pcd body "%.6f %.6f %.6f %.0f %.0f\n"         CSIM:1663-1664        */
+#define MC_CSIM_XYZ 1        /* _export_xyz "%.6f %.6f %.6f\n" (np.savetxt)           CSIM:1700-1706        */
+#define MC_CSIM_CSV 2        /* _export_csv rows "%.6f,%.6f,%.6f,%.6f,%.6f\n", NaN = empty field  CSIM:1708-1715 */
+/* File layout (CSIM:269-374): lvx2 / lvx3 = 88 header bytes, then per frame 45 + 14 n bytes (24-byte
+ * frame header, the 21-byte package header the code writes, n records); legacy = 60 header bytes,
+ * then 12 + 14 n per frame.  frame_pos[F] = file size.  Host only. */
+int mc_csim_lvx_layout(int version, int32_t n_frames, const int64_t* counts, int64_t* frame_pos);
+/* The whole file of write_lvx_file (CSIM:245-374) into d_out (>= frame_pos[F] bytes, else
+ * MC_ERR_SPACE): headers from lidar_sn (16 bytes, ASCII padded with zeros), device_type,
+ * extrinsic_enable and extrinsics[6] = roll, pitch, yaw, x, y, z (CSIM:302-306, 323-341); frame f
+ * stamped timestamp_ns[f] (frame['timestamp']) and, in lvx2, numbered f (CSIM:286).  Records: lvx2
+ * int(v * 1000) without a clip (CSIM:368-372), legacy float32 (CSIM:319), then trunc(intensity) and
+ * d_tags[row] (N bytes on the device; NULL = 0).  Where the reference's write raises — lvx2: a NaN or
+ * infinite coordinate, int(v * 1000) outside int32; legacy: a finite coordinate that rounds to +-inf in
+ * float32; both: an intensity that is NaN or outside 0..255 after truncation — MC_ERR_INVALID, and
+ * the contents of d_out are unspecified. */
+int mc_csim_lvx_encode(mc_ctx* ctx, int version, const double* d_rows, int64_t ld, int32_t n_frames,
+                       const int64_t* counts, const uint64_t* timestamp_ns, const uint8_t* d_tags,
+                       const uint8_t* lidar_sn, uint8_t device_type, uint8_t extrinsic_enable,
+                       const float* extrinsics, void* d_out, int64_t out_bytes);
+int mc_csim_lvx_encode_batch(mc_ctx* ctx, int version, const mc_batch* b, const uint64_t* timestamp_ns,
+                             const uint8_t* d_tags, const uint8_t* lidar_sn, uint8_t device_type,
+                             uint8_t extrinsic_enable, const float* extrinsics, void* d_out, int64_t out_bytes);
+/* The point lines of DataExporter._export_pcd / _export_xyz / _export_csv (CSIM:1643-1715) for F
+ * clouds, back to back in d_out; the PCD header (CSIM:1648-1659) and the CSV header line are the
+ * host's.  "%.6f" and "%.0f" are Python's correctly rounded formatting ("%.0f": ties to even on the
+ * exact binary value, "-0" for a negative value that rounds to zero, nan / inf / -inf); MC_CSIM_CSV
+ * prints a NaN as an empty field.  The mc_pcd_encode contract: body_pos[F+1] receives each cloud's
+ * byte offset (body_pos[F] = total); if out_bytes < total: MC_ERR_SPACE, body_pos filled, nothing
+ * written.  |value| >= 2^107 -> MC_ERR_INVALID. */
+int mc_csim_text_encode(mc_ctx* ctx, int format, const double* d_rows, int64_t ld, int32_t n_frames,
+                        const int64_t* counts, void* d_out, int64_t out_bytes, int64_t* body_pos);
+int mc_csim_text_encode_batch(mc_ctx* ctx, int format, const mc_batch* b, void* d_out, int64_t out_bytes,
+                              int64_t* body_pos);
 
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */

@@ -13,9 +13,13 @@ Drop-in surface (reference file:line in each docstring):
   LiDARPoint, IMUData    livox_mid70_complete_simulator.py:97-129
   LivoxLVXWriter, codecs lidar_motion_compensation.py:24-272, 932-948 (byte-exact LVX / PCD)
   CoordinateTransformer  livox_mid70_complete_simulator.py:145-233, 2107-2180 (coords)
+  csim_export            livox_mid70_complete_simulator.py:235-374, 1603-1715: its LivoxLVXWriter
+                         (lvx / lvx2 / lvx3), DataExporter (PCD / XYZ / CSV) and DeviceInfo, byte-exact
+                         (the top-level LivoxLVXWriter stays the LMC one)
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
-from . import _lib, codecs, config, coords, dist, raymarch, runtime, trajectory  # noqa: F401
+from . import _lib, codecs, config, coords, csim_export, dist, raymarch, runtime, trajectory  # noqa: F401
+from .csim_export import DataExporter, DeviceInfo  # noqa: F401
 from .coords import CoordinateSystem, CoordinateTransformer, GPSData  # noqa: F401
 from .codecs import LivoxLVXWriter  # noqa: F401
 from ._lib import McError, McLibraryError  # noqa: F401

@@ -98,6 +98,14 @@ _SIGS = {
     "mc_pcd_encode_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, _pi64]),
     "mc_deskew_pcd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, _pi64]),
     "mc_timing_read_codec": (c_int, [c_void_p, _pd, _pi64]),
+    "mc_csim_lvx_layout": (c_int, [c_int, c_int32, _pi64, _pi64]),
+    "mc_csim_lvx_encode": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int32, _pi64, POINTER(c_uint64), c_void_p,
+                                   POINTER(ctypes.c_uint8), ctypes.c_uint8, ctypes.c_uint8, _pf, c_void_p, c_int64]),
+    "mc_csim_lvx_encode_batch": (c_int, [c_void_p, c_int, c_void_p, POINTER(c_uint64), c_void_p,
+                                         POINTER(ctypes.c_uint8), ctypes.c_uint8, ctypes.c_uint8, _pf, c_void_p,
+                                         c_int64]),
+    "mc_csim_text_encode": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int32, _pi64, c_void_p, c_int64, _pi64]),
+    "mc_csim_text_encode_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

@@ -1,7 +1,9 @@
 // codecs.hip — host side of the output codecs in include/mcdeskew.h:
 // LVX v1.1 files (LMC:24-272) and ASCII PCD bodies (LMC:932-948) encoded on the device from a
-// device-resident (N, ld) float64 AoS cloud.
+// device-resident (N, ld) float64 AoS cloud; and of the CSIM exports (LVX / LVX2 / LVX3 files,
+// CSIM:235-374, and the PCD / XYZ / CSV bodies of DataExporter, CSIM:1603-1715; csim_codecs.hpp).
 #include "codecs.hpp"
+#include "csim_codecs.hpp"
 #include "hostutil.hpp"
 
 #include <algorithm>
@@ -366,6 +368,263 @@ int pcd_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, v
 }
 
 }  // namespace
+
+// ---- CSIM exports: LivoxLVXWriter.write_lvx_file (CSIM:235-374), DataExporter (CSIM:1603-1715) -----
+namespace {
+
+int csim_version(int version, int* ver) {
+  CHECK_ARG(version == MC_CSIM_LVX_LEGACY || version == MC_CSIM_LVX2 || version == MC_CSIM_LVX3,
+            "Unsupported format version: %d", version);
+  *ver = version == MC_CSIM_LVX_LEGACY ? 1 : 2;   // lvx3 writes lvx2's bytes (CSIM:289-293)
+  return MC_OK;
+}
+
+int csim_batch_source(mc_ctx* c, const mc_batch* b, Source* src) {
+  CHECK_ARG(c && b, "NULL argument");
+  CHECK_ARG(b->ctx == c, "batch belongs to another context");
+  if (!b->has_t()) return fail(MC_ERR_STATE, "the CSIM encoders need a batch created with MC_BATCH_WITH_TIME");
+  if (!b->has_starts) return fail(MC_ERR_STATE, "the batch's frame starts are not set (mc_batch_set_frame_start_ns)");
+  src->batch = b;
+  return MC_OK;
+}
+
+CsimSrc csim_src(const Source& src, const CodecFrames& fr, const uint8_t* d_tags) {
+  CsimSrc s;
+  s.fr = fr;
+  s.fr.ld = src.batch ? 5 : src.ld;
+  s.fstart = src.batch ? src.batch->d_frame_start : nullptr;
+  s.tags = d_tags;
+  return s;
+}
+
+struct CsimDevice {
+  const uint8_t* sn;   // 16 bytes
+  uint8_t type, extrinsic;
+  const float* ext;    // roll, pitch, yaw, x, y, z
+};
+
+// the bytes ahead of the first frame; -> their count
+int csim_file_header(int ver, int32_t F, const CsimDevice& dv, uint8_t h[kCsimLvx2FileHdr]) {
+  std::memset(h, 0, kCsimLvx2FileHdr);
+  if (ver == 1) {   // CSIM:295-306
+    std::memcpy(h, "livox_file", 10);
+    const uint32_t one = 1, n = (uint32_t)F;
+    std::memcpy(h + 10, &one, 4);
+    std::memcpy(h + 14, &n, 4);
+    std::memcpy(h + 28, dv.sn, 16);
+    h[44] = dv.type;
+    return kCsimLvx1FileHdr;
+  }
+  std::memcpy(h, "livox_tech", 10);   // CSIM:272-280, 323-341
+  std::memcpy(h + 10, "2.0.0", 5);
+  const uint32_t magic = 0xAC0EA767u, dur = 50, ndev = 1;
+  std::memcpy(h + 16, &magic, 4);
+  std::memcpy(h + 24, &dur, 4);
+  std::memcpy(h + 28, &ndev, 4);
+  std::memcpy(h + 32, dv.sn, 16);
+  h[48] = dv.type;
+  h[49] = dv.extrinsic ? 1 : 0;
+  std::memcpy(h + 50, dv.ext, 24);
+  return kCsimLvx2FileHdr;
+}
+
+int csim_layout(int ver, int32_t F, const int64_t* counts, int64_t* pos) {
+  const int fh = ver == 1 ? kCsimLvx1FrameHdr : kCsimLvx2FrameHdr;
+  pos[0] = ver == 1 ? kCsimLvx1FileHdr : kCsimLvx2FileHdr;
+  for (int32_t f = 0; f < F; ++f) pos[f + 1] = pos[f] + fh + counts[f] * kCsimRec;
+  return MC_OK;
+}
+
+int csim_lvx_encode(mc_ctx* c, int version, const Source& src, int32_t F, const int64_t* counts, const uint64_t* ts_ns,
+                    const uint8_t* d_tags, const CsimDevice& dv, void* d_out, int64_t out_bytes) {
+  int ver = 0;
+  if (int r = csim_version(version, &ver)) return r;
+  std::vector<int64_t> doff;
+  if (int r = check_frames(F, counts, doff)) return r;
+  CHECK_ARG(d_out, "d_out is NULL");
+  CHECK_ARG(F == 0 || ts_ns, "timestamp_ns is NULL");
+  CHECK_ARG(dv.sn && dv.ext, "device info is NULL");
+  CHECK_ARG(doff[F] == 0 || src.aos || src.batch, "points pointer is NULL");
+  std::vector<int64_t> pos((size_t)F + 1), units((size_t)F + 1, 0);
+  csim_layout(ver, F, counts, pos.data());
+  if (out_bytes < pos[F])
+    return fail(MC_ERR_SPACE, "LVX output needs %lld bytes, buffer has %lld", (long long)pos[F], (long long)out_bytes);
+  for (int32_t f = 0; f < F; ++f) units[f + 1] = units[f] + (counts[f] + kCsimUnitPoints - 1) / kCsimUnitPoints;
+  const int64_t n_units = units[F];
+  CHECK_ARG(n_units < (int64_t)INT32_MAX, "too many units for one launch");
+  DeviceGuard g(c->device);
+
+  std::vector<uint8_t> blob;
+  const size_t o_doff = put(blob, doff.data(), doff.size());
+  const size_t o_unit = put(blob, units.data(), units.size());
+  const size_t o_pos = put(blob, pos.data(), (size_t)F + 1);
+  const size_t o_ts = put(blob, ts_ns, (size_t)F);
+  char* d = nullptr;
+  if (int r = codec_scratch(c, blob.size(), &d)) return r;
+  HIPCHK(hipMemcpyAsync(d, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+  uint8_t hdr[kCsimLvx2FileHdr];
+  const int hb = csim_file_header(ver, F, dv, hdr);
+  HIPCHK(hipMemcpyAsync(d_out, hdr, hb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_codec_err, 0, sizeof(int), c->stream));
+
+  CsimLvxArgs a;
+  a.src = csim_src(src, frames_of(src, reinterpret_cast<const int64_t*>(d + o_doff),
+                                  reinterpret_cast<const int64_t*>(d + o_unit), F, n_units), d_tags);
+  a.frame_pos = reinterpret_cast<const int64_t*>(d + o_pos);
+  a.ts_ns = reinterpret_cast<const uint64_t*>(d + o_ts);
+  a.out = static_cast<char*>(d_out);
+  a.err = c->d_codec_err;
+  {
+    TimedRegion tr(c, &c->codec_ev, c->stream);
+    const bool empty_frame = std::any_of(counts, counts + F, [](int64_t n) { return n == 0; });
+    const dim3 fgrid((F + kCodecBlock - 1) / kCodecBlock), ugrid((uint32_t)n_units), blk(kCodecBlock);
+    if (F > 0 && empty_frame) {
+      if (ver == 1) hipLaunchKernelGGL(k_csim_lvx_frames<1>, fgrid, blk, 0, c->stream, a);
+      else hipLaunchKernelGGL(k_csim_lvx_frames<2>, fgrid, blk, 0, c->stream, a);
+    }
+    if (n_units > 0) {
+      if (ver == 1) hipLaunchKernelGGL(k_csim_lvx<1>, ugrid, blk, 0, c->stream, a);
+      else hipLaunchKernelGGL(k_csim_lvx<2>, ugrid, blk, 0, c->stream, a);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  int err = 0;
+  HIPCHK(hipMemcpyAsync(&err, c->d_codec_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (err)
+    return fail(MC_ERR_INVALID, ver == 1 ? "a coordinate overflows float32, or an intensity is NaN or outside 0..255"
+                                         : "a coordinate is NaN or infinite, int(v * 1000) is outside int32, or an "
+                                           "intensity is NaN or outside 0..255");
+  return MC_OK;
+}
+
+int csim_text_encode(mc_ctx* c, int format, const Source& src, int32_t F, const int64_t* counts, void* d_out,
+                     int64_t out_bytes, int64_t* body_pos) {
+  CsimLine line;
+  switch (format) {
+    case MC_CSIM_PCD: line = {5, ' ', 0x18u, 0}; break;   // CSIM:1664
+    case MC_CSIM_XYZ: line = {3, ' ', 0u, 0}; break;      // CSIM:1703
+    case MC_CSIM_CSV: line = {5, ',', 0u, 1}; break;      // CSIM:1711-1712
+    default: return fail(MC_ERR_INVALID, "unknown CSIM text format %d", format);
+  }
+  std::vector<int64_t> doff;
+  if (int r = check_frames(F, counts, doff)) return r;
+  CHECK_ARG(doff[F] == 0 || src.aos || src.batch, "points pointer is NULL");
+  std::vector<int64_t> units((size_t)F + 1, 0);
+  for (int32_t f = 0; f < F; ++f) units[f + 1] = units[f] + (counts[f] + kPcdBlock - 1) / kPcdBlock;
+  const int64_t n_tiles = units[F];
+  CHECK_ARG(n_tiles < (int64_t)INT32_MAX, "too many tiles for one launch");
+  if (n_tiles == 0) {
+    std::fill(body_pos, body_pos + F + 1, (int64_t)0);
+    return MC_OK;
+  }
+  DeviceGuard g(c->device);
+  std::vector<uint8_t> blob;
+  const size_t o_doff = put(blob, doff.data(), doff.size());
+  const size_t o_unit = put(blob, units.data(), units.size());
+  const size_t o_tb = put(blob, (const int32_t*)nullptr, 0);
+  blob.resize(o_tb + (size_t)n_tiles * sizeof(int32_t));
+  const size_t o_tp = put(blob, (const int64_t*)nullptr, 0);
+  blob.resize(o_tp + (size_t)n_tiles * sizeof(int64_t));
+  char* d = nullptr;
+  if (int r = codec_scratch(c, blob.size(), &d)) return r;
+  HIPCHK(hipMemcpyAsync(d, blob.data(), o_tb, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemsetAsync(c->d_codec_err, 0, sizeof(int), c->stream));
+  CsimTextArgs a;
+  a.src = csim_src(src, frames_of(src, reinterpret_cast<const int64_t*>(d + o_doff),
+                                  reinterpret_cast<const int64_t*>(d + o_unit), F, n_tiles), nullptr);
+  a.line = line;
+  a.tile_bytes = reinterpret_cast<int32_t*>(d + o_tb);
+  a.tile_pos = reinterpret_cast<const int64_t*>(d + o_tp);
+  a.out = static_cast<char*>(d_out);
+  a.err = c->d_codec_err;
+  const dim3 grid((uint32_t)n_tiles), blk(kPcdBlock);
+  {
+    TimedRegion tr(c, &c->codec_ev, c->stream);
+    if (line.ncols == 3) hipLaunchKernelGGL(k_csim_text_measure<3>, grid, blk, 0, c->stream, a);
+    else hipLaunchKernelGGL(k_csim_text_measure<5>, grid, blk, 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<int32_t> tb((size_t)n_tiles);
+  int err = 0;
+  HIPCHK(hipMemcpyAsync(tb.data(), a.tile_bytes, tb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&err, c->d_codec_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (err) return fail(MC_ERR_INVALID, "a value has |v| >= 2^107, beyond the device %%.6f / %%.0f formatters");
+  std::vector<int64_t> tpos((size_t)n_tiles);
+  int64_t run = 0;
+  for (int32_t f = 0; f < F; ++f) {
+    body_pos[f] = run;
+    for (int64_t t = units[f]; t < units[f + 1]; ++t) { tpos[t] = run; run += tb[t]; }
+  }
+  body_pos[F] = run;
+  if (out_bytes < run)
+    return fail(MC_ERR_SPACE, "the text needs %lld bytes, buffer has %lld", (long long)run, (long long)out_bytes);
+  CHECK_ARG(d_out, "d_out is NULL");
+  HIPCHK(hipMemcpyAsync(d + o_tp, tpos.data(), tpos.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  {
+    TimedRegion tr(c, &c->codec_ev, c->stream);
+    if (line.ncols == 3) hipLaunchKernelGGL(k_csim_text_write<3>, grid, blk, 0, c->stream, a);
+    else hipLaunchKernelGGL(k_csim_text_write<5>, grid, blk, 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return MC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mc_csim_lvx_layout(int version, int32_t F, const int64_t* counts, int64_t* pos) {
+  int ver = 0;
+  if (int r = csim_version(version, &ver)) return r;
+  CHECK_ARG(pos, "frame_pos is NULL");
+  std::vector<int64_t> doff;
+  if (int r = check_frames(F, counts, doff)) return r;
+  return csim_layout(ver, F, counts, pos);
+}
+
+int mc_csim_lvx_encode(mc_ctx* c, int version, const double* d_rows, int64_t ld, int32_t F, const int64_t* counts,
+                       const uint64_t* ts_ns, const uint8_t* d_tags, const uint8_t* lidar_sn, uint8_t device_type,
+                       uint8_t extrinsic_enable, const float* extrinsics, void* d_out, int64_t out_bytes) {
+  CHECK_ARG(c, "ctx is NULL");
+  if (ld < 5) return fail(MC_ERR_INDEX, "CSIM rows are x, y, z, intensity, timestamp: ld >= 5; got %lld", (long long)ld);
+  Source src;
+  src.aos = d_rows;
+  src.ld = ld;
+  return csim_lvx_encode(c, version, src, F, counts, ts_ns, d_tags, {lidar_sn, device_type, extrinsic_enable, extrinsics},
+                         d_out, out_bytes);
+}
+
+int mc_csim_lvx_encode_batch(mc_ctx* c, int version, const mc_batch* b, const uint64_t* ts_ns, const uint8_t* d_tags,
+                             const uint8_t* lidar_sn, uint8_t device_type, uint8_t extrinsic_enable,
+                             const float* extrinsics, void* d_out, int64_t out_bytes) {
+  Source src;
+  if (int r = csim_batch_source(c, b, &src)) return r;
+  return csim_lvx_encode(c, version, src, b->F, b->counts.data(), ts_ns, d_tags,
+                         {lidar_sn, device_type, extrinsic_enable, extrinsics}, d_out, out_bytes);
+}
+
+int mc_csim_text_encode(mc_ctx* c, int format, const double* d_rows, int64_t ld, int32_t F, const int64_t* counts,
+                        void* d_out, int64_t out_bytes, int64_t* body_pos) {
+  CHECK_ARG(c && body_pos, "NULL argument");
+  if (ld < 5) return fail(MC_ERR_INDEX, "CSIM rows are x, y, z, intensity, timestamp: ld >= 5; got %lld", (long long)ld);
+  Source src;
+  src.aos = d_rows;
+  src.ld = ld;
+  return csim_text_encode(c, format, src, F, counts, d_out, out_bytes, body_pos);
+}
+
+int mc_csim_text_encode_batch(mc_ctx* c, int format, const mc_batch* b, void* d_out, int64_t out_bytes,
+                              int64_t* body_pos) {
+  CHECK_ARG(body_pos, "NULL argument");
+  Source src;
+  if (int r = csim_batch_source(c, b, &src)) return r;
+  return csim_text_encode(c, format, src, b->F, b->counts.data(), d_out, out_bytes, body_pos);
+}
+
+}  // extern "C"
 
 extern "C" {
 

@@ -421,6 +421,7 @@ class Batch:
         if len(s) != self.n_frames:
             raise ValueError("one frame start per frame expected")
         check(self.lib.mc_batch_set_frame_start_ns(self.handle, ptr(s, c_int64)), "set_frame_starts")
+        self.frame_starts = s.copy()   # host copy (csim_export.batch_rows, the LVX frame timestamps)
 
     # ---- host <-> device ----------------------------------------------------------------
     def upload_aos(self, points):
