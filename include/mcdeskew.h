@@ -297,6 +297,75 @@ int mc_csim_text_encode(mc_ctx* ctx, int format, const double* d_rows, int64_t l
 int mc_csim_text_encode_batch(mc_ctx* ctx, int format, const mc_batch* b, void* d_out, int64_t out_bytes,
                               int64_t* body_pos);
 
+/* ---- ingest (f7): the inverse of the writers above -------------------------------------------
+ * Recorded LVX files and ASCII PCD / XYZ / CSV text decoded on the device into float64 rows
+ * [x, y, z, intensity, timestamp_ns] (the points_array of CSIM:1627) plus one tag byte per point, or
+ * into the float32 columns of a batch ("float64, rounded once").  The layout is sniffed from the
+ * bytes: MC_LVX_V11 (what mc_lvx_encode writes, LMC:57-272), MC_CSIM_LVX_LEGACY (CSIM:256-267,
+ * 295-321) and MC_CSIM_LVX2 (CSIM:269-293, 323-374; an lvx3 file is the same bytes and reports lvx2).
+ *   int32 mm records   x = float64(mm) / 1000.0, one IEEE division       (inverse of LMC:257, CSIM:368)
+ *   legacy records     the float32 widened exactly                        (inverse of CSIM:319)
+ *   intensity          V11: reflectivity / 255.0 (LMC:266); CSIM: the byte 0..255 (CSIM:320, 373)
+ *   timestamp          the frame's (V11: the package's, LMC:237) + point_period_ns * (index in frame),
+ *                      added in int64, then converted to float64
+ * What the files do not hold: (1) NONE OF THESE FORMATS STORES A PER-POINT TIME — point_period_ns
+ * (default 0) is the caller's knowledge; (2) V11 stores no point count and pads a frame's last package
+ * with zero records (LMC:246-250): by default the trailing all-zero records of each frame's last package
+ * are dropped (counted on the device), so a trailing real point at the origin with reflectivity 0 is
+ * dropped too; keep_padding keeps every slot (96 x packages).  A V11 frame without a package has no
+ * timestamp: -1.  Re-encoding decoded mm records need not reproduce the file: both writers truncate
+ * x * 1000, and (m / 1000.0) * 1000 can fall just below m; legacy files and the text formats round-trip.
+ *
+ * mc_lvx_probe / mc_lvx_index are host only and validate everything a launch relies on: magic and
+ * version, offsets increasing and inside the file, (frame size - 24) % 1366 == 0 for V11, position +
+ * header + 14 * count <= bytes for the CSIM layouts.  A file that fails -> MC_ERR_INVALID with a
+ * message, nothing launched.  The decoders re-check frame_pos / counts against `bytes` and never
+ * follow an offset stored in the file.  d_file / d_text: device copies of the file, 16-byte aligned
+ * and allocated up to the next multiple of 16 bytes (the kernels load whole 16-byte chunks).
+ * frame_pos[F + 1]: each frame header's offset, then the file size; slots[F]: record slots per frame.
+ * frame_ids: V11 the stored id, lvx2 the stored index, legacy the position.  Any output may be NULL. */
+#define MC_LVX_V11 0
+int mc_lvx_probe(const void* file, int64_t bytes, int* format, int32_t* n_frames);
+int mc_lvx_index(const void* file, int64_t bytes, int format, int32_t n_frames, int64_t* frame_pos, int64_t* slots,
+                 uint64_t* frame_ids, int64_t* timestamp_ns, uint8_t* lidar_sn16, uint8_t* device_type,
+                 uint8_t* extrinsic_enable, float* extrinsics6);
+/* counts_out[F]: the points per frame — slots for the CSIM layouts and with keep_padding, else V11's
+ * slots less the trailing zero records of each frame's last package (k_lvx_trim). */
+int mc_lvx_count(mc_ctx* ctx, int format, const void* d_file, int64_t bytes, int32_t n_frames,
+                 const int64_t* frame_pos, const int64_t* slots, int keep_padding, int64_t* counts_out);
+/* d_rows (sum(counts), ld >= 5) float64, frames back to back; d_tags [sum(counts)] or NULL.  ld < 5 ->
+ * MC_ERR_INDEX.  timestamp_ns[F]: the frame timestamps of mc_lvx_index (V11 reads its package headers
+ * and takes NULL).  Synchronous; timed under mc_timing_read_codec. */
+int mc_lvx_decode(mc_ctx* ctx, int format, const void* d_file, int64_t bytes, int32_t n_frames,
+                  const int64_t* frame_pos, const int64_t* counts, const int64_t* timestamp_ns,
+                  int64_t point_period_ns, double* d_rows, int64_t ld, uint8_t* d_tags);
+/* The same into a batch created with MC_BATCH_WITH_TIME (else MC_ERR_STATE) whose counts equal
+ * `counts`: columns = float32 of the row values, t_ns = index * point_period_ns (must fit int32, else
+ * MC_ERR_INVALID before any launch), frame starts = timestamp_ns. */
+int mc_lvx_decode_batch(mc_ctx* ctx, int format, const void* d_file, int64_t bytes, int32_t n_frames,
+                        const int64_t* frame_pos, const int64_t* counts, const int64_t* timestamp_ns,
+                        int64_t point_period_ns, mc_batch* out, uint8_t* d_tags);
+/* ASCII point lines: LMC save_pcd (4 fields, LMC:932-948), CSIM _export_pcd (5 fields, CSIM:1648-1664),
+ * _export_xyz (3 fields, CSIM:1700-1706), _export_csv (5 comma-separated fields, an empty field = NaN,
+ * CSIM:1708-1715); the host strips the PCD header / CSV header line and passes the body.  sep ' ' or
+ * ','; n_cols 3..8.  A line holding nothing or a lone '\r' is skipped, a trailing '\r' ignored, the
+ * last line may lack its '\n'.  Tokens: [+-]digits[.digits], nan, inf, -inf.  With the sign, leading
+ * zeros and the fraction's trailing zeros stripped, a token of at most 19 significant digits and at
+ * most 19 fractional digits decodes bit-equal to strtod / Python float(); anything else (an exponent,
+ * more digits, other text) is beyond the device parser: MC_ERR_INVALID with *bad_line = the first such
+ * line (1-based among the non-empty lines) — no host fallback, as the formatters' |v| >= 2^107.  A
+ * line with another number of fields: the same.  mc_text_decode: n_lines must be mc_text_lines' count;
+ * ld < n_cols -> MC_ERR_INDEX.  mc_text_decode_batch: the batch's points must equal the line count
+ * (frames = its counts); x, y, z, intensity = float32(float64(token)) (3 columns: intensity 0); with
+ * n_cols >= 5 the batch needs MC_BATCH_WITH_TIME (else MC_ERR_STATE) and t_ns = int64(column 4) -
+ * frame_start_ns[f] (NULL: the frame's first point's timestamp; frame_start_out[F], may be NULL,
+ * receives the starts used), which must fit int32 (else MC_ERR_INVALID).  Synchronous. */
+int mc_text_lines(mc_ctx* ctx, const void* d_text, int64_t bytes, int64_t* n_lines);
+int mc_text_decode(mc_ctx* ctx, int sep, int32_t n_cols, const void* d_text, int64_t bytes, int64_t n_lines,
+                   double* d_rows, int64_t ld, int64_t* bad_line);
+int mc_text_decode_batch(mc_ctx* ctx, int sep, int32_t n_cols, const void* d_text, int64_t bytes, mc_batch* out,
+                         const int64_t* frame_start_ns, int64_t* frame_start_out, int64_t* bad_line);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

@@ -16,10 +16,14 @@ Drop-in surface (reference file:line in each docstring):
   csim_export            livox_mid70_complete_simulator.py:235-374, 1603-1715: its LivoxLVXWriter
                          (lvx / lvx2 / lvx3), DataExporter (PCD / XYZ / CSV) and DeviceInfo, byte-exact
                          (the top-level LivoxLVXWriter stays the LMC one)
+  ingest                 the inverse of both writers: read_lvx / read_lvx_batch (LVX v1.1, CSIM lvx /
+                         lvx2 / lvx3) and read_points / read_points_batch (ASCII PCD / XYZ / CSV)
+                         decoded on the device into rows or a Batch
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
-from . import _lib, codecs, config, coords, csim_export, dist, raymarch, runtime, trajectory  # noqa: F401
+from . import _lib, codecs, config, coords, csim_export, dist, ingest, raymarch, runtime, trajectory  # noqa: F401
 from .csim_export import DataExporter, DeviceInfo  # noqa: F401
+from .ingest import read_lvx, read_lvx_batch, read_points, read_points_batch  # noqa: F401
 from .coords import CoordinateSystem, CoordinateTransformer, GPSData  # noqa: F401
 from .codecs import LivoxLVXWriter  # noqa: F401
 from ._lib import McError, McLibraryError  # noqa: F401

@@ -106,6 +106,17 @@ _SIGS = {
                                          c_int64]),
     "mc_csim_text_encode": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int32, _pi64, c_void_p, c_int64, _pi64]),
     "mc_csim_text_encode_batch": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, _pi64]),
+    "mc_lvx_probe": (c_int, [c_void_p, c_int64, POINTER(c_int), _pi32]),
+    "mc_lvx_index": (c_int, [c_void_p, c_int64, c_int, c_int32, _pi64, _pi64, POINTER(c_uint64), _pi64,
+                             POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8), _pf]),
+    "mc_lvx_count": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int32, _pi64, _pi64, c_int, _pi64]),
+    "mc_lvx_decode": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int32, _pi64, _pi64, _pi64, c_int64, c_void_p,
+                              c_int64, c_void_p]),
+    "mc_lvx_decode_batch": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int32, _pi64, _pi64, _pi64, c_int64,
+                                    c_void_p, c_void_p]),
+    "mc_text_lines": (c_int, [c_void_p, c_void_p, c_int64, _pi64]),
+    "mc_text_decode": (c_int, [c_void_p, c_int, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, _pi64]),
+    "mc_text_decode_batch": (c_int, [c_void_p, c_int, c_int32, c_void_p, c_int64, c_void_p, _pi64, _pi64, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

@@ -1,10 +1,13 @@
-// codecs.hip — host side of the output codecs in include/mcdeskew.h:
+// codecs.hip — host side of the file codecs in include/mcdeskew.h:
 // LVX v1.1 files (LMC:24-272) and ASCII PCD bodies (LMC:932-948) encoded on the device from a
 // device-resident (N, ld) float64 AoS cloud; and of the CSIM exports (LVX / LVX2 / LVX3 files,
-// CSIM:235-374, and the PCD / XYZ / CSV bodies of DataExporter, CSIM:1603-1715; csim_codecs.hpp).
+// CSIM:235-374, and the PCD / XYZ / CSV bodies of DataExporter, CSIM:1603-1715; csim_codecs.hpp); and
+// of their inverse, the decoders of those files into device rows or a batch (ingest.hpp, f7).
 #include "codecs.hpp"
 #include "csim_codecs.hpp"
 #include "hostutil.hpp"
+#include "ingest.hpp"
+#include "ingest_index.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -622,6 +625,301 @@ int mc_csim_text_encode_batch(mc_ctx* c, int format, const mc_batch* b, void* d_
   Source src;
   if (int r = csim_batch_source(c, b, &src)) return r;
   return csim_text_encode(c, format, src, b->F, b->counts.data(), d_out, out_bytes, body_pos);
+}
+
+}  // extern "C"
+
+// ---- ingest (f7): LVX files and ASCII PCD / XYZ / CSV text back into device rows or a batch ----------
+namespace {
+
+int ingest_fail(const char* msg) { return fail(MC_ERR_INVALID, "%s", msg); }
+
+int lvx_decode(mc_ctx* c, int format, const void* d_file, int64_t bytes, int32_t F, const int64_t* frame_pos,
+               const int64_t* counts, const int64_t* ts_ns, int64_t period, double* d_rows, int64_t ld, mc_batch* out,
+               uint8_t* d_tags) {
+  CHECK_ARG(c && d_file, "NULL argument");
+  CHECK_ARG(((uintptr_t)d_file & 15) == 0, "d_file must be 16-byte aligned (and padded to a multiple of 16 bytes)");
+  char msg[256];
+  if (mcingest::check_layout(format, bytes, F, frame_pos, counts, msg, sizeof msg)) return ingest_fail(msg);
+  CHECK_ARG(F == 0 || counts, "counts is NULL");
+  CHECK_ARG(format == MC_LVX_V11 || F == 0 || ts_ns, "timestamp_ns is NULL");
+  std::vector<int64_t> doff;
+  if (int r = check_frames(F, counts, doff)) return r;
+  std::vector<int64_t> units((size_t)F + 1, 0);
+  for (int32_t f = 0; f < F; ++f) units[f + 1] = units[f] + (counts[f] + kIngestUnit - 1) / kIngestUnit;
+  const int64_t n_units = units[F];
+  CHECK_ARG(n_units < (int64_t)INT32_MAX, "too many units for one launch");
+  if (out) {
+    CHECK_ARG(out->ctx == c, "batch belongs to another context");
+    if (!out->has_t()) return fail(MC_ERR_STATE, "mc_lvx_decode_batch needs a batch created with MC_BATCH_WITH_TIME");
+    CHECK_ARG(out->F == F && std::equal(counts, counts + F, out->counts.begin()),
+              "the batch's frame counts differ from the decoded counts");
+    CHECK_ARG(period >= 0, "point_period_ns must be >= 0");
+    for (int32_t f = 0; f < F; ++f)
+      CHECK_ARG(counts[f] <= 1 || (unsigned __int128)period * (uint64_t)(counts[f] - 1) <= (uint64_t)INT32_MAX,
+                "frame %d: t_ns = index x point_period_ns exceeds int32 nanoseconds", f);
+    CHECK_ARG(F == 0 || ts_ns, "timestamp_ns is NULL");
+  } else {
+    CHECK_ARG(doff[F] == 0 || d_rows, "d_rows is NULL");
+  }
+  DeviceGuard g(c->device);
+  if (out)
+    if (int r = mc_batch_set_frame_start_ns(out, ts_ns)) return r;
+  if (n_units == 0) return MC_OK;
+
+  std::vector<uint8_t> blob;
+  const size_t o_doff = put(blob, doff.data(), doff.size());
+  const size_t o_unit = put(blob, units.data(), units.size());
+  const size_t o_pos = put(blob, frame_pos, (size_t)F + 1);
+  const size_t o_ts = ts_ns ? put(blob, ts_ns, (size_t)F) : 0;
+  char* d = nullptr;
+  if (int r = codec_scratch(c, blob.size(), &d)) return r;
+  HIPCHK(hipMemcpyAsync(d, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+  LvxInArgs a;
+  Source none;
+  a.fr = frames_of(none, reinterpret_cast<const int64_t*>(d + o_doff), reinterpret_cast<const int64_t*>(d + o_unit), F,
+                   n_units);
+  a.fr.poff = out ? out->d_poff : nullptr;
+  a.file = static_cast<const uint8_t*>(d_file);
+  a.frame_pos = reinterpret_cast<const int64_t*>(d + o_pos);
+  a.ts_ns = ts_ns ? reinterpret_cast<const int64_t*>(d + o_ts) : nullptr;
+  a.period = period;
+  a.rows = d_rows;
+  a.ld = ld;
+  a.cols = out ? out->d_cols : nullptr;
+  a.tags = d_tags;
+  const dim3 grid((uint32_t)n_units), blk(kCodecBlock);
+  {
+    TimedRegion tr(c, &c->codec_ev, c->stream);
+    if (out) {
+      if (format == MC_LVX_V11) hipLaunchKernelGGL((k_lvx_decode<0, true>), grid, blk, 0, c->stream, a);
+      else if (format == MC_CSIM_LVX_LEGACY) hipLaunchKernelGGL((k_lvx_decode<1, true>), grid, blk, 0, c->stream, a);
+      else hipLaunchKernelGGL((k_lvx_decode<2, true>), grid, blk, 0, c->stream, a);
+    } else {
+      if (format == MC_LVX_V11) hipLaunchKernelGGL((k_lvx_decode<0, false>), grid, blk, 0, c->stream, a);
+      else if (format == MC_CSIM_LVX_LEGACY) hipLaunchKernelGGL((k_lvx_decode<1, false>), grid, blk, 0, c->stream, a);
+      else hipLaunchKernelGGL((k_lvx_decode<2, false>), grid, blk, 0, c->stream, a);
+    }
+  }
+  HIPCHK(hipGetLastError());
+  if (out)
+    if (int r = mcimpl::batch_columns_written(out)) return r;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return MC_OK;
+}
+
+// the count pass: lines starting in each 4096-byte tile -> tile_off (exclusive prefix, host) and the total
+int text_count(mc_ctx* c, const void* d_text, int64_t bytes, std::vector<int64_t>& tile_off, int64_t* n_lines) {
+  CHECK_ARG(c && n_lines, "NULL argument");
+  CHECK_ARG(bytes >= 0, "negative size");
+  CHECK_ARG(bytes == 0 || d_text, "d_text is NULL");
+  CHECK_ARG(((uintptr_t)d_text & 15) == 0, "d_text must be 16-byte aligned (and padded to a multiple of 16 bytes)");
+  const int64_t T = (bytes + kTextTile - 1) / kTextTile;
+  CHECK_ARG(T < (int64_t)INT32_MAX, "text too large for one launch");
+  tile_off.assign((size_t)T + 1, 0);
+  if (T == 0) { *n_lines = 0; return MC_OK; }
+  char* d = nullptr;
+  if (int r = codec_scratch(c, (size_t)T * sizeof(int32_t), &d)) return r;
+  {
+    TimedRegion tr(c, &c->codec_ev, c->stream);
+    hipLaunchKernelGGL(k_text_count, dim3((uint32_t)T), dim3(kPcdBlock), 0, c->stream, static_cast<const char*>(d_text),
+                       bytes, reinterpret_cast<int32_t*>(d));
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<int32_t> tc((size_t)T);
+  HIPCHK(hipMemcpyAsync(tc.data(), d, tc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < T; ++t) tile_off[t + 1] = tile_off[t] + tc[t];
+  *n_lines = tile_off[T];
+  return MC_OK;
+}
+
+int text_decode(mc_ctx* c, int sep, int32_t n_cols, const void* d_text, int64_t bytes, int64_t n_lines, double* d_rows,
+                int64_t ld, mc_batch* out, const int64_t* frame_start_ns, int64_t* frame_start_out, int64_t* bad_line) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(sep == ' ' || sep == ',', "the separator is ' ' (PCD, XYZ) or ',' (CSV)");
+  CHECK_ARG(n_cols >= 3 && n_cols <= kIngestMaxCols, "3 to %d columns; got %d", kIngestMaxCols, n_cols);
+  if (bad_line) *bad_line = 0;
+  DeviceGuard g(c->device);
+  std::vector<int64_t> tile_off;
+  int64_t counted = 0;
+  if (int r = text_count(c, d_text, bytes, tile_off, &counted)) return r;
+  const bool with_t = out && out->has_t() && n_cols >= 5;
+  if (out) {
+    CHECK_ARG(out->ctx == c, "batch belongs to another context");
+    CHECK_ARG(out->N == counted, "the batch holds %lld points, the text %lld lines", (long long)out->N,
+              (long long)counted);
+    if (n_cols >= 5 && !out->has_t())
+      return fail(MC_ERR_STATE, "a text with a timestamp column needs a batch created with MC_BATCH_WITH_TIME");
+  } else {
+    CHECK_ARG(n_lines == counted, "the text holds %lld lines, not %lld", (long long)counted, (long long)n_lines);
+    if (ld < n_cols) return fail(MC_ERR_INDEX, "rows of %d columns need ld >= %d; got %lld", n_cols, n_cols, (long long)ld);
+    CHECK_ARG(counted == 0 || d_rows, "d_rows is NULL");
+  }
+  if (counted == 0) {
+    if (out && out->has_t()) {
+      std::vector<int64_t> z((size_t)out->F, 0);
+      if (int r = mc_batch_set_frame_start_ns(out, frame_start_ns ? frame_start_ns : z.data())) return r;
+      if (frame_start_out) std::copy_n(frame_start_ns ? frame_start_ns : z.data(), out->F, frame_start_out);
+    }
+    return MC_OK;
+  }
+  const int64_t T = (int64_t)tile_off.size() - 1, PT = (counted + kTextLines - 1) / kTextLines;
+  CHECK_ARG(PT < (int64_t)INT32_MAX, "too many lines for one launch");
+  // scratch: tile_off[T] | starts[n + 1] | flags[PT]
+  const size_t o_off = 0, o_st = o_off + (size_t)T * 8, o_fl = o_st + ((size_t)counted + 1) * 8;
+  char* d = nullptr;
+  if (int r = codec_scratch(c, o_fl + (size_t)PT * 4, &d)) return r;
+  HIPCHK(hipMemcpyAsync(d + o_off, tile_off.data(), (size_t)T * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d + o_st + (size_t)counted * 8, &bytes, 8, hipMemcpyHostToDevice, c->stream));
+  TextArgs a;
+  a.text = static_cast<const char*>(d_text);
+  a.bytes = bytes;
+  a.starts = reinterpret_cast<const int64_t*>(d + o_st);
+  a.n_lines = counted;
+  a.n_cols = n_cols;
+  a.sep = sep;
+  a.rows = d_rows;
+  a.ld = ld;
+  a.cols = out ? out->d_cols : nullptr;
+  a.C = out ? out->C : 0;
+  a.doff = out ? out->d_doff : nullptr;
+  a.poff = out ? out->d_poff : nullptr;
+  a.F = out ? out->F : 0;
+  a.fstart = out ? out->d_frame_start : nullptr;
+  a.tile_flag = reinterpret_cast<uint32_t*>(d + o_fl);
+  if (with_t && frame_start_ns)
+    if (int r = mc_batch_set_frame_start_ns(out, frame_start_ns)) return r;
+  {
+    TimedRegion tr(c, &c->codec_ev, c->stream);
+    hipLaunchKernelGGL(k_text_starts, dim3((uint32_t)T), dim3(kPcdBlock), 0, c->stream, a.text, bytes,
+                       reinterpret_cast<const int64_t*>(d + o_off), reinterpret_cast<int64_t*>(d + o_st));
+    if (with_t && !frame_start_ns && out->F > 0)
+      hipLaunchKernelGGL(k_text_frame_start, dim3((out->F + kPcdBlock - 1) / kPcdBlock), dim3(kPcdBlock), 0, c->stream, a);
+    if (out) hipLaunchKernelGGL(k_text_parse<true>, dim3((uint32_t)PT), dim3(kPcdBlock), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_text_parse<false>, dim3((uint32_t)PT), dim3(kPcdBlock), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  std::vector<uint32_t> flags((size_t)PT);
+  HIPCHK(hipMemcpyAsync(flags.data(), a.tile_flag, flags.size() * 4, hipMemcpyDeviceToHost, c->stream));
+  if (out) {
+    if (with_t && !frame_start_ns) {
+      std::vector<int64_t> fs((size_t)out->F);
+      HIPCHK(hipMemcpyAsync(fs.data(), out->d_frame_start, fs.size() * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      out->has_starts = true;
+      ++out->prep_ver;
+      if (frame_start_out) std::copy(fs.begin(), fs.end(), frame_start_out);
+    } else if (with_t && frame_start_out) {
+      std::copy_n(frame_start_ns, out->F, frame_start_out);
+    }
+    if (int r = mcimpl::batch_columns_written(out)) return r;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int64_t t = 0; t < PT; ++t) {
+    if (flags[t] == 0xffffffffu) continue;
+    const int64_t line = t * kTextLines + (flags[t] >> 2) + 1;
+    if (bad_line) *bad_line = line;
+    switch (flags[t] & 3u) {
+      case kIngestBadFields:
+        return fail(MC_ERR_INVALID, "line %lld does not hold %d fields", (long long)line, n_cols);
+      case kIngestBadTime:
+        return fail(MC_ERR_INVALID, "line %lld: the timestamp minus its frame start does not fit int32 nanoseconds",
+                    (long long)line);
+      default:
+        return fail(MC_ERR_INVALID,
+                    "line %lld holds a token beyond the device parser ([+-]digits[.digits] with at most 19 "
+                    "significant and 19 fractional digits, nan, inf)", (long long)line);
+    }
+  }
+  return MC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mc_lvx_probe(const void* file, int64_t bytes, int* format, int32_t* n_frames) {
+  char msg[256];
+  if (mcingest::probe(static_cast<const uint8_t*>(file), bytes, format, n_frames, msg, sizeof msg)) return ingest_fail(msg);
+  return MC_OK;
+}
+
+int mc_lvx_index(const void* file, int64_t bytes, int format, int32_t n_frames, int64_t* frame_pos, int64_t* slots,
+                 uint64_t* frame_ids, int64_t* timestamp_ns, uint8_t* lidar_sn, uint8_t* device_type,
+                 uint8_t* extrinsic_enable, float* extrinsics) {
+  char msg[256];
+  mcingest::DeviceBlock dv;
+  if (mcingest::index(static_cast<const uint8_t*>(file), bytes, format, n_frames, frame_pos, slots, frame_ids,
+                      timestamp_ns, &dv, msg, sizeof msg))
+    return ingest_fail(msg);
+  if (lidar_sn) std::memcpy(lidar_sn, dv.sn, 16);
+  if (device_type) *device_type = dv.device_type;
+  if (extrinsic_enable) *extrinsic_enable = dv.extrinsic_enable;
+  if (extrinsics) std::memcpy(extrinsics, dv.extrinsics, sizeof dv.extrinsics);
+  return MC_OK;
+}
+
+int mc_lvx_count(mc_ctx* c, int format, const void* d_file, int64_t bytes, int32_t F, const int64_t* frame_pos,
+                 const int64_t* slots, int keep_padding, int64_t* counts_out) {
+  CHECK_ARG(c && counts_out, "NULL argument");
+  CHECK_ARG(F == 0 || slots, "slots is NULL");
+  char msg[256];
+  if (mcingest::check_layout(format, bytes, F, frame_pos, slots, msg, sizeof msg)) return ingest_fail(msg);
+  if (format != MC_LVX_V11 || keep_padding || F == 0) {
+    std::copy_n(slots, F, counts_out);
+    return MC_OK;
+  }
+  CHECK_ARG(d_file, "d_file is NULL");
+  DeviceGuard g(c->device);
+  const size_t o_cnt = ((size_t)F + 1) * 8;
+  char* d = nullptr;
+  if (int r = codec_scratch(c, o_cnt + (size_t)F * 8, &d)) return r;
+  HIPCHK(hipMemcpyAsync(d, frame_pos, ((size_t)F + 1) * 8, hipMemcpyHostToDevice, c->stream));
+  {
+    TimedRegion tr(c, &c->codec_ev, c->stream);
+    hipLaunchKernelGGL(k_lvx_trim, dim3((F + 3) / 4), dim3(kCodecBlock), 0, c->stream,
+                       static_cast<const uint8_t*>(d_file), reinterpret_cast<const int64_t*>(d), F,
+                       reinterpret_cast<int64_t*>(d + o_cnt));
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(counts_out, d + o_cnt, (size_t)F * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return MC_OK;
+}
+
+int mc_lvx_decode(mc_ctx* c, int format, const void* d_file, int64_t bytes, int32_t F, const int64_t* frame_pos,
+                  const int64_t* counts, const int64_t* timestamp_ns, int64_t point_period_ns, double* d_rows,
+                  int64_t ld, uint8_t* d_tags) {
+  if (ld < 5) return fail(MC_ERR_INDEX, "decoded rows are x, y, z, intensity, timestamp: ld >= 5; got %lld", (long long)ld);
+  return lvx_decode(c, format, d_file, bytes, F, frame_pos, counts, timestamp_ns, point_period_ns, d_rows, ld, nullptr,
+                    d_tags);
+}
+
+int mc_lvx_decode_batch(mc_ctx* c, int format, const void* d_file, int64_t bytes, int32_t F, const int64_t* frame_pos,
+                        const int64_t* counts, const int64_t* timestamp_ns, int64_t point_period_ns, mc_batch* out,
+                        uint8_t* d_tags) {
+  CHECK_ARG(out, "batch is NULL");
+  return lvx_decode(c, format, d_file, bytes, F, frame_pos, counts, timestamp_ns, point_period_ns, nullptr, 5, out,
+                    d_tags);
+}
+
+int mc_text_lines(mc_ctx* c, const void* d_text, int64_t bytes, int64_t* n_lines) {
+  CHECK_ARG(c, "ctx is NULL");
+  DeviceGuard g(c->device);
+  std::vector<int64_t> tile_off;
+  return text_count(c, d_text, bytes, tile_off, n_lines);
+}
+
+int mc_text_decode(mc_ctx* c, int sep, int32_t n_cols, const void* d_text, int64_t bytes, int64_t n_lines,
+                   double* d_rows, int64_t ld, int64_t* bad_line) {
+  return text_decode(c, sep, n_cols, d_text, bytes, n_lines, d_rows, ld, nullptr, nullptr, nullptr, bad_line);
+}
+
+int mc_text_decode_batch(mc_ctx* c, int sep, int32_t n_cols, const void* d_text, int64_t bytes, mc_batch* out,
+                         const int64_t* frame_start_ns, int64_t* frame_start_out, int64_t* bad_line) {
+  CHECK_ARG(out, "batch is NULL");
+  return text_decode(c, sep, n_cols, d_text, bytes, 0, nullptr, 0, out, frame_start_ns, frame_start_out, bad_line);
 }
 
 }  // extern "C"

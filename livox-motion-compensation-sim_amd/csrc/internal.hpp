@@ -250,4 +250,6 @@ namespace mcimpl {
 int deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select, int32_t* pcd_len);
 // the sub-tile order (0 dealt, 1 XCD-contiguous) mc_deskew's kernel takes for this mode and batch
 int deskew_order(const mc_ctx* c, const mc_batch* in, int mode);
+// a kernel of another file has queued a write of b's columns (t_ns included) on the context's stream
+int batch_columns_written(mc_batch* b);
 }  // namespace mcimpl

@@ -411,6 +411,18 @@ int mc_batch_set_frame_start_ns(mc_batch* b, const int64_t* s) {
 // context's own deskew kernel.  Every API that returns with work in flight calls this.
 static inline void queued_async(mc_ctx* c) { c->prep_fence = true; }
 
+// After a kernel outside this file (the ingest decoders) queued a write of the batch's columns: the PCD
+// text sums are stale, the t_ns spans are recomputed, and the next prep must not overtake the write.
+extern "C++" {
+namespace mcimpl {
+int batch_columns_written(mc_batch* b) {
+  queued_async(b->ctx);
+  b->wrote(false);
+  return compute_trange(b);
+}
+}  // namespace mcimpl
+}
+
 // device AoS -> batch columns (async, timed as a layout kernel)
 static int launch_stage(mc_batch* b, const double* d_aos, int64_t ld) {
   mc_ctx* c = b->ctx;
