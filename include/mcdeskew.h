@@ -366,6 +366,67 @@ int mc_text_decode(mc_ctx* ctx, int sep, int32_t n_cols, const void* d_text, int
 int mc_text_decode_batch(mc_ctx* ctx, int sep, int32_t n_cols, const void* d_text, int64_t bytes, mc_batch* out,
                          const int64_t* frame_start_ns, int64_t* frame_start_out, int64_t* bad_line);
 
+/* ---- LAS 1.2 (f8): the files of save_las (LMC:950-963) and _export_las (CSIM:1671-1698), both thin
+ * laspy calls in the reference, written and read on the device without laspy.  Little-endian, a
+ * 227-byte public header block, no VLRs on write, point formats 0..3 (20 / 28 / 26 / 34-byte records:
+ * X, Y, Z i32, intensity u16, six zero bytes, [gps_time f64], [R, G, B u16 = 0]).
+ *   X = int32(rint((x - offset) / scale)): subtract, IEEE divide, round half to even (np.round);
+ *   intensity = trunc(column 3 * intensity_mul) as u16; gps_time = time * time_mul in float64
+ *   (time_mul == 0: 0.0).  LMC:950-963 is intensity_mul 65535, time_mul 0; CSIM:1671-1698 is
+ *   intensity_mul 1, time_mul 1e-9, scale 0.001.  Every other record byte is 0 (return number 0
+ *   included) and the points-by-return counts are 0, as the reference leaves them.  Header bounds =
+ *   min / max of the stored integers * scale + offset (host, float64, multiply then add); system
+ *   identifier "OTHER"; 0.0 bounds for an empty cloud.
+ * NOT CLAIMED: laspy is not available where this was written, so no file of its making was compared.
+ * Byte equality with laspy's own header choices (identifier strings, creation date, by-return counts)
+ * is neither promised nor tested, and the 0.01 scale the Python layer defaults to for the LMC variant
+ * is laspy's documented default from memory, unchecked.  Scale and offset are parameters, so any
+ * other writer can be matched.
+ * Refused (MC_ERR_INVALID naming the first such row, *bad_row = that row, may be NULL; where numpy
+ * wraps around silently): a coordinate that is not finite, rint(...) outside int32, an intensity that
+ * is NaN or outside 0..65535 after truncation, n >= 2^32.  Too small a buffer -> MC_ERR_SPACE with
+ * the size needed (227 + n * record bytes) in the message.  Synchronous; timed under
+ * mc_timing_read_codec. ------------------------------------------------------------------------- */
+/* Host only: parse an untrusted header (file = the first bytes .. the whole file, bytes = the file
+ * size).  Accepted: "LASF", version 1.0 .. 1.3, formats 0..3, header size >= 227, offset to point
+ * data >= header size, record length >= the format's nominal size, offset + n * record length <=
+ * bytes; everything else MC_ERR_INVALID with a message, nothing reported.  bounds[6] = max x, min x,
+ * max y, min y, max z, min z as stored.  Any output may be NULL.  (LMC:950-963 / CSIM:1671-1698) */
+int mc_las_probe(const void* file, int64_t bytes, int32_t* point_format, int32_t* record_length,
+                 int64_t* offset_to_points, int64_t* n_points, double* scale, double* offset, double* bounds);
+/* The whole file into d_out from device rows (n, ld) float64 = x, y, z, intensity[, time]
+ * (ld >= 4, >= 5 when time_mul != 0, else MC_ERR_INDEX).  scale[3] finite > 0, offset[3] finite;
+ * software: the generating-software field (at most 32 bytes, NULL = "mcdeskew"); year / day_of_year:
+ * the creation date.  (LMC:950-963 / CSIM:1671-1698) */
+int mc_las_encode(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t n, int point_format, const double* scale,
+                  const double* offset, double intensity_mul, double time_mul, const char* software, int32_t year,
+                  int32_t day_of_year, void* d_out, int64_t out_bytes, int64_t* bad_row);
+/* The same from a batch's float32 columns, widened exactly to float64 and run through the same
+ * formula, points in dense order; time = frame_start_ns[f] + t_ns, converted to float64, then
+ * multiplied (time_mul != 0 needs MC_BATCH_WITH_TIME and the frame starts, else MC_ERR_STATE).
+ * (LMC:950-963 / CSIM:1671-1698) */
+int mc_las_encode_batch(mc_ctx* ctx, const mc_batch* batch, int point_format, const double* scale,
+                        const double* offset, double intensity_mul, double time_mul, const char* software,
+                        int32_t year, int32_t day_of_year, void* d_out, int64_t out_bytes, int64_t* bad_row);
+/* Decode the records of a file whose header mc_las_probe accepted (the numbers are re-checked against
+ * `bytes`; no kernel follows a number stored in the file): d_file = the device copy of the file,
+ * 16-byte aligned and allocated up to a multiple of 16 bytes; any offset_to_points >= 227, any
+ * record_length >= nominal (extra bytes skipped).  d_rows (n, ld >= 5) float64 = x, y, z, intensity,
+ * gps_time in seconds (0.0 for formats 0 and 2); x = X * scale + offset as a float64 multiply, rounded,
+ * then an add, rounded (never fused).  (LMC:950-963 / CSIM:1671-1698) */
+int mc_las_decode(mc_ctx* ctx, const void* d_file, int64_t bytes, int point_format, int64_t record_length,
+                  int64_t offset_to_points, int64_t n_points, const double* scale, const double* offset,
+                  double* d_rows, int64_t ld);
+/* The same into a MC_BATCH_WITH_TIME batch of n_points points (frames = its counts): x, y, z =
+ * float32 of the float64 values, intensity = float32(intensity * intensity_scale), t_ns =
+ * int64(rint(gps_time * 1e9)) - frame_start_ns[f] (NULL: each frame's first point's time;
+ * frame_start_out[F], may be NULL, receives the starts used), which must fit int32, else
+ * MC_ERR_INVALID naming the first such point (*bad_row).  (LMC:950-963 / CSIM:1671-1698) */
+int mc_las_decode_batch(mc_ctx* ctx, const void* d_file, int64_t bytes, int point_format, int64_t record_length,
+                        int64_t offset_to_points, int64_t n_points, const double* scale, const double* offset,
+                        double intensity_scale, mc_batch* out, const int64_t* frame_start_ns,
+                        int64_t* frame_start_out, int64_t* bad_row);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

@@ -19,11 +19,15 @@ Drop-in surface (reference file:line in each docstring):
   ingest                 the inverse of both writers: read_lvx / read_lvx_batch (LVX v1.1, CSIM lvx /
                          lvx2 / lvx3) and read_points / read_points_batch (ASCII PCD / XYZ / CSV)
                          decoded on the device into rows or a Batch
+  las                    LAS 1.2 without laspy (lidar_motion_compensation.py:950-963,
+                         livox_mid70_complete_simulator.py:1671-1698): encode_las / write_las from rows
+                         or a Batch, read_las / read_las_batch back, records packed and unpacked on the device
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
-from . import _lib, codecs, config, coords, csim_export, dist, ingest, raymarch, runtime, trajectory  # noqa: F401
+from . import _lib, codecs, config, coords, csim_export, dist, ingest, las, raymarch, runtime, trajectory  # noqa: F401
 from .csim_export import DataExporter, DeviceInfo  # noqa: F401
 from .ingest import read_lvx, read_lvx_batch, read_points, read_points_batch  # noqa: F401
+from .las import LasData, encode_las, read_las, read_las_batch, write_las  # noqa: F401
 from .coords import CoordinateSystem, CoordinateTransformer, GPSData  # noqa: F401
 from .codecs import LivoxLVXWriter  # noqa: F401
 from ._lib import McError, McLibraryError  # noqa: F401

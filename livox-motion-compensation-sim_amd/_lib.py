@@ -117,6 +117,15 @@ _SIGS = {
     "mc_text_lines": (c_int, [c_void_p, c_void_p, c_int64, _pi64]),
     "mc_text_decode": (c_int, [c_void_p, c_int, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, _pi64]),
     "mc_text_decode_batch": (c_int, [c_void_p, c_int, c_int32, c_void_p, c_int64, c_void_p, _pi64, _pi64, _pi64]),
+    "mc_las_probe": (c_int, [c_void_p, c_int64, _pi32, _pi32, _pi64, _pi64, _pd, _pd, _pd]),
+    "mc_las_encode": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, _pd, _pd, c_double, c_double, c_char_p,
+                              c_int32, c_int32, c_void_p, c_int64, _pi64]),
+    "mc_las_encode_batch": (c_int, [c_void_p, c_void_p, c_int, _pd, _pd, c_double, c_double, c_char_p, c_int32,
+                                    c_int32, c_void_p, c_int64, _pi64]),
+    "mc_las_decode": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, _pd, _pd, c_void_p,
+                              c_int64]),
+    "mc_las_decode_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, _pd, _pd, c_double,
+                                    c_void_p, _pi64, _pi64, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

@@ -17,7 +17,8 @@ come from gfx950 kernels (csrc/csim_codecs.hpp; include/mcdeskew.h ``mc_csim_lvx
 
 Deviations from the reference: where its write raises halfway (``struct.error`` /
 ``OverflowError``, leaving a partial file), ``ValueError`` is raised here before the file is opened;
-no ``.las`` is written (the reference's LASPY_AVAILABLE = False branch); ``export_sensor_data`` is
+no ``.las`` is written by default (the reference's LASPY_AVAILABLE = False branch; the config key
+``'las_writer': 'device'`` adds it through las.write_las, without laspy); ``export_sensor_data`` is
 not part of this module.
 """
 from __future__ import annotations
@@ -312,13 +313,16 @@ class DataExporter:
 
     def export_point_clouds(self, frames_data: List[Dict], output_prefix: str = "lidar_data"):
         """CSIM:1612-1641: the merged cloud as .pcd, .xyz and .csv (no .las: laspy is absent, the
-        reference's LASPY_AVAILABLE = False); no points, no files."""
+        reference's LASPY_AVAILABLE = False); no points, no files.  With the config key
+        ``'las_writer': 'device'`` the .las of CSIM:1634-1635 is written too, by las.write_las."""
         n = sum(len(fr["points"]) for fr in frames_data)
         if not n:
             return
         points = np.array([[p.x, p.y, p.z, p.intensity, p.timestamp] for fr in frames_data for p in fr["points"]],
                           dtype=np.float64)   # CSIM:1627
         self._export_pcd(points, f"{output_prefix}.pcd")
+        if self.config.get("las_writer") == "device":
+            self._export_las(points, f"{output_prefix}.las")
         self._export_xyz(points, f"{output_prefix}.xyz")
         self._export_csv(points, f"{output_prefix}.csv")
 
@@ -330,6 +334,10 @@ class DataExporter:
 
     def _export_pcd(self, points, filename: str):
         self._write(points, "pcd", pcd_header, filename)                  # CSIM:1643-1669
+
+    def _export_las(self, points, filename: str):
+        from . import las                                                  # CSIM:1671-1698
+        las.write_las(filename, np.asarray(points, np.float64), variant="csim", context=self._context)
 
     def _export_xyz(self, points, filename: str):
         self._write(points, "xyz", lambda n: b"", filename)               # CSIM:1700-1706

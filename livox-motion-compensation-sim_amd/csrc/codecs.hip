@@ -2,14 +2,19 @@
 // LVX v1.1 files (LMC:24-272) and ASCII PCD bodies (LMC:932-948) encoded on the device from a
 // device-resident (N, ld) float64 AoS cloud; and of the CSIM exports (LVX / LVX2 / LVX3 files,
 // CSIM:235-374, and the PCD / XYZ / CSV bodies of DataExporter, CSIM:1603-1715; csim_codecs.hpp); and
-// of their inverse, the decoders of those files into device rows or a batch (ingest.hpp, f7).
+// of their inverse, the decoders of those files into device rows or a batch (ingest.hpp, f7); and of
+// the LAS 1.2 codec in both directions (las.hpp, f8).
 #include "codecs.hpp"
 #include "csim_codecs.hpp"
 #include "hostutil.hpp"
 #include "ingest.hpp"
 #include "ingest_index.hpp"
+#include "las.hpp"
+#include "las_index.hpp"
 
 #include <algorithm>
+#include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <vector>
 
@@ -920,6 +925,236 @@ int mc_text_decode_batch(mc_ctx* c, int sep, int32_t n_cols, const void* d_text,
                          const int64_t* frame_start_ns, int64_t* frame_start_out, int64_t* bad_line) {
   CHECK_ARG(out, "batch is NULL");
   return text_decode(c, sep, n_cols, d_text, bytes, 0, nullptr, 0, out, frame_start_ns, frame_start_out, bad_line);
+}
+
+}  // extern "C"
+
+// ---- LAS 1.2 (f8): save_las (LMC:950-963) / _export_las (CSIM:1671-1698) and their inverse ---------
+namespace {
+
+struct LasWrite {
+  int fmt;
+  const double* scale;
+  const double* off;
+  double imul, tmul;
+  const char* software;
+  int32_t year, doy;
+};
+
+int las_encode(mc_ctx* c, const Source& src, int64_t n, const LasWrite& p, void* d_out, int64_t out_bytes,
+               int64_t* bad_row) {
+  if (bad_row) *bad_row = -1;
+  const int64_t reclen = mclas::nominal(p.fmt);
+  CHECK_ARG(reclen, "point format %d: formats 0 to 3 are written", p.fmt);
+  CHECK_ARG(p.scale && p.off, "scale / offset is NULL");
+  for (int k = 0; k < 3; ++k)
+    CHECK_ARG(std::isfinite(p.scale[k]) && p.scale[k] > 0.0 && std::isfinite(p.off[k]),
+              "scale must be finite and > 0, offset finite (axis %d: %g, %g)", k, p.scale[k], p.off[k]);
+  CHECK_ARG(std::isfinite(p.imul) && std::isfinite(p.tmul), "the intensity / time multipliers must be finite");
+  CHECK_ARG(p.year >= 0 && p.year <= 65535 && p.doy >= 0 && p.doy <= 366, "creation date %d / day %d", p.year, p.doy);
+  CHECK_ARG(n >= 0, "negative point count");
+  CHECK_ARG(n < ((int64_t)1 << 32), "LAS 1.2 stores the point count as a u32: %lld points do not fit", (long long)n);
+  const int64_t need = mclas::kHeader + n * reclen;
+  if (out_bytes < need)
+    return fail(MC_ERR_SPACE, "LAS output needs %lld bytes, buffer has %lld", (long long)need, (long long)out_bytes);
+  CHECK_ARG(d_out, "d_out is NULL");
+  CHECK_ARG(n == 0 || src.aos || src.batch, "points pointer is NULL");
+  DeviceGuard g(c->device);
+  struct Stats {
+    unsigned long long bad[2];
+    int32_t mm[6];
+  } st = {{0ull, ~0ull}, {INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN, INT32_MAX, INT32_MIN}};
+  if (n > 0) {
+    const int64_t tiles = (n + kLasTile - 1) / kLasTile;   // < 2^23
+    char* d = nullptr;
+    if (int r = codec_scratch(c, sizeof st + (size_t)tiles * 6 * sizeof(int32_t), &d)) return r;
+    HIPCHK(hipMemcpyAsync(d, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
+    LasEncArgs a;
+    a.rows = src.aos;
+    a.ld = src.ld;
+    a.cols = src.batch ? src.batch->d_cols : nullptr;
+    a.C = src.batch ? src.batch->C : 0;
+    a.doff = src.batch ? src.batch->d_doff : nullptr;
+    a.poff = src.batch ? src.batch->d_poff : nullptr;
+    a.fstart = src.batch ? src.batch->d_frame_start : nullptr;
+    a.F = src.batch ? src.batch->F : 0;
+    a.n = n;
+    std::copy_n(p.scale, 3, a.scale);
+    std::copy_n(p.off, 3, a.off);
+    a.imul = p.imul;
+    a.tmul = p.tmul;
+    a.fmt = p.fmt;
+    a.reclen = (int32_t)reclen;
+    a.body = static_cast<char*>(d_out) + mclas::kHeader;
+    a.bad = reinterpret_cast<unsigned long long*>(d);
+    a.tile_mm = reinterpret_cast<int32_t*>(d + sizeof st);
+    const dim3 grid((uint32_t)tiles), blk(kCodecBlock);
+    const dim3 rgrid((uint32_t)std::min<int64_t>((tiles + kCodecBlock - 1) / kCodecBlock, kLasReduceGrid));
+    {
+      TimedRegion tr(c, &c->codec_ev, c->stream);
+      if (src.batch) hipLaunchKernelGGL(k_las_encode<true>, grid, blk, 0, c->stream, a);
+      else hipLaunchKernelGGL(k_las_encode<false>, grid, blk, 0, c->stream, a);
+      hipLaunchKernelGGL(k_las_minmax, rgrid, blk, 0, c->stream, (const int32_t*)a.tile_mm, tiles,
+                         reinterpret_cast<int32_t*>(d + offsetof(Stats, mm)));
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&st, d, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (st.bad[0]) {
+      if (bad_row) *bad_row = (int64_t)st.bad[1];
+      return fail(MC_ERR_INVALID,
+                  "row %lld (the first of %llu): a coordinate is not finite or rint((v - offset) / scale) is outside "
+                  "int32, or the intensity is NaN or outside 0..65535",
+                  (long long)st.bad[1], st.bad[0]);
+    }
+  }
+  uint8_t hdr[mclas::kHeader];
+  mclas::write_header(hdr, p.fmt, n, p.scale, p.off, st.mm, p.software ? p.software : "mcdeskew", p.year, p.doy);
+  HIPCHK(hipMemcpyAsync(d_out, hdr, sizeof hdr, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return MC_OK;
+}
+
+int las_decode(mc_ctx* c, const void* d_file, int64_t bytes, int fmt, int64_t reclen, int64_t offset, int64_t n,
+               const double* scale, const double* off, double* d_rows, int64_t ld, mc_batch* out, double iscale,
+               const int64_t* frame_start_ns, int64_t* frame_start_out, int64_t* bad_row) {
+  if (bad_row) *bad_row = -1;
+  CHECK_ARG(c && d_file && scale && off, "NULL argument");
+  CHECK_ARG(((uintptr_t)d_file & 15) == 0, "d_file must be 16-byte aligned (and padded to a multiple of 16 bytes)");
+  char msg[256];
+  if (mclas::check_layout(bytes, fmt, reclen, offset, n, msg, sizeof msg)) return ingest_fail(msg);
+  if (out) {
+    CHECK_ARG(out->ctx == c, "batch belongs to another context");
+    if (!out->has_t()) return fail(MC_ERR_STATE, "mc_las_decode_batch needs a batch created with MC_BATCH_WITH_TIME");
+    CHECK_ARG(out->N == n, "the batch holds %lld points, the file %lld", (long long)out->N, (long long)n);
+  } else {
+    CHECK_ARG(n == 0 || d_rows, "d_rows is NULL");
+  }
+  DeviceGuard g(c->device);
+  if (out && (frame_start_ns || n == 0)) {
+    std::vector<int64_t> z((size_t)out->F, 0);
+    const int64_t* s = frame_start_ns ? frame_start_ns : z.data();
+    if (int r = mc_batch_set_frame_start_ns(out, s)) return r;
+    if (frame_start_out) std::copy_n(s, out->F, frame_start_out);
+  }
+  if (n == 0) return MC_OK;
+  unsigned long long bad[2] = {0ull, ~0ull};
+  char* d = nullptr;
+  if (int r = codec_scratch(c, sizeof bad, &d)) return r;
+  HIPCHK(hipMemcpyAsync(d, bad, sizeof bad, hipMemcpyHostToDevice, c->stream));
+  LasDecArgs a;
+  a.file = static_cast<const uint8_t*>(d_file);
+  a.offset = offset;
+  a.fmt = fmt;
+  a.reclen = (int32_t)reclen;
+  a.n = n;
+  std::copy_n(scale, 3, a.scale);
+  std::copy_n(off, 3, a.off);
+  a.rows = d_rows;
+  a.ld = ld;
+  a.cols = out ? out->d_cols : nullptr;
+  a.doff = out ? out->d_doff : nullptr;
+  a.poff = out ? out->d_poff : nullptr;
+  a.fstart = out ? out->d_frame_start : nullptr;
+  a.F = out ? out->F : 0;
+  a.iscale = iscale;
+  a.bad = reinterpret_cast<unsigned long long*>(d);
+  const dim3 grid((uint32_t)((n + kLasDecTile - 1) / kLasDecTile)), blk(kLasDecTile);
+  {
+    TimedRegion tr(c, &c->codec_ev, c->stream);
+    if (out && !frame_start_ns)
+      hipLaunchKernelGGL(k_las_frame_start, dim3((out->F + kCodecBlock - 1) / kCodecBlock), dim3(kCodecBlock), 0,
+                         c->stream, a);
+    if (out) hipLaunchKernelGGL(k_las_decode<true>, grid, blk, 0, c->stream, a);
+    else hipLaunchKernelGGL(k_las_decode<false>, grid, blk, 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  if (out) {
+    HIPCHK(hipMemcpyAsync(bad, d, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    if (!frame_start_ns) {
+      std::vector<int64_t> fs((size_t)out->F);
+      HIPCHK(hipMemcpyAsync(fs.data(), out->d_frame_start, fs.size() * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      out->has_starts = true;
+      ++out->prep_ver;
+      if (frame_start_out) std::copy(fs.begin(), fs.end(), frame_start_out);
+    }
+    if (int r = mcimpl::batch_columns_written(out)) return r;
+  }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (bad[0]) {
+    if (bad_row) *bad_row = (int64_t)bad[1];
+    return fail(MC_ERR_INVALID,
+                "point %lld (the first of %llu): rint(gps_time * 1e9) minus its frame start does not fit int32 "
+                "nanoseconds", (long long)bad[1], bad[0]);
+  }
+  return MC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mc_las_probe(const void* file, int64_t bytes, int32_t* point_format, int32_t* record_length,
+                 int64_t* offset_to_points, int64_t* n_points, double* scale, double* offset, double* bounds) {
+  char msg[256];
+  mclas::Header h;
+  if (mclas::probe(static_cast<const uint8_t*>(file), bytes, &h, msg, sizeof msg)) return ingest_fail(msg);
+  if (point_format) *point_format = h.format;
+  if (record_length) *record_length = h.reclen;
+  if (offset_to_points) *offset_to_points = h.offset;
+  if (n_points) *n_points = h.n;
+  if (scale) std::copy_n(h.scale, 3, scale);
+  if (offset) std::copy_n(h.off, 3, offset);
+  if (bounds) std::copy_n(h.bounds, 6, bounds);
+  return MC_OK;
+}
+
+int mc_las_encode(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n, int point_format, const double* scale,
+                  const double* offset, double intensity_mul, double time_mul, const char* software, int32_t year,
+                  int32_t day_of_year, void* d_out, int64_t out_bytes, int64_t* bad_row) {
+  CHECK_ARG(c, "ctx is NULL");
+  const int64_t need = time_mul != 0.0 ? 5 : 4;
+  if (ld < need)
+    return fail(MC_ERR_INDEX, "LAS rows are x, y, z, intensity%s: ld >= %lld; got %lld", need == 5 ? ", timestamp" : "",
+                (long long)need, (long long)ld);
+  Source src;
+  src.aos = d_rows;
+  src.ld = ld;
+  return las_encode(c, src, n, {point_format, scale, offset, intensity_mul, time_mul, software, year, day_of_year},
+                    d_out, out_bytes, bad_row);
+}
+
+int mc_las_encode_batch(mc_ctx* c, const mc_batch* b, int point_format, const double* scale, const double* offset,
+                        double intensity_mul, double time_mul, const char* software, int32_t year, int32_t day_of_year,
+                        void* d_out, int64_t out_bytes, int64_t* bad_row) {
+  CHECK_ARG(c && b, "NULL argument");
+  CHECK_ARG(b->ctx == c, "batch belongs to another context");
+  if (time_mul != 0.0) {
+    if (!b->has_t()) return fail(MC_ERR_STATE, "a LAS time needs a batch created with MC_BATCH_WITH_TIME");
+    if (!b->has_starts) return fail(MC_ERR_STATE, "the batch's frame starts are not set (mc_batch_set_frame_start_ns)");
+  }
+  Source src;
+  src.batch = b;
+  return las_encode(c, src, b->N, {point_format, scale, offset, intensity_mul, time_mul, software, year, day_of_year},
+                    d_out, out_bytes, bad_row);
+}
+
+int mc_las_decode(mc_ctx* c, const void* d_file, int64_t bytes, int point_format, int64_t record_length,
+                  int64_t offset_to_points, int64_t n_points, const double* scale, const double* offset, double* d_rows,
+                  int64_t ld) {
+  if (ld < 5) return fail(MC_ERR_INDEX, "decoded rows are x, y, z, intensity, gps_time: ld >= 5; got %lld", (long long)ld);
+  return las_decode(c, d_file, bytes, point_format, record_length, offset_to_points, n_points, scale, offset, d_rows, ld,
+                    nullptr, 1.0, nullptr, nullptr, nullptr);
+}
+
+int mc_las_decode_batch(mc_ctx* c, const void* d_file, int64_t bytes, int point_format, int64_t record_length,
+                        int64_t offset_to_points, int64_t n_points, const double* scale, const double* offset,
+                        double intensity_scale, mc_batch* out, const int64_t* frame_start_ns, int64_t* frame_start_out,
+                        int64_t* bad_row) {
+  CHECK_ARG(out, "batch is NULL");
+  return las_decode(c, d_file, bytes, point_format, record_length, offset_to_points, n_points, scale, offset, nullptr, 5,
+                    out, intensity_scale, frame_start_ns, frame_start_out, bad_row);
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@ import numpy as np
 from . import _lib
 from . import codecs as _codecs
 from . import config as _config
+from . import las as _las
 from . import trajectory as _traj
 from ._lib import check, fptr, ptr
 from .runtime import Context, default_context, deskew_points_f64, host_pool
@@ -274,10 +275,14 @@ class LiDARMotionSimulator:
         las.intensity = (points[:, 3] * 65535).astype(np.uint16)
         las.write(filename)
 
-    def save_results(self, results, output_dir="lidar_simulation_output"):
+    def save_results(self, results, output_dir="lidar_simulation_output", las="laspy"):
         """LMC:860-931: motion / trajectory CSVs, per-frame raw and aligned PCDs, the merged PCDs,
         LAS and LVX.  Every PCD's point lines come from one GPU launch pair over all frames; the
-        merged files reuse the frames' lines (a vstack of the clouds prints the same lines)."""
+        merged files reuse the frames' lines (a vstack of the clouds prints the same lines).
+        ``las``: "laspy" (the default) is the reference's save_las; "device" writes
+        merged_aligned.las through las.write_las(variant="lmc") without laspy."""
+        if las not in ("laspy", "device"):
+            raise ValueError(f"las must be 'laspy' or 'device', got {las!r}")
         import pandas as pd
         os.makedirs(output_dir, exist_ok=True)
         print(f"Saving results to {output_dir}...")
@@ -317,7 +322,13 @@ class LiDARMotionSimulator:
             if merged_aligned is None:
                 # LMC:903 reads merged_aligned, unbound when LMC:887 skipped the merge
                 raise UnboundLocalError("local variable 'merged_aligned' referenced before assignment")
-            self.save_las(merged_aligned, os.path.join(output_dir, "merged_aligned.las"))
+            las_path = os.path.join(output_dir, "merged_aligned.las")
+            if las == "device" and rows is not None:   # the merged cloud is the aligned rows still on the device
+                _write(las_path, _las.encode_las_device_rows(rows.d_aligned, len(merged_aligned)))
+            elif las == "device":
+                _las.write_las(las_path, merged_aligned, variant="lmc", context=self.context)
+            else:
+                self.save_las(merged_aligned, las_path)
             print("LAS format saved successfully")
         except Exception as e:
             print(f"Could not save LAS format: {e}")
