@@ -381,7 +381,10 @@ __device__ __noinline__ Fmt6 fmt6_prepare_exact(double v) {
     N = q;
   }
   r.kind = 0;
-  if ((uint64_t)(N >> 32) == 0) {
+  // e < 0: only then can N be below 2^32, and N < 2^73 there, so the 64-bit view of N >> 32 is all of
+  // it.  Without it 2^100 (N = 2^106 5^6, bits 32..95 zero) printed "0.000000", as did every
+  // float32-valued |v| >= 2^90 with enough trailing zero bits.
+  if (e < 0 && (uint64_t)(N >> 32) == 0) {
     const uint32_t n = (uint32_t)N;
     const uint32_t ip = n / 1000000u;
     r.ip = ip;
@@ -438,7 +441,7 @@ __device__ __forceinline__ void fmt6_write(const Fmt6& f, char* p) {
     fp = q;
   }
   p[nd] = '.';
-  if ((uint64_t)(f.ip >> 32) == 0) {
+  if (nd <= 10 && (uint64_t)(f.ip >> 32) == 0) {   // nd: the 64-bit view misses bits 96.. (2^100: bits 32..95 zero)
     uint32_t y = (uint32_t)f.ip;
     for (int i = nd - 1; i >= 0; --i) {
       const uint32_t q = y / 10u;

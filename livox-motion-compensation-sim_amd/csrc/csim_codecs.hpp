@@ -199,7 +199,7 @@ __device__ __forceinline__ Fmt6 fmt0_prepare(double v) {
     if (rem > half || (rem == half && (q & 1))) ++q;
     r.ip = q;
   }
-  if ((uint64_t)(r.ip >> 32) == 0) {
+  if (e < 0 && (uint64_t)(r.ip >> 32) == 0) {   // e >= 0: ip >= 2^52, and 2^100 (bits 32..95 zero) printed "6"
     r.nd = u32_digits((uint32_t)r.ip);
   } else if ((uint64_t)(r.ip >> 64) == 0) {
     r.nd = u64_digits((uint64_t)r.ip);

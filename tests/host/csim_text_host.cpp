@@ -7,6 +7,10 @@
 // "nan" whatever its sign, as Python does), then whole lines of the three descriptors (PCD, XYZ, CSV)
 // are emitted back to back into a guarded buffer and compared.  Prints "bad <count>"; exit status
 // = min(count, 255).
+//   csim_text_host file <in> <out>   in: raw float64 values; out: per value one line, the texts of
+//                                    fmt6_prepare, fmt0_prepare and csim_fmt6_prepare separated by tabs
+//                                    ("range" for a value beyond the formatters).  The harness computes;
+//                                    tests/test_corevalues_cpu.py compares.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -59,7 +63,33 @@ static void check_value(double v) {
   }
 }
 
+// file mode: the three formatters' text of every value of a file, for the test to compare
+static int file_mode(const char* in_path, const char* out_path) {
+  FILE* in = std::fopen(in_path, "rb");
+  FILE* out = std::fopen(out_path, "wb");
+  if (!in || !out) return 2;
+  double v;
+  while (std::fread(&v, sizeof v, 1, in) == 1) {
+    for (int which = 0; which < 3; ++which) {
+      const Fmt6 f = which == 1 ? fmt0_prepare(v) : which == 2 ? csim_fmt6_prepare(v) : fmt6_prepare(v);
+      char got[96];
+      if (f.kind == 3) {
+        std::fputs("range", out);
+      } else {
+        if (which == 1) fmt0_write(f, got);
+        else if (which == 2) csim_fmt6_write(f, got);
+        else fmt6_write(f, got);
+        std::fwrite(got, 1, (size_t)f.len, out);
+      }
+      std::fputc(which < 2 ? '\t' : '\n', out);
+    }
+  }
+  std::fclose(in);
+  return std::fclose(out) ? 2 : 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc == 4 && !std::strcmp(argv[1], "file")) return file_mode(argv[2], argv[3]);
   const int N = argc > 1 ? std::atoi(argv[1]) : 200000;
   std::mt19937_64 g(7);
   std::vector<double> vals = {0.0, -0.0, 0.5, 1.5, 2.5, -0.5, -0.3, 0.3, -1.5, 3.5, 0.49999999999999994, 0.5000000000000001,
@@ -67,7 +97,11 @@ int main(int argc, char** argv) {
                               0.9999995, 9.9999995, 999.9999995, 0.0000005, 0.0000015, 0.0078125, 1e15 + 0.5, 4503599627370495.5,
                               4503599627370496.5, 9.5, 10.5, 99.5, 999999.5, 1.7e18, 1700000000000001000.0,
                               std::ldexp(1.0, 107), -std::ldexp(1.0, 107), std::nextafter(std::ldexp(1.0, 107), 0.0),
-                              1e300, (double)INFINITY, -(double)INFINITY, std::nan(""), -std::nan("")};
+                              1e300, (double)INFINITY, -(double)INFINITY, std::nan(""), -std::nan(""),
+                              // integers whose bits 32..95 are all zero (a 64-bit view of ip >> 32 took them for
+                              // 32-bit values: "0.000000" and "6" for 2^100), and float32 values with as many zeros
+                              std::ldexp(1.0, 96), std::ldexp(1.0, 100), -std::ldexp(1.0, 106), std::ldexp(2047.0, 96),
+                              std::ldexp(1.0, 90), std::ldexp(3.0, 90), -0x1.62c7p+106, -0x1.8d4p+101, 0x1.fffffep+106};
   // random doubles over every exponent up to 2^107 (and a few beyond), random sign and mantissa
   for (int i = 0; i < N; ++i) {
     const uint64_t r = g();

@@ -5,6 +5,9 @@
 // strtod (Python's float()); out-of-window tokens must be flagged and carry no value.  argv[1] =
 // random tokens per (significant digits, fractional digits) pair.  Prints "bad <count>"; exit status
 // = min(count, 255).
+//   ingest_host file <in> <out>   in: newline-separated tokens; out: per token the value's bits (u64), bad
+//                                 and len (i32 each), parsed with a ' ' separator behind the token.  The
+//                                 harness computes; tests/test_corevalues_cpu.py compares.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -81,7 +84,33 @@ static std::string make(const std::string& digits, int k) {
   return digits.substr(0, n - k) + "." + digits.substr(n - k);
 }
 
+// file mode: every token of a file parsed in place (the '\n' behind it ends it), for the test to compare
+static int file_mode(const char* in_path, const char* out_path) {
+  std::string text;
+  if (FILE* in = std::fopen(in_path, "rb")) {
+    char buf[65536];
+    size_t k;
+    while ((k = std::fread(buf, 1, sizeof buf, in)) > 0) text.append(buf, k);
+    std::fclose(in);
+  } else {
+    return 2;
+  }
+  FILE* out = std::fopen(out_path, "wb");
+  if (!out) return 2;
+  const char* e = text.data() + text.size();
+  for (const char* p = text.data(); p < e;) {
+    const char* nl = (const char*)std::memchr(p, '\n', (size_t)(e - p));
+    const IngestTok t = ingest_token(p, e, ' ', false);
+    struct { uint64_t bits; int32_t bad, len; } o = {bits_of(t.v), t.bad, t.len};
+    static_assert(sizeof o == 16, "packed");
+    std::fwrite(&o, sizeof o, 1, out);
+    p = nl ? nl + 1 : e;
+  }
+  return std::fclose(out) ? 2 : 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc == 4 && !std::strcmp(argv[1], "file")) return file_mode(argv[2], argv[3]);
   const int per = argc > 1 ? std::atoi(argv[1]) : 530;
   std::mt19937_64 rng(20240607);
   // every significant-digit count 1..19 with every fractional length 0..19
