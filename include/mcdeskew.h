@@ -32,6 +32,8 @@
  *     (lvx, lvx2, lvx3)                                          mc_csim_lvx_encode_batch
  *   DataExporter._export_pcd / _xyz / _csv     CSIM:1643-1715  mc_csim_text_encode / mc_csim_text_encode_batch
  *   (build-added)                          mc_deskew(MC_MODE_POSE_SLERP)
+ *   (build-added: a11 into the sensor frame at a reference     mc_deskew_relative, mc_deskew_points_relative_f64,
+ *    time per frame)                                             mc_pose_at, mc_batch_time_spans
  *
  * LMC = lidar_motion_compensation.py, CSIM = livox_mid70_complete_simulator.py.
  *
@@ -437,6 +439,35 @@ int mc_batch_checksum(mc_batch* b, double* sums5);
 /* out must have the same frame counts as in (it may be the same batch: in-place). */
 int mc_deskew(mc_ctx* ctx, const mc_batch* in, mc_batch* out, int mode, int pose_select);
 
+/* The SLERP deskew into the SENSOR frame at a reference time per frame (build-added, as SURVEY §8a
+ * row a11 is): with (R_ref, pos_ref) = the SLERP / LERP pose of the trajectory at t_ref[f] (seconds,
+ * the pose table's time base, clamped to the table exactly as a point's time is),
+ *   p' = R_ref^T ( R(q(t)) p + pos(t) - pos_ref ),   t = frame_time[f] + t_ns * 1e-9,
+ * x, y, z formed in float64 and rounded once to float32 on the store; intensity and t_ns pass through
+ * as in mc_deskew.  The inverse reference pose is folded into the frame's pose records once per frame
+ * and segment (in float64, where pos - pos_ref cancels), so the per-point work and the bytes moved are
+ * those of mc_deskew(MC_MODE_POSE_SLERP), and a float32 batch stays exact for GPS / UTM-scale
+ * trajectories.  A point whose time equals t_ref[f] comes back as itself; p_global = R_ref p' + pos_ref
+ * with the pose of mc_pose_at(t_ref[f]).  t_ref[n_frames] is a host array, copied and not retained;
+ * NULL: each frame's own time (mc_batch_set_frame_times), i.e. frame start.  Preconditions and error
+ * codes of mc_deskew(MC_MODE_POSE_SLERP); a non-finite t_ref -> MC_ERR_INVALID.  out may be in.
+ * Asynchronous on the context stream like mc_deskew, after a first call that sizes the batch's
+ * relative table (one synchronisation; again when the trajectory, the frame times, t_ns or t_ref
+ * change).  No mc_deskew_steps / mc_deskew_pcd / mc_tune_order variants and no IMU-mode variant. */
+int mc_deskew_relative(mc_ctx* ctx, const mc_batch* in, mc_batch* out, const double* t_ref);
+
+/* The pose the library interpolates at n arbitrary finite times t (seconds): R (n, 3, 3) row-major and
+ * pos (n, 3), quaternion SLERP + position LERP of the uploaded trajectory, clamped to the table — the
+ * device function that builds mc_deskew_relative's reference poses (build-added, like a11).
+ * A non-finite time -> MC_ERR_INVALID; no trajectory -> MC_ERR_STATE.  Synchronous. */
+int mc_pose_at(mc_ctx* ctx, int64_t n, const double* t, double* R, double* pos);
+
+/* Per-frame [min, max] of t_ns over the frame's valid points, as the library keeps them for the
+ * per-point modes (computed here if stale): t_min[n_frames], t_max[n_frames]; an empty frame has
+ * min > max.  A frame-end reference is frame_time[f] + t_max[f] * 1e-9.  A batch without
+ * MC_BATCH_WITH_TIME -> MC_ERR_STATE.  Synchronous. */
+int mc_batch_time_spans(mc_batch* b, int32_t* t_min, int32_t* t_max);
+
 /* Measure, on this device, which sub-tile order streams the mode's deskew kernel faster for batches
  * shaped like `in` (dealt over the 8 XCDs vs XCD-contiguous: the faster one differs between MI355X
  * boxes by up to 7 %) and use it for every later launch of that mode on batches of the same padded
@@ -480,6 +511,15 @@ int mc_rotation_from_euler_xyz(int64_t n, const double* rpy, double* R);
 int mc_deskew_points_f64(mc_ctx* ctx, int mode, int32_t n_frames, const int64_t* counts, const double* points,
                          int64_t ld, const int64_t* t_ns, const double* frame_times, const int64_t* frame_start_ns,
                          double* out);
+
+/* mc_deskew_relative's contract on float64 rows (build-added, like a11): the arguments of
+ * mc_deskew_points_f64(MC_MODE_POSE_SLERP) plus t_ref[n_frames] (NULL: frame_times).  Computed by
+ * the direct formula, not the folded records: per point the global float64 value, minus pos_ref, then
+ * R_ref^T — an independent check of the batch path.  A non-finite t_ref -> MC_ERR_INVALID.
+ * Synchronous. */
+int mc_deskew_points_relative_f64(mc_ctx* ctx, int32_t n_frames, const int64_t* counts, const double* points,
+                                  int64_t ld, const int64_t* t_ns, const double* frame_times, const double* t_ref,
+                                  double* out);
 
 /* The frame loop (LMC:802-832) on host arrays: frames[f] (counts[f], lds[f] >= 4) float64 rows
  * -> outs[f] (counts[f], 4) float64, pose per frame from the uploaded trajectory (pose_select as

@@ -232,6 +232,21 @@ struct mc_batch {
   mc::FrameWin* d_swin = nullptr;  // per sub-tile window, double-buffered (2 * n_sub)
   double* d_partial = nullptr;
   bool has_times = false, has_starts = false, trange_valid = false;
+  // mc_deskew_relative: the per-frame relative segment table (relative.hpp) — frame f's records
+  // [d_roff[f], d_roff[f+1]) are its segments [klo, khi] folded into its reference pose.  Kept with
+  // the batch: the offsets hold while the trajectory upload (rel_traj) and the batch's frame times and
+  // t_ns spans (rel_frames = prep_ver) are the ones they were counted for, the records while the
+  // reference times are the same too (rel_own: each frame's own time; else rel_tref).
+  mc::PoseSeg* d_rel = nullptr;
+  size_t rel_cap = 0;              // records allocated
+  int64_t rel_total = 0;           // records in use (d_roff[F])
+  int64_t* d_roff = nullptr;       // F + 1
+  int32_t* d_relw = nullptr;       // F window widths (the count pass)
+  double* d_tref = nullptr;        // F reference times
+  double* d_refpose = nullptr;     // F reference quaternions (4 F), then F reference positions (3 F)
+  bool rel_offsets_valid = false, rel_valid = false, rel_own = false;
+  uint64_t rel_traj = 0, rel_frames = 0;
+  std::vector<double> rel_tref;
   // MC_BATCH_WITH_PCD_LEN: ASCII PCD text bytes per 256-point block (layout.hpp PcdCount sums).
   // data_ver counts the writes of the x|y|z|intensity columns; pcd_ver is the data_ver the sums
   // were written with (current iff equal).

@@ -5,6 +5,7 @@
 // plain pointers and sizes in, status codes out (thread-local message in mc_last_error()).
 #include "../../include/mcdeskew.h"
 #include "kernels.hpp"
+#include "relative.hpp"
 #include <hip/hip_ext.h>
 #include "scan.hpp"
 #include "raymarch.hpp"
@@ -17,6 +18,7 @@
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -355,6 +357,7 @@ int mc_batch_destroy(mc_batch* b) {
   b->d_frec = nullptr;
   dev_free(b->d_ftile); dev_free(b->d_strange); dev_free(b->d_swin);
   dev_free(b->d_pcd_len);
+  dev_free(b->d_rel); dev_free(b->d_roff); dev_free(b->d_relw); dev_free(b->d_tref); dev_free(b->d_refpose);
   delete b;
   return MC_OK;
 }
@@ -1038,7 +1041,143 @@ int mc_deskew_steps(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int 
   return deskew_steps_pipelined(c, in, out, mode, pose_select, n_steps, sample_every);
 }
 
-constexpr int64_t kPipeRows = 1 << 21;                                 // 64 MB of (n,4) float64 (max chunk)
+// ---- the relative (sensor-frame) SLERP deskew: relative.hpp ---------------------------------------
+namespace {
+// The batch's relative table for reference times t_ref (null: each frame's own time), built after the
+// step's k_prep (sp: its plan) on the main stream.  Cached with the batch: nothing is launched when
+// the table already holds these references over these tables; the offsets (a count pass and one
+// synchronisation to size the table) are redone only when the trajectory, the frame times or the
+// t_ns spans changed.
+int rel_table(mc_ctx* c, mc_batch* b, const StepPlan& sp, const double* t_ref) {
+  hipStream_t s = c->stream;
+  const int32_t F = b->F;
+  const bool same_tab = b->rel_offsets_valid && b->rel_traj == c->traj_ver && b->rel_frames == b->prep_ver;
+  const bool same_ref = b->rel_own == (t_ref == nullptr) &&
+                        (!t_ref || (b->rel_tref.size() == (size_t)F && std::equal(t_ref, t_ref + F, b->rel_tref.begin())));
+  if (same_tab && b->rel_valid && same_ref) return MC_OK;
+  b->rel_valid = false;
+  RelTableArgs ra;
+  std::memset(&ra, 0, sizeof(ra));
+  ra.F = F;
+  ra.frame_time = b->d_frame_time; ra.trange = b->d_trange;
+  ra.pose_time = c->d_time; ra.T = c->T; ra.nseg = sp.pa.nseg;
+  if (!same_tab) {
+    b->rel_offsets_valid = false;
+    if (!b->d_roff) {
+      if (int r = dev_alloc(&b->d_roff, (size_t)F + 1)) return r;
+      if (int r = dev_alloc(&b->d_relw, (size_t)F)) return r;
+      if (int r = dev_alloc(&b->d_tref, (size_t)F)) return r;
+      if (int r = dev_alloc(&b->d_refpose, 7 * (size_t)F)) return r;
+    }
+    ra.width = b->d_relw;
+    hipLaunchKernelGGL(k_rel_count, dim3((F + kBlock - 1) / kBlock), dim3(kBlock), 0, s, ra);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> w((size_t)F);
+    HIPCHK(hipMemcpyAsync(w.data(), b->d_relw, (size_t)F * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<int64_t> roff((size_t)F + 1, 0);
+    for (int32_t f = 0; f < F; ++f) {
+      if (w[f] < 1 || (int64_t)w[f] > sp.pa.nseg) return fail(MC_ERR_HIP, "relative table: window of frame %d", f);
+      roff[f + 1] = roff[f] + w[f];
+    }
+    if ((size_t)roff[F] > b->rel_cap) {
+      if (int r = sync_all(c)) return r;
+      dev_free(b->d_rel);
+      b->rel_cap = 0;
+      if (int r = dev_alloc(&b->d_rel, (size_t)roff[F])) return r;
+      b->rel_cap = (size_t)roff[F];
+    }
+    HIPCHK(hipMemcpyAsync(b->d_roff, roff.data(), roff.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    b->rel_total = roff[F];
+    b->rel_traj = c->traj_ver;
+    b->rel_frames = b->prep_ver;
+    b->rel_offsets_valid = true;
+  }
+  const double* d_t = b->d_frame_time;
+  if (t_ref) {
+    // the caller's array is copied, not retained
+    HIPCHK(hipMemcpyAsync(b->d_tref, t_ref, (size_t)F * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    d_t = b->d_tref;
+  }
+  {
+    TimedRegion tr(c, &c->prep_ev, s);
+    PoseAtArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    pa.t = d_t; pa.n = F;
+    pa.pose_time = c->d_time; pa.pose_seg = sp.da.pose_seg; pa.nseg = sp.pa.nseg; pa.ntab = c->T;
+    pa.q = b->d_refpose; pa.pos = b->d_refpose + 4 * (size_t)F;
+    hipLaunchKernelGGL(k_pose_at, dim3((F + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pa);
+    ra.roff = b->d_roff; ra.pose_seg = sp.da.pose_seg;
+    ra.ref_q = pa.q; ra.ref_pos = pa.pos; ra.rel = b->d_rel;
+    const int64_t blocks = std::min<int64_t>((b->rel_total + kBlock - 1) / kBlock, 4096);
+    hipLaunchKernelGGL(k_rel_compose, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(kBlock), 0, s, ra);
+  }
+  HIPCHK(hipGetLastError());
+  b->rel_own = t_ref == nullptr;
+  if (t_ref) b->rel_tref.assign(t_ref, t_ref + F); else b->rel_tref.clear();
+  b->rel_valid = true;
+  return MC_OK;
+}
+}  // namespace
+
+int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const double* t_ref) {
+  if (int r = deskew_check(c, in, out, MC_MODE_POSE_SLERP, MC_POSE_SEARCHSORTED)) return r;
+  if (t_ref)
+    for (int32_t f = 0; f < in->F; ++f)
+      CHECK_ARG(std::isfinite(t_ref[f]), "t_ref[%d] is not finite", f);
+  if (in->F == 0) return MC_OK;
+  DeviceGuard g(c->device);
+  hipStream_t s = c->stream;
+  // No speculation, no fused next-prep launch, no any-order prep (deskew_steps_pipelined's treatment
+  // of itself): ordinary in-order launches of prep, compose and the kernel into table half h.
+  forget_speculation(c);
+  const int h = c->buf;
+  StepPlan sp;
+  if (int r = begin_steps(c, in, out, MC_MODE_POSE_SLERP, MC_POSE_SEARCHSORTED, h, false, &sp)) return r;
+  c->buf ^= 1;
+  c->prep_fence = true;
+  {
+    LaunchEvents ev(c);
+    launch_prep(sp, s, ev.e0, ev.e1, 0u);
+    ev.keep(&c->prep_ev);
+  }
+  HIPCHK(hipGetLastError());
+  if (sp.kernel < 0) return MC_OK;
+  mc_batch* b = const_cast<mc_batch*>(in);   // the table is cached with the input batch, as its k_prep outputs are
+  if (int r = rel_table(c, b, sp, t_ref)) return r;
+  const RelArgs rl{b->d_rel, b->d_roff};
+  {
+    LaunchEvents ev(c);
+    if (ev.e0) sp.da.span = span_take(c);
+    launch<k_deskew_points_rel>(false, sp.grid, s, ev.e0, ev.e1, 0u, sp.da, rl);
+    ev.keep(&c->main_ev);
+  }
+  HIPCHK(hipGetLastError());
+  out->wrote(false);
+  return MC_OK;
+}
+
+int mc_batch_time_spans(mc_batch* b, int32_t* t_min, int32_t* t_max) {
+  CHECK_ARG(b, "batch is NULL");
+  if (!b->has_t()) return fail(MC_ERR_STATE, "batch was created without MC_BATCH_WITH_TIME");
+  if (b->F == 0) return MC_OK;
+  CHECK_ARG(t_min && t_max, "NULL output");
+  mc_ctx* c = b->ctx;
+  DeviceGuard g(c->device);
+  if (!b->trange_valid) {
+    if (int r = compute_trange(b)) return r;
+    c->prep_fence = true;
+  }
+  std::vector<int2> tr((size_t)b->F);
+  HIPCHK(hipMemcpyAsync(tr.data(), b->d_trange, tr.size() * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int32_t f = 0; f < b->F; ++f) { t_min[f] = tr[f].x; t_max[f] = tr[f].y; }
+  return MC_OK;
+}
+
+constexpr int64_t kPipeRows = 1 << 21;                                // 64 MB of (n,4) float64 (max chunk)
 constexpr size_t kPipeBytes = (size_t)kPipeRows * 4 * sizeof(double);
 constexpr int kPoolThreads = 16;                                       // the box's CPU share per GPU
 constexpr int64_t kJobRows = 8192;                                     // rows per host copy job (256 KB)
@@ -1105,6 +1244,41 @@ int mc_transform_pointcloud_f64(mc_ctx* c, const double* points, int64_t n, int6
 
 // ---- per-point modes on host float64 rows (k_points_f64) --------------------------------------
 
+// The segment table of the uploaded trajectory / IMU samples for the float64 row paths and mc_pose_at
+// (k_prep's table lanes, no frames), kept until the mode or the upload it came from changes.  Queued
+// on the main stream; *nseg_out = its records.
+static int seg64_table(mc_ctx* c, int mode, int64_t* nseg_out) {
+  hipStream_t s = c->stream;
+  const uint64_t ver = mode == MC_MODE_POSE_SLERP ? c->traj_ver : c->imu_ver;
+  const int64_t nseg = mode == MC_MODE_POSE_SLERP ? std::max<int64_t>(c->T - 1, 1) : c->M;
+  *nseg_out = nseg;
+  const size_t seg_b = (size_t)nseg * (mode == MC_MODE_POSE_SLERP ? sizeof(PoseSeg) : sizeof(ImuSeg));
+  if (c->d_seg64 && c->seg64_mode == mode && c->seg64_ver == ver) return MC_OK;
+  c->seg64_mode = -1;
+  if (seg_b > c->seg64_bytes) {
+    if (c->d_seg64) (void)hipFree(c->d_seg64);
+    c->d_seg64 = nullptr;
+    c->seg64_bytes = 0;
+    HIPCHK(hipMalloc(&c->d_seg64, seg_b));
+    c->seg64_bytes = seg_b;
+  }
+  PrepArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.mode = mode;
+  pa.n_frames = 0;
+  pa.time = c->d_time; pa.pos = c->d_pos; pa.rpy = c->d_rpy; pa.T = c->T;
+  pa.imu_ts = c->d_imu_ts; pa.gyro = c->d_gyro; pa.M = c->M;
+  pa.pose_seg = static_cast<PoseSeg*>(c->d_seg64);
+  pa.imu_seg = static_cast<ImuSeg*>(c->d_seg64);
+  pa.nseg = nseg;
+  const uint32_t blocks = (uint32_t)(((nseg + 63) / 64 + 3) / 4);
+  hipLaunchKernelGGL(k_prep, dim3(blocks), dim3(kBlock), 0, s, pa);
+  HIPCHK(hipGetLastError());
+  c->seg64_mode = mode;
+  c->seg64_ver = ver;
+  return MC_OK;
+}
+
 int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, const double* points, int64_t ld,
                          const int64_t* t_ns, const double* frame_times, const int64_t* frame_start_ns, double* out) {
   CHECK_ARG(c, "ctx is NULL");
@@ -1128,34 +1302,8 @@ int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, 
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
   hipStream_t s = c->stream;
-  // the segment table of the uploaded trajectory / IMU samples (k_prep's table lanes, no frames)
-  const uint64_t ver = mode == MC_MODE_POSE_SLERP ? c->traj_ver : c->imu_ver;
-  const int64_t nseg = mode == MC_MODE_POSE_SLERP ? std::max<int64_t>(c->T - 1, 1) : c->M;
-  const size_t seg_b = (size_t)nseg * (mode == MC_MODE_POSE_SLERP ? sizeof(PoseSeg) : sizeof(ImuSeg));
-  if (!(c->d_seg64 && c->seg64_mode == mode && c->seg64_ver == ver)) {
-    c->seg64_mode = -1;
-    if (seg_b > c->seg64_bytes) {
-      if (c->d_seg64) (void)hipFree(c->d_seg64);
-      c->d_seg64 = nullptr;
-      c->seg64_bytes = 0;
-      HIPCHK(hipMalloc(&c->d_seg64, seg_b));
-      c->seg64_bytes = seg_b;
-    }
-    PrepArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    pa.mode = mode;
-    pa.n_frames = 0;
-    pa.time = c->d_time; pa.pos = c->d_pos; pa.rpy = c->d_rpy; pa.T = c->T;
-    pa.imu_ts = c->d_imu_ts; pa.gyro = c->d_gyro; pa.M = c->M;
-    pa.pose_seg = static_cast<PoseSeg*>(c->d_seg64);
-    pa.imu_seg = static_cast<ImuSeg*>(c->d_seg64);
-    pa.nseg = nseg;
-    const uint32_t blocks = (uint32_t)(((nseg + 63) / 64 + 3) / 4);
-    hipLaunchKernelGGL(k_prep, dim3(blocks), dim3(kBlock), 0, s, pa);
-    HIPCHK(hipGetLastError());
-    c->seg64_mode = mode;
-    c->seg64_ver = ver;
-  }
+  int64_t nseg = 0;
+  if (int r = seg64_table(c, mode, &nseg)) return r;
   // scratch: [doff (F+1) | per-frame value (F) | t_ns (n) | points (n, ld) | out (n, 4)]
   const size_t w_doff = 0, w_fv = (size_t)F + 1, w_t = w_fv + (size_t)F, w_pts = w_t + (size_t)n,
                w_out = w_pts + (size_t)n * (size_t)ld, words = w_out + 4 * (size_t)n;
@@ -1181,6 +1329,88 @@ int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, 
     TimedRegion tr(c, &c->main_ev, s);
     if (mode == MC_MODE_POSE_SLERP) hipLaunchKernelGGL(k_points_f64<1>, dim3(sc.grid(n)), dim3(kBlock), 0, s, a);
     else hipLaunchKernelGGL(k_points_f64<2>, dim3(sc.grid(n)), dim3(kBlock), 0, s, a);
+  }
+  HIPCHK(hipGetLastError());
+  return sc.fetch(out, w_out, 4 * (size_t)n);
+}
+
+int mc_pose_at(mc_ctx* c, int64_t n, const double* t, double* R, double* pos) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(n >= 0, "negative count");
+  if (c->T < 1) return fail(MC_ERR_STATE, "no trajectory uploaded (mc_set_trajectory)");
+  if (n == 0) return MC_OK;
+  CHECK_ARG(t && R && pos, "NULL t / R / pos");
+  for (int64_t i = 0; i < n; ++i) CHECK_ARG(std::isfinite(t[i]), "t[%lld] is not finite", (long long)i);
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  int64_t nseg = 0;
+  if (int r = seg64_table(c, MC_MODE_POSE_SLERP, &nseg)) return r;
+  // scratch: [t (n) | R (9 n) | pos (3 n)]
+  const size_t w_R = (size_t)n, w_pos = w_R + 9 * (size_t)n, words = w_pos + 3 * (size_t)n;
+  RowScratch sc;
+  if (int r = sc.open(c, n, words)) return r;
+  if (int r = sc.put(0, t, (size_t)n)) return r;
+  PoseAtArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.t = sc.at<const double>(0); a.n = n;
+  a.pose_time = c->d_time; a.pose_seg = static_cast<const PoseSeg*>(c->d_seg64); a.nseg = nseg; a.ntab = c->T;
+  a.R = sc.at<double>(w_R); a.pos = sc.at<double>(w_pos);
+  hipLaunchKernelGGL(k_pose_at, dim3(sc.grid(n)), dim3(kBlock), 0, c->stream, a);
+  HIPCHK(hipGetLastError());
+  if (int r = sc.fetch(R, w_R, 9 * (size_t)n)) return r;
+  return sc.fetch(pos, w_pos, 3 * (size_t)n);
+}
+
+int mc_deskew_points_relative_f64(mc_ctx* c, int32_t F, const int64_t* counts, const double* points, int64_t ld,
+                                  const int64_t* t_ns, const double* frame_times, const double* t_ref, double* out) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(F >= 0, "n_frames must be >= 0");
+  CHECK_ARG(F == 0 || counts, "counts is NULL");
+  if (ld < 3) return fail(MC_ERR_INDEX, "points need at least 3 columns (x, y, z); got %lld", (long long)ld);
+  std::vector<int64_t> doff;
+  if (int r = frame_offsets(counts, F, &doff)) return r;
+  if (c->T < 1) return fail(MC_ERR_STATE, "no trajectory uploaded (mc_set_trajectory)");
+  CHECK_ARG(F == 0 || frame_times, "frame times are NULL");
+  if (t_ref)
+    for (int32_t f = 0; f < F; ++f) CHECK_ARG(std::isfinite(t_ref[f]), "t_ref[%d] is not finite", f);
+  const int64_t n = doff[F];
+  if (n == 0) return MC_OK;
+  CHECK_ARG(points && t_ns && out, "NULL points / t_ns / out");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  hipStream_t s = c->stream;
+  int64_t nseg = 0;
+  if (int r = seg64_table(c, MC_MODE_POSE_SLERP, &nseg)) return r;
+  // scratch: [doff (F+1) | frame times (F) | t_ref (F) | ref q (4 F) | ref pos (3 F) | t_ns (n) |
+  //           points (n, ld) | out (n, 4)]
+  const size_t w_ft = (size_t)F + 1, w_tr = w_ft + (size_t)F, w_q = w_tr + (size_t)F, w_rp = w_q + 4 * (size_t)F,
+               w_t = w_rp + 3 * (size_t)F, w_pts = w_t + (size_t)n, w_out = w_pts + (size_t)n * (size_t)ld,
+               words = w_out + 4 * (size_t)n;
+  RowScratch sc;
+  if (int r = sc.open(c, n, words)) return r;
+  if (int r = sc.put(0, doff.data(), doff.size())) return r;
+  if (int r = sc.put(w_ft, frame_times, (size_t)F)) return r;
+  if (int r = sc.put(w_tr, t_ref ? t_ref : frame_times, (size_t)F)) return r;
+  if (int r = sc.put(w_t, t_ns, (size_t)n)) return r;
+  if (int r = sc.put(w_pts, points, (size_t)n * (size_t)ld)) return r;
+  PoseAtArgs pa;
+  std::memset(&pa, 0, sizeof(pa));
+  pa.t = sc.at<const double>(w_tr); pa.n = F;
+  pa.pose_time = c->d_time; pa.pose_seg = static_cast<const PoseSeg*>(c->d_seg64); pa.nseg = nseg; pa.ntab = c->T;
+  pa.q = sc.at<double>(w_q); pa.pos = sc.at<double>(w_rp);
+  PointsRelF64Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.p.pts = sc.at<const double>(w_pts); a.p.ld = ld; a.p.n = n;
+  a.p.t_ns = sc.at<const int64_t>(w_t);
+  a.p.doff = sc.at<const int64_t>(0); a.p.F = F;
+  a.p.ftime = sc.at<const double>(w_ft);
+  a.p.pose_time = c->d_time; a.p.pose_seg = pa.pose_seg; a.p.nseg = nseg; a.p.ntab = c->T;
+  a.p.out = sc.at<double>(w_out);
+  a.ref_q = pa.q; a.ref_pos = pa.pos;
+  {
+    TimedRegion tr(c, &c->main_ev, s);
+    hipLaunchKernelGGL(k_pose_at, dim3((F + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pa);
+    hipLaunchKernelGGL(k_points_rel_f64, dim3(sc.grid(n)), dim3(kBlock), 0, s, a);
   }
   HIPCHK(hipGetLastError());
   return sc.fetch(out, w_out, 4 * (size_t)n);

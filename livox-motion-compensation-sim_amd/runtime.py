@@ -102,13 +102,61 @@ class Context:
         return Batch(self, counts, with_time, with_pcd_len)
 
     def deskew(self, inp: "Batch", out: "Batch | None" = None, mode: str = "frame",
-               pose_select: str = "searchsorted") -> "Batch":
-        """Launch the hot path on the context stream (asynchronous); returns ``out``."""
+               pose_select: str = "searchsorted", reference=None) -> "Batch":
+        """Launch the hot path on the context stream (asynchronous); returns ``out``.
+
+        ``reference`` (``mode="pose_slerp"`` only; ``None``: the global frame, as ever): deskew into the
+        SENSOR frame at one reference time per frame (mc_deskew_relative),
+        p' = R_ref^T (R(q(t)) p + pos(t) - pos_ref) — ``"start"``: each frame's time; ``"end"``: the
+        time of each frame's last return (frame time + max t_ns, :meth:`Batch.time_spans`; the frame
+        time for an empty frame); an array of one absolute time (s) per frame; or one float, a keyframe
+        time common to all frames.  :meth:`reference_times` returns the times used."""
+        if reference is not None and mode != "pose_slerp":
+            raise ValueError(f"reference= needs mode='pose_slerp' (got mode={mode!r})")
         if out is None:
             out = Batch(self, inp.counts, with_time=inp.with_time)
+        if reference is not None:
+            t_ref = self.reference_times(inp, reference)
+            check(self.lib.mc_deskew_relative(self.handle, inp.handle, out.handle, ptr(t_ref, c_double)),
+                  "deskew_relative")
+            return out
         check(self.lib.mc_deskew(self.handle, inp.handle, out.handle, _lib.MODES[mode],
                                  _lib.POSE_SELECT[pose_select]), f"deskew[{mode}]")
         return out
+
+    def reference_times(self, inp: "Batch", reference):
+        """The per-frame reference times (s) :meth:`deskew` uses for ``reference``: ``None`` for
+        ``"start"`` (the library takes each frame's own time), else a float64 array of one per frame."""
+        if isinstance(reference, str):
+            if reference == "start":
+                return None
+            if reference == "end":
+                if inp.frame_times is None:
+                    raise _lib.McError("reference='end': frame times not set (Batch.set_frame_times)")
+                lo, hi = inp.time_spans()
+                # slerp_time(frame_time, max t_ns): the product rounded, then the sum, as a point's time
+                end = inp.frame_times + hi.astype(np.float64) * 1e-9
+                return np.ascontiguousarray(np.where(lo <= hi, end, inp.frame_times), dtype=np.float64)
+            raise ValueError(f"reference: 'start', 'end', a time or one time per frame expected (got {reference!r})")
+        t = np.asarray(reference, dtype=np.float64)
+        if t.ndim == 0:
+            return np.full(inp.n_frames, float(t), np.float64)
+        if t.shape != (inp.n_frames,):
+            raise ValueError(f"reference: one time per frame expected ({inp.n_frames}), got {t.shape}")
+        return np.ascontiguousarray(t)
+
+    def pose_at(self, t):
+        """The pose the library interpolates at times ``t`` (s; scalar or (n,)): (R (n, 3, 3), pos
+        (n, 3)), quaternion SLERP + position LERP of the uploaded trajectory, clamped to the table
+        (mc_pose_at).  With ``p'`` from ``deskew(reference=...)``: p_global = R_ref p' + pos_ref."""
+        tq = np.ascontiguousarray(np.atleast_1d(t), dtype=np.float64)
+        if tq.ndim != 1:
+            raise ValueError("pose_at: a scalar or a 1-D array of times expected")
+        R = np.empty((len(tq), 3, 3), np.float64)
+        pos = np.empty((len(tq), 3), np.float64)
+        check(self.lib.mc_pose_at(self.handle, len(tq), ptr(tq, c_double), ptr(R, c_double), ptr(pos, c_double)),
+              "pose_at")
+        return R, pos
 
     def deskew_steps(self, inp: "Batch", out: "Batch", n_steps: int, mode: str = "frame",
                      pose_select: str = "searchsorted", sample_every: int = 0) -> "Batch":
@@ -395,9 +443,18 @@ class Batch:
         check(self.lib.mc_batch_info(h, ctypes.byref(n), ctypes.byref(p), ctypes.byref(f), ctypes.byref(t)))
         self.n_points, self.padded_points, self.n_frames, self.n_tiles = n.value, p.value, f.value, t.value
         self.offsets = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+        self.frame_times = None
 
     def close(self):
         self._fin()
+
+    def time_spans(self):
+        """Per-frame (min, max) of t_ns over the frame's points, two int32 arrays (mc_batch_time_spans);
+        an empty frame has min > max."""
+        lo = np.zeros(self.n_frames, np.int32)
+        hi = np.zeros(self.n_frames, np.int32)
+        check(self.lib.mc_batch_time_spans(self.handle, ptr(lo, c_int32), ptr(hi, c_int32)), "time_spans")
+        return lo, hi
 
     def pcd_len_current(self) -> bool:
         """True when the per-block PCD text sums describe the current columns."""
@@ -415,6 +472,7 @@ class Batch:
         if len(t) != self.n_frames:
             raise ValueError("one frame time per frame expected")
         check(self.lib.mc_batch_set_frame_times(self.handle, ptr(t, c_double)), "set_frame_times")
+        self.frame_times = t.copy()    # host copy (Context.deskew(reference="end"))
 
     def set_frame_starts(self, start_ns):
         s = np.ascontiguousarray(np.atleast_1d(start_ns), dtype=np.int64)
@@ -506,12 +564,16 @@ class Batch:
         return [aos[self.offsets[f]:self.offsets[f + 1]] for f in range(self.n_frames)]
 
 
-def deskew_points_f64(ctx: Context, mode: str, counts, points, t_ns, frame_times=None, frame_start_ns=None) -> np.ndarray:
+def deskew_points_f64(ctx: Context, mode: str, counts, points, t_ns, frame_times=None, frame_start_ns=None,
+                      t_ref=None) -> np.ndarray:
     """The per-point modes on host float64 rows (mc_deskew_points_f64): frames back to back
     (``counts``), ``points`` (N, >=3) float64, ``t_ns`` (N,) int64 ns since each point's frame start,
     ``frame_times`` (SLERP, s) or ``frame_start_ns`` (IMU) per frame.  Returns (N, 4) float64:
     x', y', z' in float64, column 3 = points[:, 3] (0 for 3-column input).  The pose / IMU table is
-    the one uploaded to ``ctx``."""
+    the one uploaded to ``ctx``.  ``t_ref`` (SLERP only; one absolute time (s) per frame): into the
+    sensor frame at that time instead, R_ref^T (p' - pos_ref) (mc_deskew_points_relative_f64)."""
+    if t_ref is not None and mode != "pose_slerp":
+        raise ValueError(f"t_ref= needs mode='pose_slerp' (got mode={mode!r})")
     c = np.ascontiguousarray(np.atleast_1d(counts), dtype=np.int64)
     p = np.asarray(points)
     if p.ndim != 2:
@@ -523,10 +585,16 @@ def deskew_points_f64(ctx: Context, mode: str, counts, points, t_ns, frame_times
         raise ValueError(f"counts add up to {n} points; got {p.shape[0]} rows and {t.shape[0]} timestamps")
     ft = None if frame_times is None else np.ascontiguousarray(frame_times, dtype=np.float64)
     fs = None if frame_start_ns is None else np.ascontiguousarray(frame_start_ns, dtype=np.int64)
-    for v, what in ((ft, "frame_times"), (fs, "frame_start_ns")):
+    tr = None if t_ref is None else np.ascontiguousarray(t_ref, dtype=np.float64)
+    for v, what in ((ft, "frame_times"), (fs, "frame_start_ns"), (tr, "t_ref")):
         if v is not None and v.shape != (len(c),):
             raise ValueError(f"{what}: one value per frame expected ({len(c)}), got {v.shape}")
     out = np.empty((n, 4), np.float64)
+    if tr is not None:
+        check(ctx.lib.mc_deskew_points_relative_f64(ctx.handle, len(c), ptr(c, c_int64), ptr(p, c_double), p.shape[1],
+                                                    ptr(t, c_int64), ptr(ft, c_double), ptr(tr, c_double),
+                                                    ptr(out, c_double)), "deskew_points_relative_f64")
+        return out
     check(ctx.lib.mc_deskew_points_f64(ctx.handle, _lib.MODES[mode], len(c), ptr(c, c_int64), ptr(p, c_double),
                                        p.shape[1], ptr(t, c_int64), ptr(ft, c_double),
                                        ptr(fs, c_int64), ptr(out, c_double)), f"deskew_points_f64[{mode}]")

@@ -156,12 +156,17 @@ class LiDARMotionSimulator:
         return self._align_host(scans, times, _lib.MC_POSE_SEARCHSORTED)
 
     def deskew_frames(self, frames: List[np.ndarray], t_ns: List[np.ndarray], trajectory: dict,
-                      times: Optional[np.ndarray] = None) -> List[np.ndarray]:
+                      times: Optional[np.ndarray] = None, reference=None) -> List[np.ndarray]:
         """Per-point motion compensation into the global frame: every return at time
         t_frame + t_ns*1e-9 gets the SLERP/LERP-interpolated pose of the trajectory
         (position_gps, orientation_imu), p' = R(q(t)) p + pos(t).  Computed in float64 on the given
         float64 rows, one launch for all frames (mc_deskew_points_f64); device-resident frames take
-        ``Context.deskew(mode="pose_slerp")`` instead."""
+        ``Context.deskew(mode="pose_slerp")`` instead.
+
+        ``reference``: into the sensor frame at a reference time per frame instead,
+        R_ref^T (p' - pos_ref) with the interpolated pose at that time — ``"start"`` (the frame's
+        time), ``"end"`` (the time of its last return; the frame's time for an empty frame), one
+        absolute time per frame, or one float for all (mc_deskew_points_relative_f64)."""
         if times is None:
             times = self.lidar_times()[: len(frames)]
         times = np.asarray(times, dtype=np.float64)
@@ -172,12 +177,27 @@ class LiDARMotionSimulator:
         for f, t in zip(frames, t_ns):
             if np.shape(t) != (f.shape[0],):
                 raise ValueError("one timestamp per point expected")
+        t_ref = None
+        if isinstance(reference, str):
+            if reference not in ("start", "end"):
+                raise ValueError(f"reference: 'start', 'end', a time or one time per frame expected (got {reference!r})")
+            t_ref = times.copy()
+            if reference == "end":
+                for f, t in enumerate(t_ns):
+                    if len(t):
+                        t_ref[f] = times[f] + float(np.max(np.asarray(t, np.int64))) * 1e-9
+        elif reference is not None:
+            t_ref = np.asarray(reference, dtype=np.float64)
+            t_ref = np.full(len(frames), float(t_ref)) if t_ref.ndim == 0 else t_ref
+            if t_ref.shape != (len(frames),):
+                raise ValueError(f"reference: one time per frame expected ({len(frames)}), got {t_ref.shape}")
         if not frames or counts.sum() == 0:
             return [np.zeros((0, 4)) for _ in frames]
         ctx = self.context
         ctx.set_trajectory(trajectory["time"], trajectory["position_gps"], trajectory["orientation_imu"])
         out = deskew_points_f64(ctx, "pose_slerp", counts, _stack_aos(frames),
-                                np.concatenate([np.asarray(t, np.int64) for t in t_ns]), frame_times=times)
+                                np.concatenate([np.asarray(t, np.int64) for t in t_ns]), frame_times=times,
+                                t_ref=t_ref)
         offs = np.concatenate([[0], np.cumsum(counts)])
         return [out[offs[f]:offs[f + 1]] for f in range(len(frames))]
 
