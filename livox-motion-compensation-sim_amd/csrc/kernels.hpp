@@ -9,6 +9,8 @@
 //                       LERP of the pose table at each point's time, fused rotate-then-translate.
 //   k_deskew_points<2>  Path B, CSIM:1435-1536: gyro LERP at the point timestamp,
 //                       theta = w*dt, p' = Rx(-tx) Ry(-ty) Rz(-tz) p.
+//   k_deskew_points<1, false, false, RelArgs>  the SLERP mode into the sensor frame at a reference
+//                       time: the same kernel over the per-frame relative table (relative.hpp).
 //   k_trange / k_synth / k_checksum / layout converters: staging, not the per-step path.
 //
 // Work decomposition: the batch is a "padded CSR" of frames (every frame starts at a multiple of
@@ -24,6 +26,7 @@
 #include <type_traits>
 
 #include "layout.hpp"
+#include "relfold.hpp"
 
 namespace mc {
 
@@ -226,6 +229,12 @@ __device__ __forceinline__ int64_t upper_bound(const T* a, int64_t n, T x) {
     if (a[mid] <= x) lo = mid + 1; else hi = mid;
   }
   return lo;
+}
+
+// segment of the pose table at time t as the oracle selects it: searchsorted 'right' - 1, clamped
+__device__ __forceinline__ int64_t pose_segment_of(const double* time, int64_t T, int64_t nseg, double t) {
+  const int64_t k = upper_bound(time, T, t) - 1;
+  return k > nseg - 1 ? nseg - 1 : (k < 0 ? 0 : k);
 }
 
 // numpy searchsorted(a, x, 'left'): first index with a[i] >= x  (LMC:804)
@@ -1415,9 +1424,25 @@ __device__ __forceinline__ void fast_path(const WinOf<MODE>* rec, const FrameWin
 // (NEXT: at least 4 waves / SIMD like the plain kernel — the prep body alone would take 172 VGPRs)
 // PCD (mc_deskew_pcd): a wave's 64 groups are one 256-point block of the output batch; it also
 // writes that block's ASCII PCD text bytes (a wave reduction, no barrier).
-template <int MODE, bool NEXT = false, bool PCD = false>
+// REL = RelArgs (mc_deskew_relative, SLERP only): the same kernel with every record read from the
+// per-frame relative table (relative.hpp).  A frame's window [klo_f, khi_f] starts at rel + roff[f]; a
+// window fw (the frame's own, or a sub-tile's) inside it starts fw.klo - klo_f records further on.  The
+// records are folded into the frame's reference pose and already carry the frame time, so the SGPR
+// path loads them as they are, the LDS path copies them, and the per-point search path indexes them
+// by segment - klo_f.  A trailing pack, not a DeskewArgs field or a fixed parameter: the other
+// instantiations keep their kernarg layout and their instruction text.
+struct RelArgs {
+  const PoseWin* rel;     // per-frame folded records of [klo_f, khi_f], frame-specialised (tf set)
+  const int64_t* roff;    // F + 1 offsets into rel
+};
+
+template <int MODE, bool NEXT = false, bool PCD = false, typename... REL>
 __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const DeskewArgs a, const PrepArgs pn,
-                                                                         const uint32_t pre) {
+                                                                         const uint32_t pre, const REL... rel) {
+  constexpr bool kRel = sizeof...(REL) != 0;
+  static_assert(sizeof...(REL) <= 1 && (std::is_same_v<REL, RelArgs> && ...), "REL is empty or RelArgs");
+  static_assert(!kRel || (MODE == 1 && !NEXT && !PCD), "the relative variant is SLERP only, without NEXT and PCD");
+  const RelArgs ra{rel...};   // (null when not relative, and never read)
   span_start(a.span);
   if constexpr (NEXT) {
     if (blockIdx.x < pre) {
@@ -1462,11 +1487,27 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
     // point loads)
     bool sub = true;
     if constexpr (MODE != 2) sub = ldu(a.fwin + f).W > kFastMaxW;
-    const FrameWin fw = MODE == 2 ? fw_first : ldu(sub ? a.swin + st : a.fwin + f);
+    const FrameWin* pw = sub ? a.swin + st : a.fwin + f;
+    // relative: klo_f below is a second read of a.fwin[f]; the compiler then reuses it for half of fw,
+    // branches around the other half and loads bnd1 on its own inside the SGPR path (54 scalar loads,
+    // 0.5 % slower than with 53).  An opaque pointer keeps the one load of the chosen record.
+    if constexpr (kRel) asm volatile("" : "+s"(pw));
+    const FrameWin fw = MODE == 2 ? fw_first : ldu(pw);
     // sub-tile windows point into the step's segment table (SLERP: whose records carry no frame time)
     const Win* rec = sub ? (MODE == 1 ? reinterpret_cast<const Win*>(a.pose_seg) : reinterpret_cast<const Win*>(a.imu_seg)) + fw.klo
                          : frec + 2 * f;
-    const bool set_tf = MODE == 1 && sub;
+    bool set_tf = MODE == 1 && sub;
+    const Win* frel = nullptr;   // relative: the frame's records, segment klo_f first
+    int64_t wmax = 0;            //           khi_f - klo_f
+    int32_t klo_f = 0;           //           its first segment (the frame window's klo)
+    if constexpr (kRel) {
+      klo_f = ldu(&a.fwin[f].klo);
+      const int64_t r0 = ldu(ra.roff + f), r1 = ldu(ra.roff + f + 1);
+      frel = ra.rel + r0;
+      wmax = r1 - r0 - 1;
+      rec = frel + (fw.klo - klo_f);   // the window's
+      set_tf = false;                   // the folded records carry the frame time
+    }
 
     if (fw.W <= kFastMaxW) {
       // the tier k_prep chose for the window: its coefficient load is issued here, beside the point
@@ -1484,7 +1525,8 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
         const int64_t k = fw.klo + tid;
         if constexpr (MODE == 1) {
           const double tf = a.frame_time[f];
-          s_win[tid] = make_pose_win(a.pose_seg[k], tf);
+          if constexpr (kRel) s_win[tid] = rec[tid];
+          else s_win[tid] = make_pose_win(a.pose_seg[k], tf);
           s_bnd[tid] = rel_ns_ceil(a.pose_time[k], tf);
         } else {
           ImuSeg sg = a.imu_seg[k];
@@ -1507,12 +1549,20 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
         const double tf = a.frame_time[f];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          int64_t k = upper_bound(a.pose_time, a.ntab, slerp_time(tf, (double)i4c(Tq, c))) - 1;
-          k = k > a.nseg - 1 ? a.nseg - 1 : (k < 0 ? 0 : k);
+          int64_t k = pose_segment_of(a.pose_time, a.ntab, a.nseg, slerp_time(tf, (double)i4c(Tq, c)));
+          if constexpr (kRel) {
+            // the record of segment k is at k - klo_f, clamped into the frame's window: a padding
+            // slot's t_ns = 0 may lie outside the valid points' span
+            k -= klo_f;
+            k = k > wmax ? wmax : (k < 0 ? 0 : k);
+          }
           seg[c] = act ? (int)k : -1;
         }
-        points_peeled<MODE>(seg, [&](int j) { return make_pose_win(ldu(a.pose_seg + j), tf); },
-                            poly_load<kTierAny<MODE>>(), Tq, X, Y, Z);
+        if constexpr (kRel)
+          points_peeled<MODE>(seg, [&](int j) { return ldu(frel + j); }, poly_load<kTierAny<MODE>>(), Tq, X, Y, Z);
+        else
+          points_peeled<MODE>(seg, [&](int j) { return make_pose_win(ldu(a.pose_seg + j), tf); },
+                              poly_load<kTierAny<MODE>>(), Tq, X, Y, Z);
       } else {
         const int64_t fs = a.frame_start[f];
 #pragma unroll
@@ -1610,30 +1660,44 @@ struct PointsF64Args {
   double* out;                                // (n, 4): x', y', z', column 3 (0 when ld == 3)
 };
 
-template <int MODE>
-__global__ __launch_bounds__(kBlock) void k_points_f64(const PointsF64Args a) {
+// REF = RefPoses (mc_deskew_points_relative_f64, SLERP only): the global float64 value, then minus
+// pos_ref, then R_ref^T — the direct formula, no folded record anywhere: an independent device-side
+// check of the folded batch path.
+struct RefPoses {
+  const double* q;     // (F, 4) reference quaternion (x, y, z, w)
+  const double* pos;   // (F, 3) reference position
+};
+
+template <int MODE, typename... REF>
+__global__ __launch_bounds__(kBlock) void k_points_f64(const PointsF64Args a, const REF... ref) {
+  constexpr bool kRel = sizeof...(REF) != 0;
+  static_assert(sizeof...(REF) <= 1 && (std::is_same_v<REF, RefPoses> && ...), "REF is empty or RefPoses");
+  static_assert(!kRel || MODE == 1, "the relative variant is SLERP only");
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * kBlock) {
-    int32_t lo = 0, hi = a.F;                    // last f with doff[f] <= i
-    while (hi - lo > 1) {
-      const int32_t mid = (lo + hi) >> 1;
-      if (a.doff[mid] <= i) lo = mid; else hi = mid;
-    }
+    const int32_t f = row_frame(a.doff, a.F, i);
     const double* q = a.pts + i * a.ld;
     double x = q[0], y = q[1], z = q[2];
     const double w = a.ld > 3 ? q[3] : 0.0;
     const int64_t t = a.t_ns[i];
     if constexpr (MODE == 1) {
-      const double tf = a.ftime[lo];
-      const double tq = slerp_time(tf, (double)t);
-      int64_t k = upper_bound(a.pose_time, a.ntab, tq) - 1;
-      k = k > a.nseg - 1 ? a.nseg - 1 : (k < 0 ? 0 : k);
-      slerp_core(a.pose_seg[k], kPoly10, tq, x, y, z);
+      const double tq = slerp_time(a.ftime[f], (double)t);
+      slerp_core(a.pose_seg[pose_segment_of(a.pose_time, a.ntab, a.nseg, tq)], kPoly10, tq, x, y, z);
     } else {
-      const int64_t ta = a.fstart[lo] + t;       // the point's absolute timestamp (CSIM:1447)
+      const int64_t ta = a.fstart[f] + t;        // the point's absolute timestamp (CSIM:1447)
       int64_t k = upper_bound(a.imu_ts, a.ntab, ta) - 1;
       k = k < 0 ? 0 : k;                         // before the first sample: the first (CSIM:1496)
       const ImuSeg sg = a.imu_seg[k];
       imu_core(sg, NoPoly{}, (double)(ta - sg.ts), (double)t, x, y, z);
+    }
+    if constexpr (kRel) {
+      const RefPoses r{ref...};
+      const double* rq = r.q + 4 * (int64_t)f;
+      const double* rp = r.pos + 3 * (int64_t)f;
+      const double qr[4] = {rq[0], rq[1], rq[2], rq[3]};
+      const double d[3] = {x - rp[0], y - rp[1], z - rp[2]};
+      double o3[3];
+      quat_rot_inv(qr, d, o3);
+      x = o3[0]; y = o3[1]; z = o3[2];
     }
     double* o = a.out + 4 * i;
     o[0] = x; o[1] = y; o[2] = z; o[3] = w;

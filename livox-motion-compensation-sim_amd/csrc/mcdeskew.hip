@@ -1043,6 +1043,23 @@ int mc_deskew_steps(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int 
 
 // ---- the relative (sensor-frame) SLERP deskew: relative.hpp ---------------------------------------
 namespace {
+// k_pose_at's arguments for times t[0..n) over the segment table seg (nseg records) of the uploaded
+// trajectory; the caller names the outputs it wants
+PoseAtArgs pose_at_args(const mc_ctx* c, const PoseSeg* seg, int64_t nseg, const double* t, int64_t n) {
+  PoseAtArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.t = t; a.n = n;
+  a.pose_time = c->d_time; a.pose_seg = seg; a.nseg = nseg; a.ntab = c->T;
+  return a;
+}
+
+// reference times (null: each frame's own time) must be finite
+int check_t_ref(const double* t_ref, int32_t F) {
+  if (t_ref)
+    for (int32_t f = 0; f < F; ++f) CHECK_ARG(std::isfinite(t_ref[f]), "t_ref[%d] is not finite", f);
+  return MC_OK;
+}
+
 // The batch's relative table for reference times t_ref (null: each frame's own time), built after the
 // step's k_prep (sp: its plan) on the main stream.  Cached with the batch: nothing is launched when
 // the table already holds these references over these tables; the offsets (a count pass and one
@@ -1103,10 +1120,7 @@ int rel_table(mc_ctx* c, mc_batch* b, const StepPlan& sp, const double* t_ref) {
   }
   {
     TimedRegion tr(c, &c->prep_ev, s);
-    PoseAtArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    pa.t = d_t; pa.n = F;
-    pa.pose_time = c->d_time; pa.pose_seg = sp.da.pose_seg; pa.nseg = sp.pa.nseg; pa.ntab = c->T;
+    PoseAtArgs pa = pose_at_args(c, sp.da.pose_seg, sp.pa.nseg, d_t, F);
     pa.q = b->d_refpose; pa.pos = b->d_refpose + 4 * (size_t)F;
     hipLaunchKernelGGL(k_pose_at, dim3((F + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pa);
     ra.roff = b->d_roff; ra.pose_seg = sp.da.pose_seg;
@@ -1124,9 +1138,7 @@ int rel_table(mc_ctx* c, mc_batch* b, const StepPlan& sp, const double* t_ref) {
 
 int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const double* t_ref) {
   if (int r = deskew_check(c, in, out, MC_MODE_POSE_SLERP, MC_POSE_SEARCHSORTED)) return r;
-  if (t_ref)
-    for (int32_t f = 0; f < in->F; ++f)
-      CHECK_ARG(std::isfinite(t_ref[f]), "t_ref[%d] is not finite", f);
+  if (int r = check_t_ref(t_ref, in->F)) return r;
   if (in->F == 0) return MC_OK;
   DeviceGuard g(c->device);
   hipStream_t s = c->stream;
@@ -1151,7 +1163,7 @@ int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const doubl
   {
     LaunchEvents ev(c);
     if (ev.e0) sp.da.span = span_take(c);
-    launch<k_deskew_points_rel>(false, sp.grid, s, ev.e0, ev.e1, 0u, sp.da, rl);
+    launch<k_deskew_points<1, false, false, RelArgs>>(false, sp.grid, s, ev.e0, ev.e1, 0u, sp.da, sp.pa, 0u, rl);
     ev.keep(&c->main_ev);
   }
   HIPCHK(hipGetLastError());
@@ -1279,8 +1291,12 @@ static int seg64_table(mc_ctx* c, int mode, int64_t* nseg_out) {
   return MC_OK;
 }
 
-int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, const double* points, int64_t ld,
-                         const int64_t* t_ns, const double* frame_times, const int64_t* frame_start_ns, double* out) {
+// The float64 row paths of the per-point modes.  relative (SLERP only): into each frame's sensor frame
+// at t_ref[f] (null: the frame's own time) — the reference poses by k_pose_at, then the relative
+// variant of the row kernel.
+static int points_f64(mc_ctx* c, int mode, bool relative, int32_t F, const int64_t* counts, const double* points,
+                      int64_t ld, const int64_t* t_ns, const double* frame_times, const int64_t* frame_start_ns,
+                      const double* t_ref, double* out) {
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(mode == MC_MODE_POSE_SLERP || mode == MC_MODE_IMU, "mode %d: MC_MODE_POSE_SLERP or MC_MODE_IMU expected",
             mode);
@@ -1296,6 +1312,7 @@ int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, 
     if (c->M < 1) return fail(MC_ERR_STATE, "no IMU samples uploaded (mc_set_imu)");
     CHECK_ARG(F == 0 || frame_start_ns, "frame start times are NULL");
   }
+  if (int r = check_t_ref(t_ref, F)) return r;
   const int64_t n = doff[F];
   if (n == 0) return MC_OK;
   CHECK_ARG(points && t_ns && out, "NULL points / t_ns / out");
@@ -1304,14 +1321,18 @@ int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, 
   hipStream_t s = c->stream;
   int64_t nseg = 0;
   if (int r = seg64_table(c, mode, &nseg)) return r;
-  // scratch: [doff (F+1) | per-frame value (F) | t_ns (n) | points (n, ld) | out (n, 4)]
-  const size_t w_doff = 0, w_fv = (size_t)F + 1, w_t = w_fv + (size_t)F, w_pts = w_t + (size_t)n,
-               w_out = w_pts + (size_t)n * (size_t)ld, words = w_out + 4 * (size_t)n;
+  // scratch: [doff (F+1) | per-frame value (F) | relative: t_ref (F), ref q (4 F), ref pos (3 F) |
+  //           t_ns (n) | points (n, ld) | out (n, 4)]
+  const size_t nF = (size_t)F, w_doff = 0, w_fv = nF + 1, w_tr = w_fv + nF, w_q = w_tr + nF, w_rp = w_q + 4 * nF,
+               w_t = relative ? w_rp + 3 * nF : w_tr, w_pts = w_t + (size_t)n, w_out = w_pts + (size_t)n * (size_t)ld,
+               words = w_out + 4 * (size_t)n;
   RowScratch sc;
   if (int r = sc.open(c, n, words)) return r;
   if (int r = sc.put(w_doff, doff.data(), doff.size())) return r;
   if (int r = sc.put(w_fv, mode == MC_MODE_POSE_SLERP ? static_cast<const void*>(frame_times)
-                                                      : static_cast<const void*>(frame_start_ns), (size_t)F)) return r;
+                                                      : static_cast<const void*>(frame_start_ns), nF)) return r;
+  if (relative)
+    if (int r = sc.put(w_tr, t_ref ? t_ref : frame_times, nF)) return r;
   if (int r = sc.put(w_t, t_ns, (size_t)n)) return r;
   if (int r = sc.put(w_pts, points, (size_t)n * (size_t)ld)) return r;
   PointsF64Args a;
@@ -1327,11 +1348,30 @@ int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, 
   a.out = sc.at<double>(w_out);
   {
     TimedRegion tr(c, &c->main_ev, s);
-    if (mode == MC_MODE_POSE_SLERP) hipLaunchKernelGGL(k_points_f64<1>, dim3(sc.grid(n)), dim3(kBlock), 0, s, a);
-    else hipLaunchKernelGGL(k_points_f64<2>, dim3(sc.grid(n)), dim3(kBlock), 0, s, a);
+    const dim3 grid(sc.grid(n)), block(kBlock);
+    if (relative) {
+      PoseAtArgs pa = pose_at_args(c, a.pose_seg, nseg, sc.at<const double>(w_tr), F);
+      pa.q = sc.at<double>(w_q); pa.pos = sc.at<double>(w_rp);
+      hipLaunchKernelGGL(k_pose_at, dim3((F + kBlock - 1) / kBlock), block, 0, s, pa);
+      hipLaunchKernelGGL((k_points_f64<1, RefPoses>), grid, block, 0, s, a, RefPoses{pa.q, pa.pos});
+    } else if (mode == MC_MODE_POSE_SLERP) {
+      hipLaunchKernelGGL(k_points_f64<1>, grid, block, 0, s, a);
+    } else {
+      hipLaunchKernelGGL(k_points_f64<2>, grid, block, 0, s, a);
+    }
   }
   HIPCHK(hipGetLastError());
   return sc.fetch(out, w_out, 4 * (size_t)n);
+}
+
+int mc_deskew_points_f64(mc_ctx* c, int mode, int32_t F, const int64_t* counts, const double* points, int64_t ld,
+                         const int64_t* t_ns, const double* frame_times, const int64_t* frame_start_ns, double* out) {
+  return points_f64(c, mode, false, F, counts, points, ld, t_ns, frame_times, frame_start_ns, nullptr, out);
+}
+
+int mc_deskew_points_relative_f64(mc_ctx* c, int32_t F, const int64_t* counts, const double* points, int64_t ld,
+                                  const int64_t* t_ns, const double* frame_times, const double* t_ref, double* out) {
+  return points_f64(c, MC_MODE_POSE_SLERP, true, F, counts, points, ld, t_ns, frame_times, nullptr, t_ref, out);
 }
 
 int mc_pose_at(mc_ctx* c, int64_t n, const double* t, double* R, double* pos) {
@@ -1350,70 +1390,12 @@ int mc_pose_at(mc_ctx* c, int64_t n, const double* t, double* R, double* pos) {
   RowScratch sc;
   if (int r = sc.open(c, n, words)) return r;
   if (int r = sc.put(0, t, (size_t)n)) return r;
-  PoseAtArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.t = sc.at<const double>(0); a.n = n;
-  a.pose_time = c->d_time; a.pose_seg = static_cast<const PoseSeg*>(c->d_seg64); a.nseg = nseg; a.ntab = c->T;
+  PoseAtArgs a = pose_at_args(c, static_cast<const PoseSeg*>(c->d_seg64), nseg, sc.at<const double>(0), n);
   a.R = sc.at<double>(w_R); a.pos = sc.at<double>(w_pos);
   hipLaunchKernelGGL(k_pose_at, dim3(sc.grid(n)), dim3(kBlock), 0, c->stream, a);
   HIPCHK(hipGetLastError());
   if (int r = sc.fetch(R, w_R, 9 * (size_t)n)) return r;
   return sc.fetch(pos, w_pos, 3 * (size_t)n);
-}
-
-int mc_deskew_points_relative_f64(mc_ctx* c, int32_t F, const int64_t* counts, const double* points, int64_t ld,
-                                  const int64_t* t_ns, const double* frame_times, const double* t_ref, double* out) {
-  CHECK_ARG(c, "ctx is NULL");
-  CHECK_ARG(F >= 0, "n_frames must be >= 0");
-  CHECK_ARG(F == 0 || counts, "counts is NULL");
-  if (ld < 3) return fail(MC_ERR_INDEX, "points need at least 3 columns (x, y, z); got %lld", (long long)ld);
-  std::vector<int64_t> doff;
-  if (int r = frame_offsets(counts, F, &doff)) return r;
-  if (c->T < 1) return fail(MC_ERR_STATE, "no trajectory uploaded (mc_set_trajectory)");
-  CHECK_ARG(F == 0 || frame_times, "frame times are NULL");
-  if (t_ref)
-    for (int32_t f = 0; f < F; ++f) CHECK_ARG(std::isfinite(t_ref[f]), "t_ref[%d] is not finite", f);
-  const int64_t n = doff[F];
-  if (n == 0) return MC_OK;
-  CHECK_ARG(points && t_ns && out, "NULL points / t_ns / out");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  hipStream_t s = c->stream;
-  int64_t nseg = 0;
-  if (int r = seg64_table(c, MC_MODE_POSE_SLERP, &nseg)) return r;
-  // scratch: [doff (F+1) | frame times (F) | t_ref (F) | ref q (4 F) | ref pos (3 F) | t_ns (n) |
-  //           points (n, ld) | out (n, 4)]
-  const size_t w_ft = (size_t)F + 1, w_tr = w_ft + (size_t)F, w_q = w_tr + (size_t)F, w_rp = w_q + 4 * (size_t)F,
-               w_t = w_rp + 3 * (size_t)F, w_pts = w_t + (size_t)n, w_out = w_pts + (size_t)n * (size_t)ld,
-               words = w_out + 4 * (size_t)n;
-  RowScratch sc;
-  if (int r = sc.open(c, n, words)) return r;
-  if (int r = sc.put(0, doff.data(), doff.size())) return r;
-  if (int r = sc.put(w_ft, frame_times, (size_t)F)) return r;
-  if (int r = sc.put(w_tr, t_ref ? t_ref : frame_times, (size_t)F)) return r;
-  if (int r = sc.put(w_t, t_ns, (size_t)n)) return r;
-  if (int r = sc.put(w_pts, points, (size_t)n * (size_t)ld)) return r;
-  PoseAtArgs pa;
-  std::memset(&pa, 0, sizeof(pa));
-  pa.t = sc.at<const double>(w_tr); pa.n = F;
-  pa.pose_time = c->d_time; pa.pose_seg = static_cast<const PoseSeg*>(c->d_seg64); pa.nseg = nseg; pa.ntab = c->T;
-  pa.q = sc.at<double>(w_q); pa.pos = sc.at<double>(w_rp);
-  PointsRelF64Args a;
-  std::memset(&a, 0, sizeof(a));
-  a.p.pts = sc.at<const double>(w_pts); a.p.ld = ld; a.p.n = n;
-  a.p.t_ns = sc.at<const int64_t>(w_t);
-  a.p.doff = sc.at<const int64_t>(0); a.p.F = F;
-  a.p.ftime = sc.at<const double>(w_ft);
-  a.p.pose_time = c->d_time; a.p.pose_seg = pa.pose_seg; a.p.nseg = nseg; a.p.ntab = c->T;
-  a.p.out = sc.at<double>(w_out);
-  a.ref_q = pa.q; a.ref_pos = pa.pos;
-  {
-    TimedRegion tr(c, &c->main_ev, s);
-    hipLaunchKernelGGL(k_pose_at, dim3((F + kBlock - 1) / kBlock), dim3(kBlock), 0, s, pa);
-    hipLaunchKernelGGL(k_points_rel_f64, dim3(sc.grid(n)), dim3(kBlock), 0, s, a);
-  }
-  HIPCHK(hipGetLastError());
-  return sc.fetch(out, w_out, 4 * (size_t)n);
 }
 
 // ---- host arrays <-> device: the row pipeline ------------------------------------------------

@@ -1,5 +1,5 @@
 // relfold.hpp — the algebra of the relative (sensor-frame) SLERP deskew, on plain double arrays so
-// the same text compiles for the device (relative.hpp) and for the host (tests/test_relative_cpu.py
+// the same text compiles for the device (kernels.hpp, relative.hpp) and for the host (tests/test_relative_cpu.py
 // builds it with g++ -ffp-contract=off).  No HIP include.
 //
 // The SLERP record is linear in what the deskew kernel evaluates,

@@ -1,5 +1,6 @@
-"""Time the relative (sensor-frame) SLERP deskew kernel (mc_deskew_relative, csrc/relative.hpp) against the
-global pose_slerp kernel it shares its per-point code with.  Stays out of bench.py.
+"""Time the relative (sensor-frame) SLERP deskew kernel (mc_deskew_relative: k_deskew_points<1, false, false,
+RelArgs> in csrc/kernels.hpp) against the global pose_slerp kernel, another instantiation of the same
+template.  Stays out of bench.py.
 
 Workload: BASELINE config 2's batch, 600 frames x 100 000 synthetic points (mc_batch_synth,
 MC_BATCH_WITH_TIME, frames at 10 Hz over a figure-eight trajectory).
