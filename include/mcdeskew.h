@@ -429,6 +429,52 @@ int mc_las_decode_batch(mc_ctx* ctx, const void* d_file, int64_t bytes, int poin
                         double intensity_scale, mc_batch* out, const int64_t* frame_start_ns,
                         int64_t* frame_start_out, int64_t* bad_row);
 
+/* ---- voxel-grid downsampling (build-added; csrc/voxel_core.hpp, voxel.hpp) ---------------------
+ * One output point per occupied voxel of a grid of size `voxel` anchored at `origin`: the mean of
+ * the voxel's points, with integer per-voxel sums, so the result is the same bit for bit on every
+ * run whatever order the device's atomics arrive in.  Per point and axis, every line ONE IEEE float64
+ * operation (no contraction):
+ *   a = double(v) - o     g = a / h     k = floor(g)     f = g - k        (f may round up to 1.0)
+ *   Q  = (int64) rint(f * 2^32),  0 <= Q <= 2^32;      QI = (int64) rint(double(intensity) * 2^16)
+ * A voxel is one (kx, ky, kz); its record is n, S[3] = sum Q, SI = sum QI (int64).  Per voxel:
+ *   m = double(S) / double(n)     w = double(k) + m * 2^-32     c = o + w * h
+ *   i = (double(SI) / double(n)) * 2^-16
+ * Voxels come out in order of first appearance (voxel A before B when A's lowest-index point is
+ * before B's; a batch's index order is frame-major, then the index within the frame; padding slots
+ * are not points).
+ * Accuracy, a property of the definition (checked on the CPU against exact rational means):
+ * |c - mean| <= h * 2^-32 plus the float64 rounding of the operations above (half an ulp each of a,
+ * g, w, w * h and c).  For h in 0.01 .. 0.5 and keys up to +-1 048 575 the worst seen at origin 0 is
+ * 1.1e-10 h; at an origin of 5e6 m half an ulp of c itself (4.7e-10 m) is the larger part.  The
+ * float32 batch output is within 1 float32 ulp of the correctly rounded mean; the intensity is within
+ * 2^-17 of the mean (reached).
+ * Refused: a coordinate or its g not finite, a k outside [-2^20, 2^20), an intensity not finite or
+ * with |intensity| > 65536.  One refused point fails the whole build with MC_ERR_INVALID naming the
+ * lowest one (*bad_frame / *bad_index, or *bad_row; -1 when none) and leaves nothing to emit.
+ * Count-then-emit, as mc_scan_count / mc_scan_emit: a build completes the sums and reports
+ * *n_voxels = M, so the emits need the source no more and may be called repeatedly.  An emit
+ * without a successful build: MC_ERR_STATE.  voxel <= 0 or not finite, origin not finite, ld < 4,
+ * 2^31 points or more: MC_ERR_INVALID.
+ * Device memory, the context's, kept (and reused while large enough) until mc_voxel_release, which
+ * must come before mc_destroy: 16 B per table slot (the power of two >= 2 N slots, so 32 .. 64 B per
+ * point), 8 B + 1/8 B per point, 36 B per voxel — 2.1 GB + 0.5 GB + up to 2.2 GB for 60 M points.  The
+ * emits allocate nothing. */
+int mc_voxel_build_batch(mc_ctx* ctx, const mc_batch* in, double voxel, const double* origin, int64_t* n_voxels,
+                         int32_t* bad_frame, int64_t* bad_index);
+/* d_rows: device (n, ld) float64 rows x, y, z, intensity, ... */
+int mc_voxel_build_f64(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t n, double voxel, const double* origin,
+                       int64_t* n_voxels, int64_t* bad_row);
+/* out: a batch of one frame of exactly M points (else MC_ERR_INVALID); receives float(c), float(i);
+ * a time column is left alone; MC_BATCH_WITH_PCD_LEN sums are marked stale. */
+int mc_voxel_emit_batch(mc_ctx* ctx, mc_batch* out);
+/* device outputs, any may be NULL: d_rows (M, 4) float64 cx, cy, cz, i (16-byte aligned); d_counts
+ * (M,) int32 points per voxel; d_keys (M, 3) int32 */
+int mc_voxel_emit_f64(mc_ctx* ctx, double* d_rows, int32_t* d_counts, int32_t* d_keys);
+/* event time (ms) of the timed phases since the last read: ms_phase[4] = insert (with the table
+ * reset), rank, accumulate, finalise; *launches = timed regions */
+int mc_timing_read_voxel(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+int mc_voxel_release(mc_ctx* ctx);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

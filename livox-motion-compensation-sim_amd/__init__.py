@@ -22,9 +22,11 @@ Drop-in surface (reference file:line in each docstring):
   las                    LAS 1.2 without laspy (lidar_motion_compensation.py:950-963,
                          livox_mid70_complete_simulator.py:1671-1698): encode_las / write_las from rows
                          or a Batch, read_las / read_las_batch back, records packed and unpacked on the device
+  voxel                  build-added: voxel_downsample(batch or rows, voxel, origin) -> VoxelCloud, the voxel-grid
+                         filter after a global deskew, with integer sums: bit-identical on every run
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
-from . import _lib, codecs, config, coords, csim_export, dist, ingest, las, raymarch, runtime, trajectory  # noqa: F401
+from . import _lib, codecs, config, coords, csim_export, dist, ingest, las, raymarch, runtime, trajectory, voxel  # noqa: F401
 from .csim_export import DataExporter, DeviceInfo  # noqa: F401
 from .ingest import read_lvx, read_lvx_batch, read_points, read_points_batch  # noqa: F401
 from .las import LasData, encode_las, read_las, read_las_batch, write_las  # noqa: F401
@@ -36,5 +38,6 @@ from .config import default_config, validate_config  # noqa: F401
 from .raymarch import LiDARSimulator  # noqa: F401
 from .runtime import Batch, Context, default_context  # noqa: F401
 from .simulator import LiDARMotionSimulator  # noqa: F401
+from .voxel import VoxelCloud, voxel_downsample  # noqa: F401
 
 __version__ = "0.1.0"

@@ -126,6 +126,13 @@ _SIGS = {
                               c_int64]),
     "mc_las_decode_batch": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int64, _pd, _pd, c_double,
                                     c_void_p, _pi64, _pi64, _pi64]),
+    # the voxel-grid filter (count-then-emit)
+    "mc_voxel_build_batch": (c_int, [c_void_p, c_void_p, c_double, _pd, _pi64, _pi32, _pi64]),
+    "mc_voxel_build_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, _pd, _pi64, _pi64]),
+    "mc_voxel_emit_batch": (c_int, [c_void_p, c_void_p]),
+    "mc_voxel_emit_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mc_timing_read_voxel": (c_int, [c_void_p, _pd, _pi64]),
+    "mc_voxel_release": (c_int, [c_void_p]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

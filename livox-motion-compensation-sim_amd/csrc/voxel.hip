@@ -1,0 +1,315 @@
+// voxel.hip — host side of the voxel-grid filter (include/mcdeskew.h mc_voxel_*; kernels in voxel.hpp).
+//
+// The filter's state (the key table, the per-point slots, the per-voxel sums and what the last build
+// left for its emits) belongs to a context but is kept here, in a table of this file keyed by the
+// context, not in mc_ctx: the deskew and codec translation units do not see it and compile to the
+// objects they were.  mc_voxel_release frees it; an entry whose context has gone (the handles
+// mc_create made for it — both streams and the span pool — no longer all match) is dropped at the
+// next look-up.  mc_ctx carries no serial number to compare instead.
+#include "../../include/mcdeskew.h"
+#include "voxel.hpp"
+#include "internal.hpp"
+#include "hostutil.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+#include <unordered_map>
+
+using namespace mc;
+
+namespace {
+
+enum { kInsert = 0, kRank = 1, kAccumulate = 2, kFinalise = 3, kPhases = 4 };
+
+struct VoxState {
+  // the owner's handles when the entry was made (mc_create's: main stream, row stream, span pool)
+  hipStream_t stream = nullptr, row_d2h = nullptr;
+  const void* span = nullptr;
+  bool owned_by(const mc_ctx* c) const { return stream == c->stream && row_d2h == c->row_d2h && span == c->d_span; }
+  int device = 0;
+  // table (cap slots), per-point arrays (n_cap points / chunks), per-voxel records (m_cap voxels)
+  unsigned long long* keys = nullptr;
+  uint32_t* first = nullptr;
+  uint32_t* vid = nullptr;
+  size_t cap_alloc = 0;
+  uint32_t* slot = nullptr;
+  uint32_t* vslot = nullptr;
+  uint8_t* flags = nullptr;
+  uint32_t* chunk = nullptr;
+  size_t n_alloc = 0;
+  long long* sums = nullptr;
+  uint32_t* cnt = nullptr;
+  size_t m_alloc = 0;
+  uint32_t* meta = nullptr;
+  // the last build
+  bool built = false;
+  int64_t M = 0;
+  double h = 0.0, o[3] = {0, 0, 0};
+  EventPairs ev[kPhases];
+
+  void free_buffers() {
+    dev_free(keys); dev_free(first); dev_free(vid); dev_free(slot); dev_free(vslot); dev_free(flags);
+    dev_free(chunk); dev_free(sums); dev_free(cnt); dev_free(meta);
+    cap_alloc = n_alloc = m_alloc = 0;
+    built = false;
+  }
+};
+
+std::mutex g_mu;
+std::unordered_map<mc_ctx*, VoxState> g_states;
+
+// the context's entry (made on demand); an entry left by a destroyed context at the same address
+// gives its buffers back first
+VoxState* state_of(mc_ctx* c, bool create) {
+  std::lock_guard<std::mutex> l(g_mu);
+  auto it = g_states.find(c);
+  if (it != g_states.end() && !it->second.owned_by(c)) {
+    DeviceGuard g(it->second.device);
+    it->second.free_buffers();
+    for (auto& v : it->second.ev)
+      for (auto& p : v) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    g_states.erase(it);
+    it = g_states.end();
+  }
+  if (it == g_states.end()) {
+    if (!create) return nullptr;
+    it = g_states.emplace(c, VoxState()).first;
+    it->second.stream = c->stream;
+    it->second.row_d2h = c->row_d2h;
+    it->second.span = c->d_span;
+    it->second.device = c->device;
+  }
+  return &it->second;
+}
+
+template <typename T>
+int grow(mc_ctx* c, T** p, size_t n) {
+  if (*p) { HIPCHK(hipStreamSynchronize(c->stream)); dev_free(*p); }
+  return dev_alloc(p, n);
+}
+
+int check_grid(double voxel, const double* origin) {
+  CHECK_ARG(std::isfinite(voxel) && voxel > 0.0, "voxel must be finite and > 0 (got %g)", voxel);
+  CHECK_ARG(origin, "origin is NULL");
+  for (int k = 0; k < 3; ++k) CHECK_ARG(std::isfinite(origin[k]), "origin must be finite (axis %d: %g)", k, origin[k]);
+  return MC_OK;
+}
+
+// the build over n points of src; *bad: the lowest refused point (-1: none)
+template <bool BATCH>
+int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, int64_t* bad) {
+  *bad = -1;
+  *n_voxels = 0;
+  VoxState* s = state_of(c, true);
+  s->built = false;
+  s->M = 0;
+  s->h = src.h;
+  std::copy_n(src.o, 3, s->o);
+  if (n == 0) { s->built = true; return MC_OK; }
+  int log2cap = 6;
+  while (((int64_t)1 << log2cap) < 2 * n) ++log2cap;   // n < 2^31: at most 2^32 slots
+  const size_t cap = (size_t)1 << log2cap;
+  const int64_t n_chunks = (n + kVoxChunk - 1) / kVoxChunk;
+  if (!s->meta) if (int r = dev_alloc(&s->meta, 2)) return r;
+  if (cap > s->cap_alloc) {
+    s->cap_alloc = 0;
+    if (int r = grow(c, &s->keys, cap)) return r;
+    if (int r = grow(c, &s->first, cap)) return r;
+    if (int r = grow(c, &s->vid, cap)) return r;
+    s->cap_alloc = cap;
+  }
+  if ((size_t)n > s->n_alloc) {
+    s->n_alloc = 0;
+    if (int r = grow(c, &s->slot, (size_t)n)) return r;
+    if (int r = grow(c, &s->vslot, (size_t)n)) return r;
+    if (int r = grow(c, &s->flags, (size_t)n_chunks * kVoxBlock)) return r;
+    if (int r = grow(c, &s->chunk, (size_t)n_chunks)) return r;
+    s->n_alloc = (size_t)n;
+  }
+  VoxTable t;
+  t.keys = s->keys; t.first = s->first; t.vid = s->vid; t.slot = s->slot;
+  t.shift = 64 - log2cap;
+  t.mask = (uint32_t)(cap - 1);
+  t.meta = s->meta;
+  const dim3 blk(kVoxBlock), pgrid((uint32_t)((lanes + kVoxBlock - 1) / kVoxBlock)), cgrid((uint32_t)n_chunks);
+  {
+    TimedRegion tr(c, &s->ev[kInsert], c->stream);
+    HIPCHK(hipMemsetAsync(s->keys, 0xFF, cap * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(s->first, 0xFF, cap * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(s->meta, 0xFF, 2 * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_vox_insert<BATCH>, pgrid, blk, 0, c->stream, src, t);
+  }
+  {
+    TimedRegion tr(c, &s->ev[kRank], c->stream);
+    hipLaunchKernelGGL(k_vox_flag, cgrid, blk, 0, c->stream, t, n, s->flags, s->chunk);
+    hipLaunchKernelGGL(k_vox_scan, dim3(1), blk, 0, c->stream, s->chunk, n_chunks, s->meta);
+    hipLaunchKernelGGL(k_vox_rank, cgrid, blk, 0, c->stream, t, n, (const uint8_t*)s->flags, (const uint32_t*)s->chunk,
+                       s->vslot);
+  }
+  HIPCHK(hipGetLastError());
+  uint32_t meta[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(meta, s->meta, sizeof meta, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (meta[0] != kVoxNone) {
+    *bad = (int64_t)meta[0];
+    return MC_ERR_INVALID;   // the caller words the message (frame / index or row)
+  }
+  const int64_t M = (int64_t)meta[1];
+  if (M < 1 || M > n) return fail(MC_ERR_STATE, "voxel build: %lld voxels of %lld points", (long long)M, (long long)n);
+  if ((size_t)M > s->m_alloc) {
+    s->m_alloc = 0;
+    if (int r = grow(c, &s->sums, kVoxRec * (size_t)M)) return r;
+    if (int r = grow(c, &s->cnt, (size_t)M)) return r;
+    s->m_alloc = (size_t)M;
+  }
+  {
+    TimedRegion tr(c, &s->ev[kAccumulate], c->stream);
+    HIPCHK(hipMemsetAsync(s->sums, 0, kVoxRec * (size_t)M * sizeof(long long), c->stream));
+    HIPCHK(hipMemsetAsync(s->cnt, 0, (size_t)M * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_vox_accumulate<BATCH>, pgrid, blk, 0, c->stream, src, t, s->sums, s->cnt);
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  s->M = M;
+  s->built = true;
+  *n_voxels = M;
+  return MC_OK;
+}
+
+const char* kRefused =
+    "a coordinate or (v - origin) / voxel is not finite, a voxel index is outside [-2^20, 2^20), or the intensity is "
+    "not finite or beyond +-65536";
+
+int emit(mc_ctx* c, VoxState* s, VoxOut a, bool batch, int64_t P) {
+  a.keys = s->keys; a.vslot = s->vslot; a.sums = s->sums; a.cnt = s->cnt;
+  a.M = s->M;
+  a.h = s->h;
+  std::copy_n(s->o, 3, a.o);
+  const int64_t lanes = batch ? P / 4 : s->M;
+  if (lanes == 0) return MC_OK;
+  const dim3 blk(kVoxBlock), grid((uint32_t)((lanes + kVoxBlock - 1) / kVoxBlock));
+  {
+    TimedRegion tr(c, &s->ev[kFinalise], c->stream);
+    if (batch) hipLaunchKernelGGL(k_vox_emit_batch, grid, blk, 0, c->stream, a, P);
+    else hipLaunchKernelGGL(k_vox_emit_rows, grid, blk, 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return MC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mc_voxel_build_batch(mc_ctx* c, const mc_batch* in, double voxel, const double* origin, int64_t* n_voxels,
+                         int32_t* bad_frame, int64_t* bad_index) {
+  if (bad_frame) *bad_frame = -1;
+  if (bad_index) *bad_index = -1;
+  CHECK_ARG(c && in && n_voxels, "NULL argument");
+  CHECK_ARG(in->ctx == c, "batch belongs to another context");
+  if (int r = check_grid(voxel, origin)) return r;
+  CHECK_ARG(in->N < ((int64_t)1 << 31), "%lld points: the voxel filter takes fewer than 2^31", (long long)in->N);
+  DeviceGuard g(c->device);
+  VoxSrc src = {};
+  src.cols = in->d_cols; src.C = in->C; src.F = in->F;
+  src.poff = in->d_poff; src.doff = in->d_doff; src.counts = in->d_counts;
+  src.P = in->P;
+  src.n = in->N;
+  src.h = voxel;
+  std::copy_n(origin, 3, src.o);
+  int64_t bad = -1;
+  const int r = build<true>(c, src, in->N, in->P / 4, n_voxels, &bad);
+  if (bad >= 0) {
+    // the frame holding dense point `bad`: the last one starting at or before it (empty frames start
+    // where the next begins and come earlier in the order)
+    const int32_t f = (int32_t)(std::upper_bound(in->doff.begin(), in->doff.begin() + in->F + 1, bad) - in->doff.begin()) - 1;
+    if (bad_frame) *bad_frame = f;
+    if (bad_index) *bad_index = bad - in->doff[f];
+    return fail(MC_ERR_INVALID, "frame %d, point %lld (the lowest refused): %s", f, (long long)(bad - in->doff[f]), kRefused);
+  }
+  return r;
+}
+
+int mc_voxel_build_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n, double voxel, const double* origin,
+                       int64_t* n_voxels, int64_t* bad_row) {
+  if (bad_row) *bad_row = -1;
+  CHECK_ARG(c && n_voxels, "NULL argument");
+  CHECK_ARG(ld >= 4, "voxel rows are x, y, z, intensity: ld >= 4; got %lld", (long long)ld);
+  CHECK_ARG(n >= 0 && n < ((int64_t)1 << 31), "%lld points: the voxel filter takes 0 to 2^31 - 1", (long long)n);
+  CHECK_ARG(n == 0 || d_rows, "d_rows is NULL");
+  if (int r = check_grid(voxel, origin)) return r;
+  DeviceGuard g(c->device);
+  VoxSrc src = {};
+  src.rows = d_rows; src.ld = ld; src.n = n;
+  src.h = voxel;
+  std::copy_n(origin, 3, src.o);
+  int64_t bad = -1;
+  const int r = build<false>(c, src, n, n, n_voxels, &bad);
+  if (bad >= 0) {
+    if (bad_row) *bad_row = bad;
+    return fail(MC_ERR_INVALID, "row %lld (the lowest refused): %s", (long long)bad, kRefused);
+  }
+  return r;
+}
+
+int mc_voxel_emit_batch(mc_ctx* c, mc_batch* out) {
+  CHECK_ARG(c && out, "NULL argument");
+  CHECK_ARG(out->ctx == c, "batch belongs to another context");
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_emit_batch needs a successful mc_voxel_build_* first");
+  CHECK_ARG(out->F == 1 && out->N == s->M, "the out batch must be one frame of exactly %lld points (it has %d frames, %lld points)",
+            (long long)s->M, out->F, (long long)out->N);
+  DeviceGuard g(c->device);
+  VoxOut a = {};
+  a.cols = out->d_cols;
+  a.C = out->C;
+  if (int r = emit(c, s, a, true, out->P)) return r;
+  return mcimpl::batch_columns_written(out);
+}
+
+int mc_voxel_emit_f64(mc_ctx* c, double* d_rows, int32_t* d_counts, int32_t* d_keys) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(((uintptr_t)d_rows & 15) == 0, "d_rows must be 16-byte aligned");
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_emit_f64 needs a successful mc_voxel_build_* first");
+  if (!d_rows && !d_counts && !d_keys) return MC_OK;
+  DeviceGuard g(c->device);
+  VoxOut a = {};
+  a.rows = d_rows;
+  a.counts = d_counts;
+  a.keys_out = d_keys;
+  return emit(c, s, a, false, 0);
+}
+
+int mc_timing_read_voxel(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  int64_t total = 0;
+  for (int k = 0; k < kPhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
+  if (VoxState* s = state_of(c, false)) {
+    for (int k = 0; k < kPhases; ++k) {
+      int64_t n = 0;
+      if (int r = sum_events(c, s->ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
+      total += n;
+    }
+  }
+  if (launches) *launches = total;
+  return MC_OK;
+}
+
+int mc_voxel_release(mc_ctx* c) {
+  if (!c) return MC_OK;
+  VoxState* s = state_of(c, false);
+  if (!s) return MC_OK;
+  DeviceGuard g(c->device);
+  (void)sync_all(c);
+  s->free_buffers();
+  for (auto& v : s->ev) ev_recycle(c, v);
+  std::lock_guard<std::mutex> l(g_mu);
+  g_states.erase(c);
+  return MC_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,117 @@
+// voxel_core.hpp — the scalar core of the voxel-grid filter (voxel.hpp), on plain values so the same
+// text compiles for the device and for the host (tests/test_voxel_cpu.py builds the section between
+// the VOXEL_CORE markers with g++ -ffp-contract=off).  No HIP include.
+//
+// Every line of floating-point arithmetic is ONE IEEE float64 operation, never contracted:
+//   a = double(v) - o     g = a / h     k = floor(g)     f = g - k   (f may round up to 1.0)
+//   Q  = (int64) rint(f * 2^32)                    0 <= Q <= 2^32
+//   QI = (int64) rint(double(intensity) * 2^16)
+// A voxel (kx, ky, kz) keeps n, S[3] = sum Q and SI = sum QI as integers, so the sums do not depend
+// on the order the points arrive in; its outputs are
+//   m = double(S) / double(n)     w = double(k) + m * 2^-32     c = o + w * h
+//   i = (double(SI) / double(n)) * 2^-16
+// Bounds (include/mcdeskew.h): |c - mean| <= h * 2^-32 plus float64 rounding; the intensity
+// is within 2^-17 of the mean.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define MC_VOXEL_FN __host__ __device__ __forceinline__
+#else
+#define MC_VOXEL_FN inline
+#endif
+#if defined(__clang__)
+#define MC_VOXEL_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define MC_VOXEL_NO_CONTRACT
+#endif
+
+namespace mc {
+
+// VOXEL_CORE_BEGIN
+constexpr int32_t kVoxelKeyMin = -(1 << 20);      // keys in [-2^20, 2^20): 21 bits per axis
+constexpr int32_t kVoxelKeyEnd = 1 << 20;
+constexpr double kVoxelFrac = 4294967296.0;       // 2^32: the fixed point of a coordinate inside its voxel
+constexpr double kVoxelFracInv = 1.0 / 4294967296.0;
+constexpr double kVoxelInt = 65536.0;             // 2^16: the fixed point of the intensity
+constexpr double kVoxelIntInv = 1.0 / 65536.0;
+constexpr uint64_t kVoxelEmpty = ~0ull;           // a table slot without a key (bit 63 is never a key's)
+
+struct VoxelPoint {
+  int32_t k[3];
+  int64_t Q[3];
+  int64_t QI;
+  int32_t bad;   // 1: refused (k, Q and QI are 0)
+};
+
+MC_VOXEL_FN bool voxel_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN
+
+// one point: coordinates v (already float64), intensity, voxel size h > 0, origin o
+MC_VOXEL_FN VoxelPoint voxel_quantise(const double v[3], double intensity, double h, const double o[3]) {
+  MC_VOXEL_NO_CONTRACT
+  VoxelPoint r;
+  r.bad = 0;
+  for (int c = 0; c < 3; ++c) {
+    const double a = v[c] - o[c];
+    const double g = a / h;
+    const double k = floor(g);
+    const double f = g - k;
+    const bool ok = voxel_finite(v[c]) && voxel_finite(g) && k >= (double)kVoxelKeyMin && k < (double)kVoxelKeyEnd;
+    r.k[c] = ok ? (int32_t)k : 0;
+    r.Q[c] = ok ? (int64_t)rint(f * kVoxelFrac) : 0;
+    if (!ok) r.bad = 1;
+  }
+  const bool iok = voxel_finite(intensity) && fabs(intensity) <= kVoxelInt;
+  r.QI = iok ? (int64_t)rint(intensity * kVoxelInt) : 0;
+  if (!iok) r.bad = 1;
+  if (r.bad) {
+    for (int c = 0; c < 3; ++c) { r.k[c] = 0; r.Q[c] = 0; }
+    r.QI = 0;
+  }
+  return r;
+}
+
+// 63-bit key: 21 bits per axis, x highest; bit 63 stays clear (kVoxelEmpty has it set)
+MC_VOXEL_FN uint64_t voxel_pack(const int32_t k[3]) {
+  return ((uint64_t)(uint32_t)(k[0] - kVoxelKeyMin) << 42) | ((uint64_t)(uint32_t)(k[1] - kVoxelKeyMin) << 21) |
+         (uint64_t)(uint32_t)(k[2] - kVoxelKeyMin);
+}
+MC_VOXEL_FN void voxel_unpack(uint64_t key, int32_t k[3]) {
+  k[0] = (int32_t)((key >> 42) & 0x1FFFFFu) + kVoxelKeyMin;
+  k[1] = (int32_t)((key >> 21) & 0x1FFFFFu) + kVoxelKeyMin;
+  k[2] = (int32_t)(key & 0x1FFFFFu) + kVoxelKeyMin;
+}
+
+// The probe sequence of a key in a table of mask + 1 slots (a power of two, shift = 64 - log2 of it):
+// Fibonacci hashing, then linear.  Slot index kVoxelNoSlot is never produced — it marks "no slot" in
+// the per-point slot array, and a table of 2^32 slots (2^30 < N < 2^31 points) has a slot of that
+// index; the sequence passes over it, leaving 2^32 - 1 >= 2 N usable slots.
+constexpr uint32_t kVoxelNoSlot = 0xFFFFFFFFu;
+MC_VOXEL_FN uint32_t voxel_slot_next(uint32_t at, uint32_t mask) {
+  const uint32_t n = (at + 1u) & mask;
+  return n == kVoxelNoSlot ? 0u : n;
+}
+MC_VOXEL_FN uint32_t voxel_slot_first(uint64_t key, int shift, uint32_t mask) {
+  const uint32_t at = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift) & mask;
+  return at == kVoxelNoSlot ? 0u : at;
+}
+
+// one voxel: out = cx, cy, cz, intensity (n >= 1)
+MC_VOXEL_FN void voxel_finalise(const int32_t k[3], const int64_t S[3], int64_t SI, int64_t n, double h,
+                                const double o[3], double out[4]) {
+  MC_VOXEL_NO_CONTRACT
+  const double dn = (double)n;
+  for (int c = 0; c < 3; ++c) {
+    const double m = (double)S[c] / dn;
+    const double s = m * kVoxelFracInv;
+    const double w = (double)k[c] + s;
+    const double t = w * h;
+    out[c] = o[c] + t;
+  }
+  const double mi = (double)SI / dn;
+  out[3] = mi * kVoxelIntInv;
+}
+// VOXEL_CORE_END
+
+}  // namespace mc

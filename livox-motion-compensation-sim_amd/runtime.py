@@ -33,6 +33,15 @@ def _release(fn, ctx, *args):
     fn(*args)
 
 
+def _destroy(lib, handle):
+    """Finalizer of a context: the voxel filter's scratch (kept outside mc_ctx, csrc/voxel.hip), then the
+    context itself.  A library loaded from ``lib_path`` may predate the filter."""
+    release = getattr(lib, "mc_voxel_release", None)
+    if release is not None:
+        release(handle)
+    lib.mc_destroy(handle)
+
+
 class Context:
     """One device + stream.  ``device`` defaults to $MCDESKEW_DEVICE, else $LOCAL_RANK modulo the
     visible devices (a launcher that gives each rank its own HIP_VISIBLE_DEVICES leaves every rank
@@ -52,7 +61,11 @@ class Context:
         check(self.lib.mc_create(int(device), ctypes.byref(h)), "mc_create")
         self.handle = h
         self.device = device
-        self._fin = weakref.finalize(self, self.lib.mc_destroy, h)
+        self._fin = weakref.finalize(self, _destroy, self.lib, h)
+        # the voxel filter keeps one build per context (voxel.py): _voxel_gen is the serial number of the
+        # live VoxelCloud (None: none), _voxel_serial the last one handed out
+        self._voxel_gen = None
+        self._voxel_serial = 0
 
     @staticmethod
     def device_count() -> int:
@@ -123,6 +136,11 @@ class Context:
         check(self.lib.mc_deskew(self.handle, inp.handle, out.handle, _lib.MODES[mode],
                                  _lib.POSE_SELECT[pose_select]), f"deskew[{mode}]")
         return out
+
+    def voxel_downsample(self, batch: "Batch", voxel, origin=(0.0, 0.0, 0.0)):
+        """Voxel-grid filter of a (deskewed) batch -> :class:`voxel.VoxelCloud` (voxel.voxel_downsample)."""
+        from .voxel import voxel_downsample
+        return voxel_downsample(batch, voxel, origin, context=self)
 
     def reference_times(self, inp: "Batch", reference):
         """The per-frame reference times (s) :meth:`deskew` uses for ``reference``: ``None`` for
@@ -328,6 +346,13 @@ class Context:
         n = c_int64()
         check(self.lib.mc_timing_read_spans(self.handle, ptr(buf, c_double), cap, ctypes.byref(n)), "timing_read_spans")
         return buf[:min(n.value, cap)].tolist()
+
+    def read_timing_voxel(self) -> dict:
+        """Event time (ms) of the voxel filter's phases since the last read (mc_timing_read_voxel)."""
+        ms = np.zeros(4, np.float64)
+        n = c_int64()
+        check(self.lib.mc_timing_read_voxel(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_voxel")
+        return {"insert_ms": ms[0], "rank_ms": ms[1], "accumulate_ms": ms[2], "finalise_ms": ms[3], "regions": n.value}
 
     def device_buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)
