@@ -155,6 +155,11 @@ int mc_batch_download_time_ns(mc_batch* b, int32_t* t_ns);
  * stream and timed under mc_timing_read_layout. */
 int mc_device_alloc(mc_ctx* ctx, int64_t bytes, void** dptr);
 int mc_device_free(mc_ctx* ctx, void* dptr);
+/* Device memory the library itself holds right now, over every context, batch and communicator of the
+ * process: bytes and blocks (either may be NULL).  Back to what it was once the handles that
+ * allocated are destroyed.  Not counted: the blocks mc_device_alloc hands to the caller, and pinned
+ * host memory. */
+int mc_device_memory_live(int64_t* bytes, int64_t* blocks);
 int mc_memcpy_h2d(mc_ctx* ctx, void* dptr, const void* host, int64_t bytes);
 int mc_memcpy_d2h(mc_ctx* ctx, void* host, const void* dptr, int64_t bytes);
 int mc_memcpy_d2d(mc_ctx* ctx, void* dst, const void* src, int64_t bytes);
@@ -455,8 +460,8 @@ int mc_las_decode_batch(mc_ctx* ctx, const void* d_file, int64_t bytes, int poin
  * *n_voxels = M, so the emits need the source no more and may be called repeatedly.  An emit
  * without a successful build: MC_ERR_STATE.  voxel <= 0 or not finite, origin not finite, ld < 4,
  * 2^31 points or more: MC_ERR_INVALID.
- * Device memory, the context's, kept (and reused while large enough) until mc_voxel_release, which
- * must come before mc_destroy: 16 B per table slot (the power of two >= 2 N slots, so 32 .. 64 B per
+ * Device memory, the context's, kept (and reused while large enough) until mc_destroy, or until
+ * mc_voxel_release, which frees it early (optional; MC_OK when there is nothing): 16 B per table slot (the power of two >= 2 N slots, so 32 .. 64 B per
  * point), 8 B + 1/8 B per point, 36 B per voxel — 2.1 GB + 0.5 GB + up to 2.2 GB for 60 M points.  The
  * emits allocate nothing. */
 int mc_voxel_build_batch(mc_ctx* ctx, const mc_batch* in, double voxel, const double* origin, int64_t* n_voxels,

@@ -73,6 +73,7 @@ _SIGS = {
     "mc_batch_download_time_ns": (c_int, [c_void_p, _pi32]),
     "mc_device_alloc": (c_int, [c_void_p, c_int64, POINTER(c_void_p)]),
     "mc_device_free": (c_int, [c_void_p, c_void_p]),
+    "mc_device_memory_live": (c_int, [_pi64, _pi64]),
     "mc_memcpy_h2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "mc_memcpy_d2h": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
     "mc_memcpy_d2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int64]),

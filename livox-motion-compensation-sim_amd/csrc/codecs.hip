@@ -23,16 +23,11 @@ using namespace mc;
 namespace {
 
 int codec_scratch(mc_ctx* c, size_t bytes, char** out) {
-  if (bytes > c->codec_bytes) {
-    if (c->d_codec) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->d_codec); c->d_codec = nullptr; }
-    c->codec_bytes = 0;
-    HIPCHK(hipMalloc(&c->d_codec, bytes));
-    c->codec_bytes = bytes;
-  }
+  if (int r = ctx_reserve(c, c->d_codec, bytes)) return r;
   if (!c->d_codec_err) {
-    if (int r = dev_alloc(&c->d_codec_err, 1)) return r;
+    if (int r = c->d_codec_err.alloc(1)) return r;
   }
-  *out = static_cast<char*>(c->d_codec);
+  *out = c->d_codec;
   return MC_OK;
 }
 
@@ -234,13 +229,8 @@ int mc_deskew_pcd(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
   }
   // one text-byte slot per 256-point block of the output batch (= one PCD tile)
   const int64_t blocks = out->P / kBlkPts;
-  if (blocks > c->pcd_len_cap) {
-    if (c->d_pcd_len) { (void)hipStreamSynchronize(c->stream); dev_free(c->d_pcd_len); c->d_pcd_len = nullptr; }
-    c->pcd_len_cap = 0;
-    if (int r = dev_alloc(&c->d_pcd_len, (size_t)blocks)) return r;
-    c->pcd_len_cap = blocks;
-  }
-  if (int r = mcimpl::deskew_call(c, in, out, mode, pose_select, blocks > 0 ? c->d_pcd_len : nullptr)) return r;
+  if (int r = ctx_reserve(c, c->d_pcd_len, (size_t)blocks)) return r;
+  if (int r = mcimpl::deskew_call(c, in, out, mode, pose_select, blocks > 0 ? c->d_pcd_len.get() : nullptr)) return r;
   Source src;
   src.batch = out;
   return pcd_encode(c, src, out->F, out->counts.data(), d_out, out_bytes, body_pos, c->d_pcd_len);

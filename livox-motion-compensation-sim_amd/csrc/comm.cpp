@@ -10,6 +10,7 @@
 // librccl is dlopen'ed on first use so the core library loads without it.
 #include "../../include/mcdeskew.h"
 #include "internal.hpp"
+#include "hostutil.hpp"
 #include "gather.hpp"
 #include "plan.hpp"
 
@@ -19,8 +20,6 @@
 #include <cstring>
 #include <mutex>
 #include <vector>
-
-using mcimpl::fail;
 
 namespace {
 struct Rccl {
@@ -76,25 +75,12 @@ struct mc_comm {
   mc_ctx* ctx = nullptr;
   ncclComm_t comm = nullptr;
   int nranks = 0, rank = 0;
-  int64_t* d_scratch = nullptr;  // kPlanWords (nranks + 1) int64: the per-rank plan allgather
-  float* d_stage = nullptr;      // root: shards whose column count differs from the merged batch
-  int64_t stage_cap = 0;
-  double* d_red = nullptr;       // reduction buffer
-  int64_t red_cap = 0;
+  DevBuf<int64_t> d_scratch;   // kPlanWords (nranks + 1) int64: the per-rank plan allgather
+  DevBuf<float> d_stage;       // root: shards whose column count differs from the merged batch (grow-only)
+  DevBuf<double> d_red;        // reduction buffer
 };
 
 namespace {
-// grow-only device staging area for shards re-pitched on arrival
-int ensure_stage(float** d, int64_t* cap, int64_t values) {
-  if (values <= *cap) return MC_OK;
-  if (*d) (void)hipFree(*d);
-  *d = nullptr;
-  *cap = 0;
-  const hipError_t e = hipMalloc(d, (size_t)values * sizeof(float));
-  if (e != hipSuccess) return fail(MC_ERR_NOMEM, "gather staging (%lld values): %s", (long long)values, hipGetErrorString(e));
-  *cap = values;
-  return MC_OK;
-}
 // plan.hpp's gather_finish with device copies on stream s (HIP status of the first failure)
 hipError_t finish_on_device(const mcplan::GatherPlan& G, int nranks, int root, const int64_t* P, const int64_t* C,
                             mc_batch* merged, const float* root_src, const float* stage, hipStream_t s) {
@@ -117,11 +103,6 @@ hipError_t finish_on_device(const mcplan::GatherPlan& G, int nranks, int root, c
   do {                                                                                    \
     ncclResult_t r_ = (expr);                                                             \
     if (r_ != ncclSuccess) return fail(MC_ERR_COMM, "%s: %s", #expr, g_rccl.GetErrorString(r_)); \
-  } while (0)
-#define HIPCHK(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess) return fail(MC_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
 // mcgather::Transport over RCCL on the context stream: the plan words through one ncclAllGather of
@@ -166,7 +147,7 @@ mcgather::Transport rccl_transport(RcclGather* x) {
   };
   T.stage = [](void* p, int64_t values, float** out) {
     RcclGather* g = static_cast<RcclGather*>(p);
-    if (int r = ensure_stage(&g->c->d_stage, &g->c->stage_cap, values)) return r;
+    if (int r = ctx_reserve(g->c->ctx, g->c->d_stage, (size_t)std::max<int64_t>(values, 0))) return r;
     *out = g->c->d_stage;
     return MC_OK;
   };
@@ -204,18 +185,17 @@ int mc_comm_init(mc_ctx* ctx, int nranks, int rank, const char id_in[128], mc_co
   HIPCHK(hipSetDevice(ctx->device));
   ncclUniqueId id;
   std::memcpy(id.internal, id_in, NCCL_UNIQUE_ID_BYTES);
-  mc_comm* c = new mc_comm();
+  std::unique_ptr<mc_comm> c(new mc_comm());
   c->ctx = ctx;
   c->nranks = nranks;
   c->rank = rank;
   ncclResult_t r = g_rccl.CommInitRank(&c->comm, nranks, id, rank);
-  if (r != ncclSuccess) { delete c; return fail(MC_ERR_COMM, "ncclCommInitRank: %s", g_rccl.GetErrorString(r)); }
-  if (hipMalloc(&c->d_scratch, sizeof(int64_t) * kPlanWords * (nranks + 1)) != hipSuccess) {
+  if (r != ncclSuccess) return fail(MC_ERR_COMM, "ncclCommInitRank: %s", g_rccl.GetErrorString(r));
+  if (int e = c->d_scratch.alloc((size_t)kPlanWords * (nranks + 1))) {
     g_rccl.CommDestroy(c->comm);
-    delete c;
-    return fail(MC_ERR_NOMEM, "hipMalloc failed");
+    return e;
   }
-  *out = c;
+  *out = c.release();
   return MC_OK;
 }
 
@@ -224,9 +204,6 @@ int mc_comm_destroy(mc_comm* c) {
   (void)hipSetDevice(c->ctx->device);
   (void)hipStreamSynchronize(c->ctx->stream);
   if (c->comm) g_rccl.CommDestroy(c->comm);
-  if (c->d_scratch) (void)hipFree(c->d_scratch);
-  if (c->d_red) (void)hipFree(c->d_red);
-  if (c->d_stage) (void)hipFree(c->d_stage);
   delete c;
   return MC_OK;
 }
@@ -263,13 +240,7 @@ int mc_comm_allreduce_max_f64(mc_comm* c, double* v, int64_t n) {
   if (n <= 0) return MC_OK;
   HIPCHK(hipSetDevice(c->ctx->device));
   hipStream_t s = c->ctx->stream;
-  if (n > c->red_cap) {
-    if (c->d_red) (void)hipFree(c->d_red);
-    c->d_red = nullptr;
-    c->red_cap = 0;
-    HIPCHK(hipMalloc(&c->d_red, sizeof(double) * n));
-    c->red_cap = n;
-  }
+  if (int r = ctx_reserve(c->ctx, c->d_red, (size_t)n)) return r;
   HIPCHK(hipMemcpyAsync(c->d_red, v, sizeof(double) * n, hipMemcpyHostToDevice, s));
   NCCLCHK(g_rccl.AllReduce(c->d_red, c->d_red, (size_t)n, ncclFloat64, ncclMax, c->comm, s));
   HIPCHK(hipMemcpyAsync(v, c->d_red, sizeof(double) * n, hipMemcpyDeviceToHost, s));
@@ -314,8 +285,8 @@ int mc_gather_batches(mc_ctx* ctx, int32_t n, const mc_batch* const* shards, int
   if (!perr.empty()) return fail(MC_ERR_INVALID, "%s", perr.c_str());
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  float* stage = nullptr;
-  if (G.stage_values > 0) HIPCHK(hipMalloc(&stage, (size_t)G.stage_values * sizeof(float)));
+  DevBuf<float> stage;   // freed on every way out
+  if (G.stage_values > 0) if (int r = stage.alloc((size_t)G.stage_values)) return r;
   merged->wrote(false);
   hipError_t e = hipSuccess;
   for (int32_t q = 0; q < n && e == hipSuccess; ++q) {
@@ -325,7 +296,6 @@ int mc_gather_batches(mc_ctx* ctx, int32_t n, const mc_batch* const* shards, int
   }
   if (e == hipSuccess) e = finish_on_device(G, n, root, P.data(), C.data(), merged, shards[root]->d_cols, stage, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (stage) (void)hipFree(stage);
   if (e != hipSuccess) return fail(MC_ERR_HIP, "gather_batches: %s", hipGetErrorString(e));
   merged->trange_valid = false;
   return MC_OK;

@@ -23,40 +23,26 @@ using mcimpl::fail;
   } while (0)
 
 // ------------------------------------------------------------------------------------------------
-// small device-buffer helpers
+// growing a buffer of the context (devbuf.hpp)
 // ------------------------------------------------------------------------------------------------
-template <typename T>
-static inline int dev_alloc(T** p, size_t n) {
-  *p = nullptr;
-  if (n == 0) n = 1;
-  HIPCHK(hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
-  return MC_OK;
-}
-template <typename T>
-static inline void dev_free(T*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
+// At least n elements in buf, the contents not kept.  The one rule for giving a block back: work
+// queued on the main stream may still use it, so that stream drains first — on the reallocation path
+// only.  (A block the row stream may use needs sync_all before this: rel_table.)
+template <typename Buf>
+static inline int ctx_reserve(mc_ctx* c, Buf& buf, size_t n, bool* grew = nullptr) {
+  if (buf && n > buf.capacity()) (void)hipStreamSynchronize(c->stream);
+  return buf.reserve(n, grew);
 }
 
 static inline int ctx_stage(mc_ctx* c, size_t bytes, void** out) {
-  if (bytes > c->stage_bytes) {
-    if (c->d_stage) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->d_stage); c->d_stage = nullptr; }
-    c->stage_bytes = 0;
-    HIPCHK(hipMalloc(&c->d_stage, bytes));
-    c->stage_bytes = bytes;
-  }
+  if (int r = ctx_reserve(c, c->d_stage, bytes)) return r;
   *out = c->d_stage;
   return MC_OK;
 }
 
 // pinned, device-mapped host scratch of at least `bytes` (the zero-copy path of the single calls)
 static inline int ctx_pin(mc_ctx* c, size_t bytes, void** out) {
-  if (bytes > c->pin_bytes) {
-    if (c->h_pin) { (void)hipStreamSynchronize(c->stream); (void)hipHostFree(c->h_pin); c->h_pin = nullptr; }
-    c->pin_bytes = 0;
-    HIPCHK(hipHostMalloc(&c->h_pin, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    c->pin_bytes = bytes;
-  }
+  if (int r = ctx_reserve(c, c->h_pin, bytes)) return r;
   *out = c->h_pin;
   return MC_OK;
 }
@@ -122,7 +108,6 @@ static inline hipEvent_t ev_take(mc_ctx* c) {
   if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return nullptr;
   return e;
 }
-using EventPairs = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
 // the pairs of v back into the pool
 static inline void ev_recycle(mc_ctx* c, EventPairs& v) {
   for (auto& p : v) { c->ev_pool.push_back(p.first); c->ev_pool.push_back(p.second); }

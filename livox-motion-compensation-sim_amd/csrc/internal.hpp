@@ -13,6 +13,8 @@
 #include <utility>
 #include <vector>
 
+#include "devbuf.hpp"
+
 namespace mc {
 struct Tile;
 struct PoseSeg;
@@ -72,12 +74,34 @@ class HostPool {
   uint64_t gen_ = 0;
   bool stop_ = false;
 };
-}  // namespace mcimpl
 
-struct mc_ctx {
-  int device = 0;
+// What a context owns that is not memory.  A base of mc_ctx, so it is destroyed after every member:
+// the buffers go first, then the pooled events, then the two streams.
+struct CtxQueues {
   hipStream_t stream = nullptr;   // main stream: staging, k_prep and the deskew kernels (one queue)
   hipStream_t row_d2h = nullptr;  // the row pipeline's D2H copies, beside its H2D + kernel on `stream`
+  std::vector<hipEvent_t> ev_pool;
+  CtxQueues() = default;
+  CtxQueues(const CtxQueues&) = delete;
+  CtxQueues& operator=(const CtxQueues&) = delete;
+  ~CtxQueues() {
+    for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e);
+    if (row_d2h) (void)hipStreamDestroy(row_d2h);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+using EventPairs = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
+
+// State another translation unit keeps in a context (voxel.hip): destroyed with the context's buffers,
+// before the event pool and the streams.
+struct CtxExt { virtual ~CtxExt() = default; };
+}  // namespace mcimpl
+using mcimpl::DevBuf;
+using mcimpl::EventPairs;
+
+struct mc_ctx : mcimpl::CtxQueues {
+  ~mc_ctx();   // mcdeskew.hip, where the records the buffers hold are complete types
+  int device = 0;
   // per-step tables come in two halves: the next step's prep writes half `buf` while the previous
   // step's deskew kernel still reads the other (see mc_deskew)
   int buf = 0;
@@ -114,25 +138,24 @@ struct mc_ctx {
   // paths' per-frame poses (rot.cpp frame_poses)
   int64_t T = 0, T_cap = 0;
   std::vector<double> h_time, h_pos, h_rpy;
-  double* d_time = nullptr;
-  double* d_pos = nullptr;
-  double* d_rpy = nullptr;
-  mc::PoseSeg* d_pose_seg = nullptr;   // 2 * T_cap (double buffer)
+  DevBuf<double> d_time;
+  DevBuf<double> d_pos;
+  DevBuf<double> d_rpy;
+  DevBuf<mc::PoseSeg> d_pose_seg;      // 2 * T_cap (double buffer)
   // IMU (CSIM:1191-1240)
   int64_t M = 0, M_cap = 0;
-  int64_t* d_imu_ts = nullptr;
-  double* d_gyro = nullptr;
-  mc::ImuSeg* d_imu_seg = nullptr;     // 2 * M_cap (double buffer)
+  DevBuf<int64_t> d_imu_ts;
+  DevBuf<double> d_gyro;
+  DevBuf<mc::ImuSeg> d_imu_seg;        // 2 * M_cap (double buffer)
   // scan_environment state (LMC:701-770): scene, per-frame f64 poses, per-(frame, tile) counts
   int64_t E = 0;
-  double* d_env = nullptr;   // the scene as columns (scan.hpp scene_cols)
+  DevBuf<double> d_env;   // the scene as columns (scan.hpp scene_cols)
   int32_t scan_F = 0, scan_tiles = 0;
-  double* d_scan_pose = nullptr;
-  int32_t* d_scan_tcount = nullptr;
-  int64_t* d_scan_toff = nullptr;
-  int64_t* d_scan_nvis = nullptr;
-  uint32_t* d_scan_bits = nullptr;    // pass-1 visibility words
-  size_t scan_bits_cap = 0;
+  DevBuf<double> d_scan_pose;
+  DevBuf<int32_t> d_scan_tcount;
+  DevBuf<int64_t> d_scan_toff;
+  DevBuf<int64_t> d_scan_nvis;
+  DevBuf<uint32_t> d_scan_bits;       // pass-1 visibility words
   std::vector<int64_t> scan_counts;   // final per-frame counts of the last mc_scan_count
   double scan_par[4] = {0, 0, 0, 0};  // range_min, range_max^2, fov_h/2, fov_v/2
   int64_t scan_cap = 0;
@@ -140,59 +163,54 @@ struct mc_ctx {
   // on any other scene is refused (the poses were copied to d_scan_pose by the count itself)
   uint64_t env_ver = 0, scan_env_ver = 0;
   bool scan_valid = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> scan_ev;
+  EventPairs scan_ev;
   // ray-march scanner state (CSIM:1011-1146, raymarch.hpp): the scene of point objects as columns
   // plus each point's object, then what the last mc_ray_count left for its emit
   int64_t ray_E = 0;
-  double* d_ray_scene = nullptr;            // x, y, z, intensity columns
-  int32_t* d_ray_obj = nullptr;             // object (list position) of every scene point
+  DevBuf<double> d_ray_scene;               // x, y, z, intensity columns
+  DevBuf<int32_t> d_ray_obj;                // object (list position) of every scene point
   std::vector<int64_t> ray_obj_start;       // first scene index of every object (n_objects + 1)
   uint64_t ray_scene_ver = 0, ray_count_ver = 0;
   bool ray_valid = false;
   int32_t ray_F = 0, ray_n = 0, ray_K = 0;
-  double* d_ray_frame = nullptr;            // per frame: origin (3), R (9)
-  double* d_ray_dirs = nullptr;
-  double* d_ray_steps = nullptr;
-  void* d_ray_part = nullptr;               // per-chunk keys of the count pass
-  size_t ray_part_bytes = 0;
-  void* d_ray_hit = nullptr;                // RayHit per (frame, ray)
+  DevBuf<double> d_ray_frame;               // per frame: origin (3), R (9)
+  DevBuf<double> d_ray_dirs;
+  DevBuf<double> d_ray_steps;
+  DevBuf<char> d_ray_part;                  // per-chunk keys (RayKey) of the count pass
+  DevBuf<char> d_ray_hit;                   // RayHit per (frame, ray)
   std::vector<int64_t> ray_counts;          // hits per frame of the last mc_ray_count
   std::vector<int32_t> ray_hits;            // (F * n_rays, 3): step, object, point index in the object
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ray_ev;
+  EventPairs ray_ev;
   // output codecs: per-call frame / unit tables carved from one scratch buffer, error flag
-  void* d_codec = nullptr;
-  size_t codec_bytes = 0;
-  int* d_codec_err = nullptr;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> codec_ev;
+  DevBuf<char> d_codec;
+  DevBuf<int> d_codec_err;
+  EventPairs codec_ev;
   // mc_deskew_pcd: ASCII PCD text bytes per 256-point output block, written by the deskew kernel
-  int32_t* d_pcd_len = nullptr;
-  int64_t pcd_len_cap = 0;
+  DevBuf<int32_t> d_pcd_len;
   // segment table of the float64 per-point path (mc_deskew_points_f64): built by k_prep for one mode
   // and the trajectory / IMU upload it came from (seg64_ver), rebuilt when either changes
-  void* d_seg64 = nullptr;
-  size_t seg64_bytes = 0;
+  DevBuf<char> d_seg64;
   int seg64_mode = -1;
   uint64_t seg64_ver = 0;
   // pinned, device-mapped host buffer of the single-call drop-in path
-  void* h_pin = nullptr;
-  size_t pin_bytes = 0;
+  mcimpl::PinBuf<char, hipHostMallocMapped | hipHostMallocCoherent> h_pin;
   // host <-> device row pipeline (double-buffered pinned and device chunks, in + out)
-  void* h_pipe = nullptr;
-  void* d_pipe = nullptr;
+  mcimpl::PinBuf<char, hipHostMallocDefault> h_pipe;
+  DevBuf<char> d_pipe;
   std::unique_ptr<mcimpl::HostPool> pool;
   // staging buffer for host<->device layout conversion
-  void* d_stage = nullptr;
-  size_t stage_bytes = 0;
+  DevBuf<char> d_stage;
   // launch knobs / timing
   int32_t max_grid = 0;
   bool timing = false;
   double wall_khz = 0.0;   // wall_clock64() rate
   // workgroup spans of timed deskew launches (DeskewArgs::span): kSpanSlots slots of 1 + kSpanTail
   // wall-clock stamps, zeroed, handed out in launch order until mc_timing_read_spans
-  unsigned long long* d_span = nullptr;
+  DevBuf<unsigned long long> d_span;
   int32_t span_used = 0;
-  std::vector<hipEvent_t> ev_pool;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> main_ev, prep_ev, layout_ev;
+  EventPairs main_ev, prep_ev, layout_ev;
+  // the voxel-grid filter's state (voxel.hip; freed early by mc_voxel_release)
+  std::unique_ptr<mcimpl::CtxExt> voxel;
 };
 
 struct mc_batch {
@@ -212,45 +230,44 @@ struct mc_batch {
   mutable int hot_order = 0;
   // blocked columns: block k (points 256k .. 256k+255) holds its C columns of 256 values back to
   // back, C * P values in all (mc::bidx); t_ns, when present, is column 4 (int32 bits)
-  float* d_cols = nullptr;
+  DevBuf<float> d_cols;
   bool has_t() const { return C == 5; }
-  int64_t* d_counts = nullptr;
-  int64_t* d_poff = nullptr;
-  int64_t* d_doff = nullptr;
-  mc::Tile* d_tiles = nullptr;
-  double* d_frame_time = nullptr;
-  int64_t* d_frame_start = nullptr;
+  DevBuf<int64_t> d_counts;
+  DevBuf<int64_t> d_poff;
+  DevBuf<int64_t> d_doff;
+  DevBuf<mc::Tile> d_tiles;
+  DevBuf<double> d_frame_time;
+  DevBuf<int64_t> d_frame_start;
   // k_prep outputs, double-buffered (ctx->buf selects the half): F entries per half
-  mc::FrameRow* d_frame_tbl = nullptr;   // 3 float64 rows per frame (R row, t)
-  int2* d_trange = nullptr;        // per-frame [min, max] t_ns (valid when trange_valid)
-  mc::FrameWin* d_fwin = nullptr;  // per-frame segment window
-  void* d_frec = nullptr;          // 2 frame-specialised pose/IMU records per frame
-  size_t frec_half = 0;            // bytes per half of d_frec
+  DevBuf<mc::FrameRow> d_frame_tbl;   // 3 float64 rows per frame (R row, t)
+  DevBuf<int2> d_trange;             // per-frame [min, max] t_ns (valid when trange_valid)
+  DevBuf<mc::FrameWin> d_fwin;       // per-frame segment window
+  DevBuf<char> d_frec;               // 2 frame-specialised pose/IMU records per frame
+  size_t frec_half = 0;              // bytes per half of d_frec
   // per sub-tile windows (batches with t_ns): frames wider than the SGPR path use these
-  int32_t* d_ftile = nullptr;      // first tile of each frame (F+1)
-  int2* d_strange = nullptr;       // per sub-tile [min, max] t_ns
-  mc::FrameWin* d_swin = nullptr;  // per sub-tile window, double-buffered (2 * n_sub)
-  double* d_partial = nullptr;
+  DevBuf<int32_t> d_ftile;            // first tile of each frame (F+1)
+  DevBuf<int2> d_strange;            // per sub-tile [min, max] t_ns
+  DevBuf<mc::FrameWin> d_swin;       // per sub-tile window, double-buffered (2 * n_sub)
+  DevBuf<double> d_partial;
   bool has_times = false, has_starts = false, trange_valid = false;
   // mc_deskew_relative: the per-frame relative segment table (relative.hpp) — frame f's records
   // [d_roff[f], d_roff[f+1]) are its segments [klo, khi] folded into its reference pose.  Kept with
   // the batch: the offsets hold while the trajectory upload (rel_traj) and the batch's frame times and
   // t_ns spans (rel_frames = prep_ver) are the ones they were counted for, the records while the
   // reference times are the same too (rel_own: each frame's own time; else rel_tref).
-  mc::PoseSeg* d_rel = nullptr;
-  size_t rel_cap = 0;              // records allocated
+  DevBuf<mc::PoseSeg> d_rel;
   int64_t rel_total = 0;           // records in use (d_roff[F])
-  int64_t* d_roff = nullptr;       // F + 1
-  int32_t* d_relw = nullptr;       // F window widths (the count pass)
-  double* d_tref = nullptr;        // F reference times
-  double* d_refpose = nullptr;     // F reference quaternions (4 F), then F reference positions (3 F)
+  DevBuf<int64_t> d_roff;          // F + 1
+  DevBuf<int32_t> d_relw;          // F window widths (the count pass)
+  DevBuf<double> d_tref;           // F reference times
+  DevBuf<double> d_refpose;        // F reference quaternions (4 F), then F reference positions (3 F)
   bool rel_offsets_valid = false, rel_valid = false, rel_own = false;
   uint64_t rel_traj = 0, rel_frames = 0;
   std::vector<double> rel_tref;
   // MC_BATCH_WITH_PCD_LEN: ASCII PCD text bytes per 256-point block (layout.hpp PcdCount sums).
   // data_ver counts the writes of the x|y|z|intensity columns; pcd_ver is the data_ver the sums
   // were written with (current iff equal).
-  int32_t* d_pcd_len = nullptr;
+  DevBuf<int32_t> d_pcd_len;
   uint64_t data_ver = 1, pcd_ver = 0;
   void wrote(bool with_sums) {                               // after queueing a write of the columns
     ++data_ver;

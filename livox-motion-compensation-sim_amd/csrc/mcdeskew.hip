@@ -129,6 +129,12 @@ static void with_mode(int mode, F&& f) {
   else f(std::integral_constant<int, MC_MODE_IMU>{});
 }
 
+// The recorded timing pairs go back to the pool; the members then free every buffer, and the base the
+// pooled events and the two streams.
+mc_ctx::~mc_ctx() {
+  for (EventPairs* v : {&codec_ev, &main_ev, &scan_ev, &ray_ev, &prep_ev, &layout_ev}) ev_recycle(this, *v);
+}
+
 // ------------------------------------------------------------------------------------------------
 extern "C" {
 
@@ -153,24 +159,10 @@ int mc_device_pci_bus_id(int device, char* out, int len) {
 constexpr int32_t kSpanSlots = 64;
 constexpr size_t kSpanWords = 1 + kSpanTail;
 
-// frees everything the context owns, then the context: mc_destroy, and mc_create's failure path,
-// where the handles not yet created are still null
-static void ctx_release(mc_ctx* c) {
-  dev_free(c->d_time); dev_free(c->d_pos); dev_free(c->d_rpy); dev_free(c->d_pose_seg);
-  dev_free(c->d_imu_ts); dev_free(c->d_gyro); dev_free(c->d_imu_seg);
-  dev_free(c->d_env); dev_free(c->d_scan_pose); dev_free(c->d_scan_tcount);
-  dev_free(c->d_scan_toff); dev_free(c->d_scan_nvis); dev_free(c->d_scan_bits);
-  dev_free(c->d_codec_err); dev_free(c->d_pcd_len); dev_free(c->d_span);
-  dev_free(c->d_ray_scene); dev_free(c->d_ray_obj); dev_free(c->d_ray_frame); dev_free(c->d_ray_dirs);
-  dev_free(c->d_ray_steps);
-  for (void* p : {c->d_codec, c->d_seg64, c->d_pipe, c->d_stage, c->d_ray_part, c->d_ray_hit}) if (p) (void)hipFree(p);
-  for (void* p : {c->h_pin, c->h_pipe}) if (p) (void)hipHostFree(p);
-  for (EventPairs* v : {&c->codec_ev, &c->main_ev, &c->scan_ev, &c->ray_ev, &c->prep_ev, &c->layout_ev})
-    ev_recycle(c, *v);
-  for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-  if (c->row_d2h) (void)hipStreamDestroy(c->row_d2h);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  delete c;
+int mc_device_memory_live(int64_t* bytes, int64_t* blocks) {
+  if (bytes) *bytes = mcimpl::g_live_bytes.load();
+  if (blocks) *blocks = mcimpl::g_live_blocks.load();
+  return MC_OK;
 }
 
 int mc_create(int device, mc_ctx** out) {
@@ -185,18 +177,15 @@ int mc_create(int device, mc_ctx** out) {
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(MC_ERR_STATE, "device %d is %s; this library is built for gfx950 (MI355X) only",
                 device, prop.gcnArchName);
-  mc_ctx* c = new mc_ctx();
+  std::unique_ptr<mc_ctx> c(new mc_ctx());   // a failure below frees what was created so far
   c->device = device;
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->row_d2h, hipStreamNonBlocking);
+  if (e != hipSuccess) return fail(MC_ERR_HIP, "stream/event creation: %s", hipGetErrorString(e));
   // the launch-span pool (span_take), zeroed
-  if (e == hipSuccess) e = hipMalloc(&c->d_span, kSpanSlots * kSpanWords * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(c->d_span, 0, kSpanSlots * kSpanWords * sizeof(unsigned long long));
-  if (e != hipSuccess) {
-    ctx_release(c);
-    return fail(MC_ERR_HIP, "stream/event creation: %s", hipGetErrorString(e));
-  }
-  *out = c;
+  if (int r = c->d_span.alloc(kSpanSlots * kSpanWords)) return r;
+  HIPCHK(hipMemset(c->d_span, 0, kSpanSlots * kSpanWords * sizeof(unsigned long long)));
+  *out = c.release();
   return MC_OK;
 }
 
@@ -204,7 +193,7 @@ int mc_destroy(mc_ctx* c) {
   if (!c) return MC_OK;
   DeviceGuard g(c->device);
   (void)sync_all(c);
-  ctx_release(c);
+  delete c;
   return MC_OK;
 }
 
@@ -232,12 +221,12 @@ int mc_set_trajectory(mc_ctx* c, int64_t T, const double* time, const double* po
   if (int r = sync_all(c)) return r;
   ++c->traj_ver;   // before anything changes (a failed upload must not leave a matching key)
   if (T > c->T_cap) {
-    dev_free(c->d_time); dev_free(c->d_pos); dev_free(c->d_rpy); dev_free(c->d_pose_seg);
+    c->d_time.reset(); c->d_pos.reset(); c->d_rpy.reset(); c->d_pose_seg.reset();
     c->T_cap = 0;
-    if (int r = dev_alloc(&c->d_time, T)) return r;
-    if (int r = dev_alloc(&c->d_pos, 3 * T)) return r;
-    if (int r = dev_alloc(&c->d_rpy, 3 * T)) return r;
-    if (int r = dev_alloc(&c->d_pose_seg, 2 * T)) return r;
+    if (int r = c->d_time.alloc(T)) return r;
+    if (int r = c->d_pos.alloc(3 * T)) return r;
+    if (int r = c->d_rpy.alloc(3 * T)) return r;
+    if (int r = c->d_pose_seg.alloc(2 * T)) return r;
     c->T_cap = T;
   }
   HIPCHK(hipMemcpyAsync(c->d_time, time, T * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -261,11 +250,11 @@ int mc_set_imu(mc_ctx* c, int64_t M, const int64_t* ts, const double* gyro) {
   if (int r = sync_all(c)) return r;
   ++c->imu_ver;
   if (M > c->M_cap) {
-    dev_free(c->d_imu_ts); dev_free(c->d_gyro); dev_free(c->d_imu_seg);
+    c->d_imu_ts.reset(); c->d_gyro.reset(); c->d_imu_seg.reset();
     c->M_cap = 0;
-    if (int r = dev_alloc(&c->d_imu_ts, M)) return r;
-    if (int r = dev_alloc(&c->d_gyro, 3 * M)) return r;
-    if (int r = dev_alloc(&c->d_imu_seg, 2 * M)) return r;
+    if (int r = c->d_imu_ts.alloc(M)) return r;
+    if (int r = c->d_gyro.alloc(3 * M)) return r;
+    if (int r = c->d_imu_seg.alloc(2 * M)) return r;
     c->M_cap = M;
   }
   HIPCHK(hipMemcpyAsync(c->d_imu_ts, ts, M * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
@@ -285,7 +274,8 @@ int mc_batch_create(mc_ctx* c, int32_t F, const int64_t* counts, uint32_t flags,
   mcplan::BatchLayout L;
   const std::string perr = mcplan::plan_batch(counts, F, kTileGroups, kSub, &L);
   if (!perr.empty()) return fail(MC_ERR_INVALID, "%s", perr.c_str());
-  mc_batch* b = new mc_batch();
+  std::unique_ptr<mc_batch> owner(new mc_batch());   // a failure below frees what was allocated so far
+  mc_batch* b = owner.get();
   static std::atomic<uint64_t> next_uid{1};
   b->ctx = c;
   b->uid = next_uid.fetch_add(1);
@@ -303,46 +293,45 @@ int mc_batch_create(mc_ctx* c, int32_t F, const int64_t* counts, uint32_t flags,
   b->n_tiles = (int32_t)tiles.size();
   DeviceGuard g(c->device);
   int r = MC_OK;
-  auto bail = [&](int code) { mc_batch_destroy(b); return code; };
-  if ((r = dev_alloc(&b->d_cols, col_vals))) return bail(r);
-  if ((r = dev_alloc(&b->d_counts, F + 1))) return bail(r);
-  if ((r = dev_alloc(&b->d_poff, F + 1))) return bail(r);
-  if ((r = dev_alloc(&b->d_doff, F + 1))) return bail(r);
-  if ((r = dev_alloc(&b->d_tiles, tiles.size()))) return bail(r);
-  if ((r = dev_alloc(&b->d_frame_time, F))) return bail(r);
-  if ((r = dev_alloc(&b->d_frame_start, F))) return bail(r);
+  if ((r = b->d_cols.alloc(col_vals))) return r;
+  if ((r = b->d_counts.alloc(F + 1))) return r;
+  if ((r = b->d_poff.alloc(F + 1))) return r;
+  if ((r = b->d_doff.alloc(F + 1))) return r;
+  if ((r = b->d_tiles.alloc(tiles.size()))) return r;
+  if ((r = b->d_frame_time.alloc(F))) return r;
+  if ((r = b->d_frame_start.alloc(F))) return r;
   // k_prep outputs: two halves (double buffer, see mc_deskew)
-  if ((r = dev_alloc(&b->d_frame_tbl, 2 * 3 * (size_t)F))) return bail(r);
-  if ((r = dev_alloc(&b->d_trange, F))) return bail(r);
-  if ((r = dev_alloc(&b->d_fwin, 2 * (size_t)F))) return bail(r);
+  if ((r = b->d_frame_tbl.alloc(2 * 3 * (size_t)F))) return r;
+  if ((r = b->d_trange.alloc(F))) return r;
+  if ((r = b->d_fwin.alloc(2 * (size_t)F))) return r;
   b->frec_half = 2 * (size_t)std::max<int>(F, 1) * std::max(sizeof(PoseWin), sizeof(ImuSeg));
-  if ((r = dev_alloc(reinterpret_cast<char**>(&b->d_frec), 2 * b->frec_half))) return bail(r);
+  if ((r = b->d_frec.alloc(2 * b->frec_half))) return r;
   const size_t n_sub = std::max<size_t>(tiles.size(), 1) * kSub;
   if (b->has_t()) {
-    if ((r = dev_alloc(&b->d_ftile, F + 1))) return bail(r);
-    if ((r = dev_alloc(&b->d_strange, n_sub))) return bail(r);
-    if ((r = dev_alloc(&b->d_swin, 2 * n_sub))) return bail(r);
+    if ((r = b->d_ftile.alloc(F + 1))) return r;
+    if ((r = b->d_strange.alloc(n_sub))) return r;
+    if ((r = b->d_swin.alloc(2 * n_sub))) return r;
   }
-  if ((r = dev_alloc(&b->d_partial, 5 * (size_t)b->n_tiles))) return bail(r);
-  if ((flags & MC_BATCH_WITH_PCD_LEN) && (r = dev_alloc(&b->d_pcd_len, std::max<int64_t>(b->P / kBlkPts, 1))))
-    return bail(r);
+  if ((r = b->d_partial.alloc(5 * (size_t)b->n_tiles))) return r;
+  if ((flags & MC_BATCH_WITH_PCD_LEN) && (r = b->d_pcd_len.alloc(std::max<int64_t>(b->P / kBlkPts, 1))))
+    return r;
   hipStream_t s = c->stream;
   auto cpy = [&](void* d, const void* h, size_t n) { return hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, s); };
   if (F > 0) {
     if (cpy(b->d_counts, b->counts.data(), F * sizeof(int64_t)) != hipSuccess ||
         cpy(b->d_poff, b->poff.data(), (F + 1) * sizeof(int64_t)) != hipSuccess ||
         cpy(b->d_doff, b->doff.data(), (F + 1) * sizeof(int64_t)) != hipSuccess)
-      return bail(fail(MC_ERR_HIP, "batch metadata upload failed"));
+      return fail(MC_ERR_HIP, "batch metadata upload failed");
     if (!tiles.empty() && cpy(b->d_tiles, tiles.data(), tiles.size() * sizeof(Tile)) != hipSuccess)
-      return bail(fail(MC_ERR_HIP, "tile table upload failed"));
+      return fail(MC_ERR_HIP, "tile table upload failed");
     if (b->d_ftile && cpy(b->d_ftile, ftile.data(), (F + 1) * sizeof(int32_t)) != hipSuccess)
-      return bail(fail(MC_ERR_HIP, "frame tile table upload failed"));
+      return fail(MC_ERR_HIP, "frame tile table upload failed");
   }
   // zero the columns so padding slots are defined even before the first upload
   if (hipMemsetAsync(b->d_cols, 0, col_vals * sizeof(float), s) != hipSuccess)
-    return bail(fail(MC_ERR_HIP, "memset failed"));
-  if (hipStreamSynchronize(s) != hipSuccess) return bail(fail(MC_ERR_HIP, "sync failed"));
-  *out = b;
+    return fail(MC_ERR_HIP, "memset failed");
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(MC_ERR_HIP, "sync failed");
+  *out = owner.release();
   return MC_OK;
 }
 
@@ -350,14 +339,6 @@ int mc_batch_destroy(mc_batch* b) {
   if (!b) return MC_OK;
   DeviceGuard g(b->ctx->device);
   (void)sync_all(b->ctx);
-  dev_free(b->d_cols); dev_free(b->d_counts); dev_free(b->d_poff); dev_free(b->d_doff);
-  dev_free(b->d_tiles); dev_free(b->d_frame_time); dev_free(b->d_frame_start); dev_free(b->d_frame_tbl);
-  dev_free(b->d_trange); dev_free(b->d_fwin); dev_free(b->d_partial);
-  if (b->d_frec) (void)hipFree(b->d_frec);
-  b->d_frec = nullptr;
-  dev_free(b->d_ftile); dev_free(b->d_strange); dev_free(b->d_swin);
-  dev_free(b->d_pcd_len);
-  dev_free(b->d_rel); dev_free(b->d_roff); dev_free(b->d_relw); dev_free(b->d_tref); dev_free(b->d_refpose);
   delete b;
   return MC_OK;
 }
@@ -715,7 +696,7 @@ void deskew_plan(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pos
   const mc_batch* pb = in;  // per-frame tables live with the input batch
   FrameRow* frame_tbl = pb->d_frame_tbl + 3 * (size_t)in->F * h;
   FrameWin* fwin = pb->d_fwin + (size_t)in->F * h;
-  void* frec = static_cast<char*>(pb->d_frec) + pb->frec_half * h;
+  void* frec = pb->d_frec + pb->frec_half * h;
   PoseSeg* pose_seg = c->d_pose_seg ? c->d_pose_seg + (size_t)c->T_cap * h : nullptr;
   ImuSeg* imu_seg = c->d_imu_seg ? c->d_imu_seg + (size_t)c->M_cap * h : nullptr;
 
@@ -1081,10 +1062,10 @@ int rel_table(mc_ctx* c, mc_batch* b, const StepPlan& sp, const double* t_ref) {
   if (!same_tab) {
     b->rel_offsets_valid = false;
     if (!b->d_roff) {
-      if (int r = dev_alloc(&b->d_roff, (size_t)F + 1)) return r;
-      if (int r = dev_alloc(&b->d_relw, (size_t)F)) return r;
-      if (int r = dev_alloc(&b->d_tref, (size_t)F)) return r;
-      if (int r = dev_alloc(&b->d_refpose, 7 * (size_t)F)) return r;
+      if (int r = b->d_roff.alloc((size_t)F + 1)) return r;
+      if (int r = b->d_relw.alloc((size_t)F)) return r;
+      if (int r = b->d_tref.alloc((size_t)F)) return r;
+      if (int r = b->d_refpose.alloc(7 * (size_t)F)) return r;
     }
     ra.width = b->d_relw;
     hipLaunchKernelGGL(k_rel_count, dim3((F + kBlock - 1) / kBlock), dim3(kBlock), 0, s, ra);
@@ -1097,12 +1078,9 @@ int rel_table(mc_ctx* c, mc_batch* b, const StepPlan& sp, const double* t_ref) {
       if (w[f] < 1 || (int64_t)w[f] > sp.pa.nseg) return fail(MC_ERR_HIP, "relative table: window of frame %d", f);
       roff[f + 1] = roff[f] + w[f];
     }
-    if ((size_t)roff[F] > b->rel_cap) {
-      if (int r = sync_all(c)) return r;
-      dev_free(b->d_rel);
-      b->rel_cap = 0;
-      if (int r = dev_alloc(&b->d_rel, (size_t)roff[F])) return r;
-      b->rel_cap = (size_t)roff[F];
+    if ((size_t)roff[F] > b->d_rel.capacity()) {
+      if (int r = sync_all(c)) return r;   // the row stream may still read the old table
+      if (int r = ctx_reserve(c, b->d_rel, (size_t)roff[F])) return r;
     }
     HIPCHK(hipMemcpyAsync(b->d_roff, roff.data(), roff.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -1267,21 +1245,15 @@ static int seg64_table(mc_ctx* c, int mode, int64_t* nseg_out) {
   const size_t seg_b = (size_t)nseg * (mode == MC_MODE_POSE_SLERP ? sizeof(PoseSeg) : sizeof(ImuSeg));
   if (c->d_seg64 && c->seg64_mode == mode && c->seg64_ver == ver) return MC_OK;
   c->seg64_mode = -1;
-  if (seg_b > c->seg64_bytes) {
-    if (c->d_seg64) (void)hipFree(c->d_seg64);
-    c->d_seg64 = nullptr;
-    c->seg64_bytes = 0;
-    HIPCHK(hipMalloc(&c->d_seg64, seg_b));
-    c->seg64_bytes = seg_b;
-  }
+  if (int r = ctx_reserve(c, c->d_seg64, seg_b)) return r;
   PrepArgs pa;
   std::memset(&pa, 0, sizeof(pa));
   pa.mode = mode;
   pa.n_frames = 0;
   pa.time = c->d_time; pa.pos = c->d_pos; pa.rpy = c->d_rpy; pa.T = c->T;
   pa.imu_ts = c->d_imu_ts; pa.gyro = c->d_gyro; pa.M = c->M;
-  pa.pose_seg = static_cast<PoseSeg*>(c->d_seg64);
-  pa.imu_seg = static_cast<ImuSeg*>(c->d_seg64);
+  pa.pose_seg = c->d_seg64.as<PoseSeg>();
+  pa.imu_seg = c->d_seg64.as<ImuSeg>();
   pa.nseg = nseg;
   const uint32_t blocks = (uint32_t)(((nseg + 63) / 64 + 3) / 4);
   hipLaunchKernelGGL(k_prep, dim3(blocks), dim3(kBlock), 0, s, pa);
@@ -1342,8 +1314,8 @@ static int points_f64(mc_ctx* c, int mode, bool relative, int32_t F, const int64
   a.doff = sc.at<const int64_t>(w_doff); a.F = F;
   a.ftime = sc.at<const double>(w_fv);
   a.fstart = sc.at<const int64_t>(w_fv);
-  a.pose_time = c->d_time; a.pose_seg = static_cast<const PoseSeg*>(c->d_seg64); a.nseg = nseg;
-  a.imu_ts = c->d_imu_ts; a.imu_seg = static_cast<const ImuSeg*>(c->d_seg64);
+  a.pose_time = c->d_time; a.pose_seg = c->d_seg64.as<PoseSeg>(); a.nseg = nseg;
+  a.imu_ts = c->d_imu_ts; a.imu_seg = c->d_seg64.as<ImuSeg>();
   a.ntab = mode == MC_MODE_POSE_SLERP ? c->T : c->M;
   a.out = sc.at<double>(w_out);
   {
@@ -1390,7 +1362,7 @@ int mc_pose_at(mc_ctx* c, int64_t n, const double* t, double* R, double* pos) {
   RowScratch sc;
   if (int r = sc.open(c, n, words)) return r;
   if (int r = sc.put(0, t, (size_t)n)) return r;
-  PoseAtArgs a = pose_at_args(c, static_cast<const PoseSeg*>(c->d_seg64), nseg, sc.at<const double>(0), n);
+  PoseAtArgs a = pose_at_args(c, c->d_seg64.as<PoseSeg>(), nseg, sc.at<const double>(0), n);
   a.R = sc.at<double>(w_R); a.pos = sc.at<double>(w_pos);
   hipLaunchKernelGGL(k_pose_at, dim3(sc.grid(n)), dim3(kBlock), 0, c->stream, a);
   HIPCHK(hipGetLastError());
@@ -1432,13 +1404,13 @@ static int row_pipeline(mc_ctx* c, const double* const* frames, const int64_t* l
   double t_in = 0, t_out = 0, t_wait_in = 0, t_wait_out = 0;
   auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t_start = now();
-  if (!c->h_pipe) HIPCHK(hipHostMalloc(&c->h_pipe, 4 * kPipeBytes, hipHostMallocDefault));
-  if (!c->d_pipe) HIPCHK(hipMalloc(&c->d_pipe, 4 * kPipeBytes));
+  if (!c->h_pipe) if (int r = c->h_pipe.alloc(4 * kPipeBytes)) return r;
+  if (!c->d_pipe) if (int r = c->d_pipe.alloc(4 * kPipeBytes)) return r;
   double* pin[4];
   double* dev[4];
   for (int k = 0; k < 4; ++k) {
-    pin[k] = reinterpret_cast<double*>(static_cast<char*>(c->h_pipe) + k * kPipeBytes);
-    dev[k] = reinterpret_cast<double*>(static_cast<char*>(c->d_pipe) + k * kPipeBytes);
+    pin[k] = reinterpret_cast<double*>(c->h_pipe + k * kPipeBytes);
+    dev[k] = reinterpret_cast<double*>(c->d_pipe + k * kPipeBytes);
   }
   struct Events {   // destroyed on every return
     hipEvent_t e[6] = {};
@@ -1682,11 +1654,11 @@ int mc_set_environment(mc_ctx* c, int64_t n, const double* env, int64_t ld) {
   if (int r = sync_all(c)) return r;
   ++c->env_ver;              // any earlier mc_scan_count's state is now stale
   c->scan_valid = false;
-  dev_free(c->d_env);
+  c->d_env.reset();
   c->E = 0;
   // scan.hpp's column layout: x, y, z, intensity float64, transposed here once per scene
   const size_t words = scene_words(n);
-  if (int r = dev_alloc(&c->d_env, std::max<size_t>(words, 1))) return r;
+  if (int r = c->d_env.alloc(std::max<size_t>(words, 1))) return r;
   if (n > 0) {
     std::vector<double> h(words);
     for (int64_t i = 0; i < n; ++i) {
@@ -1713,15 +1685,15 @@ int mc_scan_count(mc_ctx* c, int32_t F, const double* frame_times, int pose_sele
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
   const int32_t tiles = (int32_t)((c->E + kScanTile - 1) / kScanTile);
-  dev_free(c->d_scan_pose); dev_free(c->d_scan_tcount); dev_free(c->d_scan_toff);
-  dev_free(c->d_scan_nvis);
+  c->d_scan_pose.reset(); c->d_scan_tcount.reset(); c->d_scan_toff.reset();
+  c->d_scan_nvis.reset();
   c->scan_F = 0;
   c->scan_valid = false;
-  if (int r = dev_alloc(&c->d_scan_pose, 12 * (size_t)std::max(F, 1))) return r;
+  if (int r = c->d_scan_pose.alloc(12 * (size_t)std::max(F, 1))) return r;
   const int32_t Fp = scan_fpad(F);   // per-tile rows of counts / offsets, frames padded to kScanFrames
-  if (int r = dev_alloc(&c->d_scan_tcount, (size_t)std::max(Fp, 1) * std::max(tiles, 1))) return r;
-  if (int r = dev_alloc(&c->d_scan_toff, (size_t)std::max(Fp, 1) * std::max(tiles, 1))) return r;
-  if (int r = dev_alloc(&c->d_scan_nvis, std::max(F, 1))) return r;
+  if (int r = c->d_scan_tcount.alloc((size_t)std::max(Fp, 1) * std::max(tiles, 1))) return r;
+  if (int r = c->d_scan_toff.alloc((size_t)std::max(Fp, 1) * std::max(tiles, 1))) return r;
+  if (int r = c->d_scan_nvis.alloc(std::max(F, 1))) return r;
   c->scan_par[0] = params[0];
   c->scan_par[1] = params[1] * params[1];   // LMC:715 max_range_sq
   c->scan_par[2] = params[2] / 2;           // LMC:740
@@ -1744,12 +1716,7 @@ int mc_scan_count(mc_ctx* c, int32_t F, const double* frame_times, int pose_sele
   if (tiles > 0) {
     const ScanParams sp = make_scan_params(c->scan_par, cap);
     const size_t words = (size_t)tiles * ((F + kScanFrames - 1) / kScanFrames) * kBlock;
-    if (words > c->scan_bits_cap) {
-      dev_free(c->d_scan_bits);
-      c->scan_bits_cap = 0;
-      if (int r = dev_alloc(&c->d_scan_bits, words)) return r;
-      c->scan_bits_cap = words;
-    }
+    if (int r = ctx_reserve(c, c->d_scan_bits, words)) return r;
     {
       TimedRegion tr(c, &c->scan_ev, c->stream);
       const uint32_t units = (uint32_t)tiles * (uint32_t)((F + kScanFrames - 1) / kScanFrames);
@@ -1861,10 +1828,10 @@ int mc_set_ray_scene(mc_ctx* c, int32_t n_objects, const int64_t* counts, const 
   if (int r = sync_all(c)) return r;
   ++c->ray_scene_ver;        // any earlier mc_ray_count's result is now stale
   c->ray_valid = false;
-  dev_free(c->d_ray_scene); dev_free(c->d_ray_obj);
+  c->d_ray_scene.reset(); c->d_ray_obj.reset();
   c->ray_E = 0;
-  if (int r = dev_alloc(&c->d_ray_scene, std::max<size_t>(scene_words(n), 1))) return r;
-  if (int r = dev_alloc(&c->d_ray_obj, std::max<size_t>((size_t)n, 1))) return r;
+  if (int r = c->d_ray_scene.alloc(std::max<size_t>(scene_words(n), 1))) return r;
+  if (int r = c->d_ray_obj.alloc(std::max<size_t>((size_t)n, 1))) return r;
   if (n > 0) {
     std::vector<double> h(scene_words(n));
     std::vector<int32_t> ho((size_t)n);
@@ -1898,12 +1865,11 @@ int mc_ray_count(mc_ctx* c, int32_t F, const double* origins, const double* R, i
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
   c->ray_valid = false;
-  dev_free(c->d_ray_frame); dev_free(c->d_ray_dirs); dev_free(c->d_ray_steps);
-  if (c->d_ray_hit) { (void)hipFree(c->d_ray_hit); c->d_ray_hit = nullptr; }
-  if (int r = dev_alloc(&c->d_ray_frame, 12 * (size_t)std::max(F, 1))) return r;
-  if (int r = dev_alloc(&c->d_ray_dirs, 3 * (size_t)std::max(n_rays, 1))) return r;
-  if (int r = dev_alloc(&c->d_ray_steps, (size_t)std::max(n_steps, 1))) return r;
-  HIPCHK(hipMalloc(&c->d_ray_hit, std::max<size_t>((size_t)NR, 1) * sizeof(RayHit)));
+  c->d_ray_frame.reset(); c->d_ray_dirs.reset(); c->d_ray_steps.reset(); c->d_ray_hit.reset();
+  if (int r = c->d_ray_frame.alloc(12 * (size_t)std::max(F, 1))) return r;
+  if (int r = c->d_ray_dirs.alloc(3 * (size_t)std::max(n_rays, 1))) return r;
+  if (int r = c->d_ray_steps.alloc((size_t)std::max(n_steps, 1))) return r;
+  if (int r = c->d_ray_hit.alloc(std::max<size_t>((size_t)NR, 1) * sizeof(RayHit))) return r;
   c->ray_F = F; c->ray_n = n_rays; c->ray_K = n_steps;
   c->ray_counts.assign(F, 0);
   c->ray_hits.assign(3 * (size_t)NR, -1);
@@ -1929,24 +1895,19 @@ int mc_ray_count(mc_ctx* c, int32_t F, const double* origins, const double* R, i
   const int32_t chunk_tiles = (n_tiles + n_chunks - 1) / n_chunks;
   n_chunks = (n_tiles + chunk_tiles - 1) / chunk_tiles;
   const size_t part_bytes = (size_t)NR * n_chunks * sizeof(RayKey);
-  if (part_bytes > c->ray_part_bytes) {
-    if (c->d_ray_part) { (void)hipFree(c->d_ray_part); c->d_ray_part = nullptr; }
-    c->ray_part_bytes = 0;
-    HIPCHK(hipMalloc(&c->d_ray_part, part_bytes));
-    c->ray_part_bytes = part_bytes;
-  }
+  if (int r = ctx_reserve(c, c->d_ray_part, part_bytes)) return r;
   RayCountArgs a;
   a.scene = c->d_ray_scene; a.E = c->ray_E; a.obj = c->d_ray_obj;
   a.frame = c->d_ray_frame; a.dirs = c->d_ray_dirs; a.n_rays = n_rays;
   a.steps = c->d_ray_steps; a.m = make_ray_march(steps, n_steps, step_size);
   a.F = F; a.n_groups = (int32_t)units; a.n_chunks = n_chunks;
   a.chunk_pts = (int64_t)chunk_tiles * kRayTile;
-  a.partial = static_cast<RayKey*>(c->d_ray_part);
+  a.partial = c->d_ray_part.as<RayKey>();
   {
     TimedRegion tr(c, &c->ray_ev, c->stream);
     hipLaunchKernelGGL(k_ray_count, dim3((uint32_t)(units * n_chunks)), dim3(kBlock), 0, c->stream, a);
     hipLaunchKernelGGL(k_ray_merge, dim3((uint32_t)((NR + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                       a.partial, NR, n_chunks, static_cast<RayHit*>(c->d_ray_hit));
+                       a.partial, NR, n_chunks, c->d_ray_hit.as<RayHit>());
   }
   HIPCHK(hipGetLastError());
   std::vector<RayHit> hit((size_t)NR);
@@ -2004,7 +1965,7 @@ static int ray_emit(mc_ctx* c, mc_batch* out, const double* rinv, const double* 
   std::memset(&ea, 0, sizeof(ea));
   ea.scene = c->d_ray_scene; ea.E = c->ray_E;
   ea.frame = c->d_ray_frame; ea.rinv = d_rinv; ea.dirs = c->d_ray_dirs; ea.n_rays = c->ray_n;
-  ea.steps = c->d_ray_steps; ea.hit = static_cast<const RayHit*>(c->d_ray_hit);
+  ea.steps = c->d_ray_steps; ea.hit = c->d_ray_hit.as<RayHit>();
   ea.noise = noise ? d_noise : nullptr;
   ea.doff = d_doff;
   if (out) {

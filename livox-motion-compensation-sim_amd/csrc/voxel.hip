@@ -1,11 +1,8 @@
 // voxel.hip — host side of the voxel-grid filter (include/mcdeskew.h mc_voxel_*; kernels in voxel.hpp).
 //
 // The filter's state (the key table, the per-point slots, the per-voxel sums and what the last build
-// left for its emits) belongs to a context but is kept here, in a table of this file keyed by the
-// context, not in mc_ctx: the deskew and codec translation units do not see it and compile to the
-// objects they were.  mc_voxel_release frees it; an entry whose context has gone (the handles
-// mc_create made for it — both streams and the span pool — no longer all match) is dropped at the
-// next look-up.  mc_ctx carries no serial number to compare instead.
+// left for its emits) hangs from the context as its CtxExt (internal.hpp): the deskew and codec
+// translation units see only that hook.  mc_voxel_release frees it early; mc_destroy frees what is left.
 #include "../../include/mcdeskew.h"
 #include "voxel.hpp"
 #include "internal.hpp"
@@ -13,8 +10,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <mutex>
-#include <unordered_map>
 
 using namespace mc;
 
@@ -22,71 +17,33 @@ namespace {
 
 enum { kInsert = 0, kRank = 1, kAccumulate = 2, kFinalise = 3, kPhases = 4 };
 
-struct VoxState {
-  // the owner's handles when the entry was made (mc_create's: main stream, row stream, span pool)
-  hipStream_t stream = nullptr, row_d2h = nullptr;
-  const void* span = nullptr;
-  bool owned_by(const mc_ctx* c) const { return stream == c->stream && row_d2h == c->row_d2h && span == c->d_span; }
-  int device = 0;
-  // table (cap slots), per-point arrays (n_cap points / chunks), per-voxel records (m_cap voxels)
-  unsigned long long* keys = nullptr;
-  uint32_t* first = nullptr;
-  uint32_t* vid = nullptr;
-  size_t cap_alloc = 0;
-  uint32_t* slot = nullptr;
-  uint32_t* vslot = nullptr;
-  uint8_t* flags = nullptr;
-  uint32_t* chunk = nullptr;
-  size_t n_alloc = 0;
-  long long* sums = nullptr;
-  uint32_t* cnt = nullptr;
-  size_t m_alloc = 0;
-  uint32_t* meta = nullptr;
+struct VoxState : mcimpl::CtxExt {
+  // table (a power of two of slots), per-point arrays (points / chunks), per-voxel records
+  DevBuf<unsigned long long> keys;
+  DevBuf<uint32_t> first, vid;
+  DevBuf<uint32_t> slot, vslot;
+  DevBuf<uint8_t> flags;
+  DevBuf<uint32_t> chunk;
+  DevBuf<long long> sums;
+  DevBuf<uint32_t> cnt;
+  DevBuf<uint32_t> meta;
   // the last build
   bool built = false;
   int64_t M = 0;
   double h = 0.0, o[3] = {0, 0, 0};
   EventPairs ev[kPhases];
 
-  void free_buffers() {
-    dev_free(keys); dev_free(first); dev_free(vid); dev_free(slot); dev_free(vslot); dev_free(flags);
-    dev_free(chunk); dev_free(sums); dev_free(cnt); dev_free(meta);
-    cap_alloc = n_alloc = m_alloc = 0;
-    built = false;
+  // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
+  ~VoxState() override {
+    for (auto& v : ev)
+      for (auto& p : v) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
   }
 };
 
-std::mutex g_mu;
-std::unordered_map<mc_ctx*, VoxState> g_states;
-
-// the context's entry (made on demand); an entry left by a destroyed context at the same address
-// gives its buffers back first
+// the context's state (made on demand)
 VoxState* state_of(mc_ctx* c, bool create) {
-  std::lock_guard<std::mutex> l(g_mu);
-  auto it = g_states.find(c);
-  if (it != g_states.end() && !it->second.owned_by(c)) {
-    DeviceGuard g(it->second.device);
-    it->second.free_buffers();
-    for (auto& v : it->second.ev)
-      for (auto& p : v) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
-    g_states.erase(it);
-    it = g_states.end();
-  }
-  if (it == g_states.end()) {
-    if (!create) return nullptr;
-    it = g_states.emplace(c, VoxState()).first;
-    it->second.stream = c->stream;
-    it->second.row_d2h = c->row_d2h;
-    it->second.span = c->d_span;
-    it->second.device = c->device;
-  }
-  return &it->second;
-}
-
-template <typename T>
-int grow(mc_ctx* c, T** p, size_t n) {
-  if (*p) { HIPCHK(hipStreamSynchronize(c->stream)); dev_free(*p); }
-  return dev_alloc(p, n);
+  if (!c->voxel && create) c->voxel.reset(new VoxState());
+  return static_cast<VoxState*>(c->voxel.get());
 }
 
 int check_grid(double voxel, const double* origin) {
@@ -111,22 +68,14 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   while (((int64_t)1 << log2cap) < 2 * n) ++log2cap;   // n < 2^31: at most 2^32 slots
   const size_t cap = (size_t)1 << log2cap;
   const int64_t n_chunks = (n + kVoxChunk - 1) / kVoxChunk;
-  if (!s->meta) if (int r = dev_alloc(&s->meta, 2)) return r;
-  if (cap > s->cap_alloc) {
-    s->cap_alloc = 0;
-    if (int r = grow(c, &s->keys, cap)) return r;
-    if (int r = grow(c, &s->first, cap)) return r;
-    if (int r = grow(c, &s->vid, cap)) return r;
-    s->cap_alloc = cap;
-  }
-  if ((size_t)n > s->n_alloc) {
-    s->n_alloc = 0;
-    if (int r = grow(c, &s->slot, (size_t)n)) return r;
-    if (int r = grow(c, &s->vslot, (size_t)n)) return r;
-    if (int r = grow(c, &s->flags, (size_t)n_chunks * kVoxBlock)) return r;
-    if (int r = grow(c, &s->chunk, (size_t)n_chunks)) return r;
-    s->n_alloc = (size_t)n;
-  }
+  if (!s->meta) if (int r = s->meta.alloc(2)) return r;
+  if (int r = ctx_reserve(c, s->keys, cap)) return r;
+  if (int r = ctx_reserve(c, s->first, cap)) return r;
+  if (int r = ctx_reserve(c, s->vid, cap)) return r;
+  if (int r = ctx_reserve(c, s->slot, (size_t)n)) return r;
+  if (int r = ctx_reserve(c, s->vslot, (size_t)n)) return r;
+  if (int r = ctx_reserve(c, s->flags, (size_t)n_chunks * kVoxBlock)) return r;
+  if (int r = ctx_reserve(c, s->chunk, (size_t)n_chunks)) return r;
   VoxTable t;
   t.keys = s->keys; t.first = s->first; t.vid = s->vid; t.slot = s->slot;
   t.shift = 64 - log2cap;
@@ -157,12 +106,8 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   }
   const int64_t M = (int64_t)meta[1];
   if (M < 1 || M > n) return fail(MC_ERR_STATE, "voxel build: %lld voxels of %lld points", (long long)M, (long long)n);
-  if ((size_t)M > s->m_alloc) {
-    s->m_alloc = 0;
-    if (int r = grow(c, &s->sums, kVoxRec * (size_t)M)) return r;
-    if (int r = grow(c, &s->cnt, (size_t)M)) return r;
-    s->m_alloc = (size_t)M;
-  }
+  if (int r = ctx_reserve(c, s->sums, kVoxRec * (size_t)M)) return r;
+  if (int r = ctx_reserve(c, s->cnt, (size_t)M)) return r;
   {
     TimedRegion tr(c, &s->ev[kAccumulate], c->stream);
     HIPCHK(hipMemsetAsync(s->sums, 0, kVoxRec * (size_t)M * sizeof(long long), c->stream));
@@ -305,10 +250,8 @@ int mc_voxel_release(mc_ctx* c) {
   if (!s) return MC_OK;
   DeviceGuard g(c->device);
   (void)sync_all(c);
-  s->free_buffers();
   for (auto& v : s->ev) ev_recycle(c, v);
-  std::lock_guard<std::mutex> l(g_mu);
-  g_states.erase(c);
+  c->voxel.reset();
   return MC_OK;
 }
 

@@ -34,8 +34,9 @@ def _release(fn, ctx, *args):
 
 
 def _destroy(lib, handle):
-    """Finalizer of a context: the voxel filter's scratch (kept outside mc_ctx, csrc/voxel.hip), then the
-    context itself.  A library loaded from ``lib_path`` may predate the filter."""
+    """Finalizer of a context: the voxel filter's scratch, then the context itself.  mc_destroy frees
+    that scratch too; the call before it is for a library loaded from ``lib_path`` that keeps the
+    scratch outside the context (or predates the filter)."""
     release = getattr(lib, "mc_voxel_release", None)
     if release is not None:
         release(handle)

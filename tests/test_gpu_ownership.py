@@ -1,0 +1,191 @@
+"""Who frees device memory: every block a context, a batch or the voxel filter allocates is owned by a
+DevBuf (csrc/devbuf.hpp) and counted by mc_device_memory_live, so "destroying the handle frees
+everything" is an equality of two readings.  The blocks mc_device_alloc hands out (DeviceBuffer) are the
+caller's and are not in the account."""
+import ctypes
+import gc
+
+import numpy as np
+import pytest
+
+import voxel as V
+from conftest import pkg
+
+pytestmark = pytest.mark.gpu
+
+CFG = dict(range_max=90.0, range_min=0.5, fov_horizontal=70.4, fov_vertical=77.2, lidar_range_noise=0.0)
+
+
+def live(m):
+    b, k = m._lib.c_int64(-1), m._lib.c_int64(-1)
+    m._lib.check(m._lib.load().mc_device_memory_live(ctypes.byref(b), ctypes.byref(k)), "device_memory_live")
+    return b.value, k.value
+
+
+def fresh_context(m):
+    """A context of this test's own whose handle the test destroys itself (no finalizer)."""
+    ctx = m.Context(0)
+    ctx._fin.detach()
+    return ctx
+
+
+def destroy_only(m, ctx):
+    m._lib.check(ctx.lib.mc_destroy(ctx.handle), "mc_destroy")
+
+
+def table(n, seed):
+    """n poses over 0.1 s per step, and n IMU samples over the same span"""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n) * 0.1
+    pos = np.cumsum(rng.uniform(0.0, 0.3, (n, 3)), axis=0)
+    rpy = np.cumsum(rng.uniform(-0.02, 0.02, (n, 3)), axis=0)
+    ts = (t * 1e9).astype(np.int64)
+    gyro = rng.uniform(-0.2, 0.2, (n, 3))
+    return t, pos, rpy, ts, gyro
+
+
+def cloud_rows(n, seed, spread=20.0):
+    rng = np.random.default_rng(seed)
+    r = np.column_stack([rng.uniform(-spread, spread, (n, 3)), rng.uniform(0.0, 255.0, n)])
+    return r.astype(np.float32).astype(np.float64)
+
+
+def ray_count(m, ctx, F, n_rays, seed):
+    rng = np.random.default_rng(seed)
+    pos = np.ascontiguousarray(rng.uniform(-1.0, 1.0, (F, 3)))
+    R = np.ascontiguousarray(np.tile(np.eye(3), (F, 1, 1)))
+    d = rng.normal(size=(n_rays, 3))
+    dirs = np.ascontiguousarray(d / np.linalg.norm(d, axis=1, keepdims=True))
+    steps = np.ascontiguousarray(np.arange(1, 41) * 0.5)
+    counts = np.zeros(F, np.int64)
+    p, cd, ci = m._lib.ptr, m._lib.c_double, m._lib.c_int64
+    m._lib.check(ctx.lib.mc_ray_count(ctx.handle, F, p(pos, cd), p(R, cd), n_rays, p(dirs, cd), len(steps), p(steps, cd),
+                                      0.5, p(counts, ci)), "ray_count")
+
+
+def test_destroy_alone_frees_all_a_context_can_own():
+    m = pkg()
+    lib, p, cd, ci = m._lib.load(), m._lib.ptr, m._lib.c_double, m._lib.c_int64
+    gc.collect()
+    start = live(m)
+    ctx = fresh_context(m)
+    assert live(m) > start   # the launch-span pool of mc_create
+
+    for n in (8, 16):        # the second upload outgrows the first
+        t, pos, rpy, ts, gyro = table(n, n)
+        ctx.set_trajectory(t, pos, rpy)
+        ctx.set_imu(ts, gyro)
+
+    counts = [300, 0, 5]
+    N = sum(counts)
+    rows = cloud_rows(N, 1)
+    t_ns = np.random.default_rng(2).integers(0, 90_000_000, N).astype(np.int32)
+    inp = ctx.batch(counts, with_time=True, with_pcd_len=True)
+    out = ctx.batch(counts, with_time=True, with_pcd_len=True)
+    plain = ctx.batch(counts, with_time=True)        # an output without its own text sums (mc_deskew_pcd's scratch)
+    inp.upload_aos(rows)
+    inp.upload_time(t_ns)
+    inp.set_frame_times(np.array([0.2, 0.5, 0.9]))
+    inp.set_frame_starts(np.array([200_000_000, 500_000_000, 900_000_000], np.int64))
+    for mode in ("frame", "pose_slerp", "imu"):
+        ctx.deskew(inp, out, mode=mode)
+    ctx.deskew(inp, out, mode="pose_slerp", reference="start")
+    ctx.deskew(inp, out, mode="pose_slerp", reference=np.array([0.25, 0.55, 0.85]))
+    ctx.sync()
+
+    t64 = t_ns.astype(np.int64)
+    m.runtime.deskew_points_f64(ctx, "pose_slerp", counts, rows, t64, frame_times=[0.2, 0.5, 0.9])
+    m.runtime.deskew_points_f64(ctx, "imu", counts, rows, t64, frame_start_ns=[200_000_000, 500_000_000, 900_000_000])
+
+    rot, trans = np.array([0.1, -0.2, 0.3]), np.array([1.0, 2.0, 3.0])
+    for n in (10, 1 << 15):   # pinned zero-copy scratch, then the device staging buffer
+        pts = cloud_rows(n, 3)
+        res = np.empty((n, 4))
+        m._lib.check(lib.mc_transform_pointcloud_f64(ctx.handle, p(pts, cd), n, 4, p(rot, cd), p(trans, cd), p(res, cd)),
+                     "transform_pointcloud")
+
+    for E in (600, 5000):     # the larger scene outgrows the visibility words
+        ctx.set_environment(cloud_rows(E, 4 + E, spread=30.0))
+        ctx.scan([0.2, 0.5, 0.9], dict(CFG, points_per_frame=200)).close()
+
+    objs = cloud_rows(300, 5, spread=8.0)
+    oc = np.array([150, 150], np.int64)
+    m._lib.check(lib.mc_set_ray_scene(ctx.handle, 2, p(oc, ci), p(objs, cd), 4), "set_ray_scene")
+    for n_rays in (64, 512):  # the per-chunk keys grow with the rays
+        ray_count(m, ctx, 2, n_rays, n_rays)
+
+    m.codecs.encode_pcd_batch(out)
+    m.codecs.encode_lvx_batch(out, [1, 2, 3], [0.2, 0.5, 0.9])
+    m.codecs.deskew_pcd_frames(inp, plain, mode="pose_slerp")
+
+    for n in (300, 5000):     # left unreleased: mc_destroy has to free it
+        assert m.voxel_downsample(cloud_rows(n, 6), 0.5, context=ctx).n_voxels > 0
+
+    for b in (inp, out, plain):
+        b.close()
+    gc.collect()              # batches this test dropped on the way
+    assert live(m) > start
+    destroy_only(m, ctx)
+    assert live(m) == start
+
+
+def test_batch_frees_its_relative_tables():
+    m = pkg()
+    ctx = fresh_context(m)
+    t, pos, rpy, _, _ = table(12, 7)
+    ctx.set_trajectory(t, pos, rpy)
+    counts = [257, 3]
+
+    def relative_pair():
+        inp = ctx.batch(counts, with_time=True)
+        out = ctx.batch(counts, with_time=True)
+        inp.upload_aos(cloud_rows(sum(counts), 8))
+        inp.upload_time(np.random.default_rng(9).integers(0, 300_000_000, sum(counts)).astype(np.int32))
+        inp.set_frame_times(np.array([0.3, 0.6]))
+        made = live(m)
+        ctx.deskew(inp, out, mode="pose_slerp", reference="start")
+        ctx.sync()
+        assert live(m)[1] == made[1] + 5    # d_roff, d_relw, d_tref, d_refpose and the records
+        inp.close()
+        out.close()
+
+    relative_pair()          # the context's own staging scratch is allocated by now
+    gc.collect()
+    before = live(m)
+    relative_pair()
+    assert live(m) == before
+    destroy_only(m, ctx)
+
+
+def test_voxel_state_is_per_context_and_dies_with_it():
+    m = pkg()
+    lib = m._lib.load()
+    gc.collect()
+    start = live(m)
+    rows = cloud_rows(700, 10)
+    a = fresh_context(m)
+    assert m.voxel_downsample(rows, 0.5, context=a).n_voxels > 0
+    destroy_only(m, a)
+    assert live(m) == start
+    # a new context, at A's address or not, has no build and no timed launches
+    b = fresh_context(m)
+    assert lib.mc_voxel_emit_f64(b.handle, None, None, None) == m._lib.MC_ERR_STATE
+    ms = np.zeros(4)
+    n = m._lib.c_int64(-1)
+    m._lib.check(lib.mc_timing_read_voxel(b.handle, m._lib.ptr(ms, m._lib.c_double), ctypes.byref(n)), "timing_read_voxel")
+    assert n.value == 0 and not ms.any()
+    # release frees early, twice is fine, and the next build is a whole one
+    idle = live(m)
+    assert m.voxel_downsample(rows, 0.5, context=b).n_voxels > 0
+    assert live(m) > idle
+    m._lib.check(lib.mc_voxel_release(b.handle), "voxel_release")
+    assert live(m) == idle
+    assert lib.mc_voxel_emit_f64(b.handle, None, None, None) == m._lib.MC_ERR_STATE
+    m._lib.check(lib.mc_voxel_release(b.handle), "voxel_release (again)")
+    want = V.downsample(rows, 0.5)
+    cloud = m.voxel_downsample(rows, 0.5, context=b)
+    assert cloud.n_voxels == len(want["rows"])
+    assert np.array_equal(cloud.keys(), want["keys"]) and np.array_equal(cloud.point_counts(), want["counts"])
+    assert np.array_equal(cloud.rows().view(np.uint64), want["rows"].view(np.uint64))
+    destroy_only(m, b)
+    assert live(m) == start

@@ -8,8 +8,12 @@ AddressSanitizer + UndefinedBehaviorSanitizer and exercised here, no GPU needed.
   shards, every root.
 * ``pcd_formatter_host``: the device ``%.6f`` line writers (codecs.hpp), as in
   ``test_pcd_formatter_host.py``, now under the sanitizers.
+* ``devbuf_host``: the owning device buffer (``csrc/devbuf.hpp``) with malloc / free behind its
+  allocation seam: growth, injected allocation failures, moves, partial construction, and the live
+  account that ``mc_device_memory_live`` reports; leaks are errors.
 """
 import os
+import re
 import shutil
 import subprocess
 
@@ -48,3 +52,30 @@ def test_pcd_formatter_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     assert "bad 0" in r.stdout
     assert "runtime error" not in r.stderr, r.stderr[-3000:]
+
+
+@needs_gxx
+def test_devbuf_host_under_asan_ubsan(tmp_path):
+    exe = tmp_path / "devbuf_host"
+    subprocess.run(["g++", *SAN, "-DMC_DEVBUF_HOST_TEST", f"-I{CSRC}", os.path.join(ROOT, "tests", "host", "devbuf_host.cpp"),
+                    "-o", str(exe)], check=True, capture_output=True, text=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300, env=ENV)
+    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
+    assert "bad 0" in r.stdout
+    assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+
+
+def test_device_memory_live_exported_and_abi_unchanged():
+    from conftest import pkg
+    m = pkg()
+    lib = m._lib.load()
+    hdr = open(os.path.join(ROOT, "include", "mcdeskew.h")).read()
+    declared = set(re.findall(r"^\s*int\s+(mc_\w+)\s*\(", hdr, flags=re.M))
+    name = "mc_device_memory_live"
+    assert name in declared and name in m._lib.EXPORTED and hasattr(lib, name)
+    assert re.search(r"^#define MC_ABI_VERSION 1$", hdr, flags=re.M) and lib.mc_abi_version() == 1
+    # no context, so nothing of the library's is allocated; either output may be NULL
+    b, k = m._lib.c_int64(-1), m._lib.c_int64(-1)
+    assert lib.mc_device_memory_live(m._lib.ctypes.byref(b), m._lib.ctypes.byref(k)) == m._lib.MC_OK
+    assert b.value >= 0 and k.value >= 0
+    assert lib.mc_device_memory_live(None, None) == m._lib.MC_OK
