@@ -29,12 +29,14 @@ def check_cloud(cloud, want, what):
     return b
 
 
-def both_sources(ctx, counts, rows, h, origin=(0.0, 0.0, 0.0), what=""):
-    """rows: (N, 4) float64 holding float32 values, frame-major.  -> (restatement, last cloud)"""
+def both_sources(ctx, counts, rows, h, origin=(0.0, 0.0, 0.0), what="", want=None):
+    """rows: (N, 4) float64 holding float32 values, frame-major; want: V.downsample(rows, h, origin) where
+    the caller has it already.  -> (restatement, last cloud)"""
     m = pkg()
     rows = np.ascontiguousarray(rows, np.float64)
     assert np.array_equal(rows, rows.astype(np.float32).astype(np.float64))
-    want = V.downsample(rows, h, origin)
+    if want is None:
+        want = V.downsample(rows, h, origin)
     b = ctx.batch(counts)
     b.upload_columns(*[rows[:, c].astype(np.float32) for c in range(4)])
     check_cloud(ctx.voxel_downsample(b, h, origin), want, f"{what} (batch)")
