@@ -22,12 +22,25 @@ using namespace mc;
 
 namespace {
 
+// The codecs' state in the context (its codec slot, internal.hpp): made by the first call that needs it.
+struct CodecState : mcimpl::CtxExt {
+  // per-call frame / unit tables carved from one scratch buffer, error flag
+  DevBuf<char> scratch;
+  DevBuf<int> err;
+  // mc_deskew_pcd: ASCII PCD text bytes per 256-point output block, written by the deskew kernel
+  DevBuf<int32_t> pcd_len;
+  EventPairs ev;
+  ~CodecState() override { ev_destroy(ev); }
+};
+CodecState& codec_of(mc_ctx* c) { return *ctx_ext<CodecState>(c, mcimpl::kSlotCodec, true); }
+
 int codec_scratch(mc_ctx* c, size_t bytes, char** out) {
-  if (int r = ctx_reserve(c, c->d_codec, bytes)) return r;
-  if (!c->d_codec_err) {
-    if (int r = c->d_codec_err.alloc(1)) return r;
+  CodecState& s = codec_of(c);
+  if (int r = ctx_reserve(c, s.scratch, bytes)) return r;
+  if (!s.err) {
+    if (int r = s.err.alloc(1)) return r;
   }
-  *out = c->d_codec;
+  *out = s.scratch;
   return MC_OK;
 }
 
@@ -160,7 +173,7 @@ int lvx_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, c
   uint8_t hdr[kLvxFileHdr];
   lvx_file_header(hdr);
   HIPCHK(hipMemcpyAsync(d_out, hdr, kLvxFileHdr, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_codec_err, 0, sizeof(int), c->stream));
+  HIPCHK(hipMemsetAsync(codec_of(c).err, 0, sizeof(int), c->stream));
 
   LvxArgs a;
   a.src = frames_of(src, reinterpret_cast<const int64_t*>(d + o_doff), reinterpret_cast<const int64_t*>(d + o_unit),
@@ -170,10 +183,10 @@ int lvx_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, c
   a.ts_ns = reinterpret_cast<const uint64_t*>(d + o_ts);
   a.has_int = has_int ? reinterpret_cast<const uint8_t*>(d + o_hi) : nullptr;
   a.out = static_cast<char*>(d_out);
-  a.err = c->d_codec_err;
+  a.err = codec_of(c).err;
   a.order = src.batch ? src.batch->hot_order ^ 1 : 0;   // start where the last kernel over the batch ended
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     // frame headers: each frame's first unit writes its own, so this launch only when a frame has no
     // points (and therefore no unit)
     const bool empty_frame = std::any_of(counts, counts + F, [](int64_t n) { return n == 0; });
@@ -187,7 +200,7 @@ int lvx_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, c
   }
   HIPCHK(hipGetLastError());
   int err = 0;
-  HIPCHK(hipMemcpyAsync(&err, c->d_codec_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&err, codec_of(c).err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (err) return fail(MC_ERR_INVALID, "cannot convert float NaN to integer (NaN coordinate or intensity)");
   return MC_OK;
@@ -229,11 +242,11 @@ int mc_deskew_pcd(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
   }
   // one text-byte slot per 256-point block of the output batch (= one PCD tile)
   const int64_t blocks = out->P / kBlkPts;
-  if (int r = ctx_reserve(c, c->d_pcd_len, (size_t)blocks)) return r;
-  if (int r = mcimpl::deskew_call(c, in, out, mode, pose_select, blocks > 0 ? c->d_pcd_len.get() : nullptr)) return r;
+  if (int r = ctx_reserve(c, codec_of(c).pcd_len, (size_t)blocks)) return r;
+  if (int r = mcimpl::deskew_call(c, in, out, mode, pose_select, blocks > 0 ? codec_of(c).pcd_len.get() : nullptr)) return r;
   Source src;
   src.batch = out;
-  return pcd_encode(c, src, out->F, out->counts.data(), d_out, out_bytes, body_pos, c->d_pcd_len);
+  return pcd_encode(c, src, out->F, out->counts.data(), d_out, out_bytes, body_pos, codec_of(c).pcd_len);
 }
 
 }  // extern "C"
@@ -268,14 +281,14 @@ int pcd_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, v
   char* d = nullptr;
   if (int r = codec_scratch(c, blob.size(), &d)) return r;
   HIPCHK(hipMemcpyAsync(d, blob.data(), o_tb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_codec_err, 0, sizeof(int), c->stream));
+  HIPCHK(hipMemsetAsync(codec_of(c).err, 0, sizeof(int), c->stream));
   PcdArgs a;
   a.src = frames_of(src, reinterpret_cast<const int64_t*>(d + o_doff), reinterpret_cast<const int64_t*>(d + o_unit),
                     F, n_tiles);
   a.tile_bytes = reinterpret_cast<int32_t*>(d + o_tb);
   a.tile_pos = reinterpret_cast<const int64_t*>(d + o_tp);
   a.out = static_cast<char*>(d_out);
-  a.err = c->d_codec_err;
+  a.err = codec_of(c).err;
   // batch source: each pass starts where the previous kernel over the batch ended (stream_unit);
   // fused (d_measured): the write pass follows the deskew kernel directly
   const int hot = src.batch ? src.batch->hot_order : 1;
@@ -292,7 +305,7 @@ int pcd_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, v
   if (!measured) {
     a.worder = a.morder ^ 1;
     {
-      TimedRegion tr(c, &c->codec_ev, c->stream);
+      TimedRegion tr(c, &codec_of(c).ev, c->stream);
       const int per = a.src.cols ? kPcdMeasureTiles : kPcdTilesPerWG;   // tiles per measure workgroup
       const dim3 mgrid((uint32_t)((n_tiles + per - 1) / per));
       if (a.src.cols) hipLaunchKernelGGL(k_pcd_measure<true>, mgrid, dim3(kPcdBlock), 0, c->stream, a);
@@ -312,7 +325,7 @@ int pcd_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, v
         HIPCHK(hipMemcpyAsync(d_list, flagged.data(), flagged.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                               c->stream));
         {
-          TimedRegion tr(c, &c->codec_ev, c->stream);
+          TimedRegion tr(c, &codec_of(c).ev, c->stream);
           hipLaunchKernelGGL(k_pcd_measure_list, dim3((uint32_t)flagged.size()), dim3(kPcdBlock), 0, c->stream, a,
                              (const int32_t*)d_list);
         }
@@ -323,7 +336,7 @@ int pcd_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, v
     }
   }
   int err = 0;
-  HIPCHK(hipMemcpyAsync(&err, c->d_codec_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&err, codec_of(c).err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (err) return fail(MC_ERR_INVALID, "a value has |v| >= 2^107, beyond the device %%.6f formatter");
   // tiles holding a line outside the packed path (kPcdSlowTile) go to the byte-path kernel
@@ -345,7 +358,7 @@ int pcd_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, v
   HIPCHK(hipMemcpyAsync(d + o_tp, tpos.data(), tpos.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   const dim3 grid((uint32_t)((n_tiles + kPcdWriteTiles - 1) / kPcdWriteTiles));
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     if (a.src.cols) hipLaunchKernelGGL(k_pcd_write<true>, grid, dim3(kPcdBlock), 0, c->stream, a);
     else hipLaunchKernelGGL(k_pcd_write<false>, grid, dim3(kPcdBlock), 0, c->stream, a);
   }
@@ -356,7 +369,7 @@ int pcd_encode(mc_ctx* c, const Source& src, int32_t F, const int64_t* counts, v
     // (same stream); the byte path reads no tile bytes
     HIPCHK(hipMemcpyAsync(a.tile_bytes, slow.data(), slow.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                           c->stream));
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     hipLaunchKernelGGL(k_pcd_write_bytes, dim3((uint32_t)slow.size()), dim3(kPcdBlock), 0, c->stream, a,
                        (const int32_t*)a.tile_bytes);
   }
@@ -463,7 +476,7 @@ int csim_lvx_encode(mc_ctx* c, int version, const Source& src, int32_t F, const 
   uint8_t hdr[kCsimLvx2FileHdr];
   const int hb = csim_file_header(ver, F, dv, hdr);
   HIPCHK(hipMemcpyAsync(d_out, hdr, hb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_codec_err, 0, sizeof(int), c->stream));
+  HIPCHK(hipMemsetAsync(codec_of(c).err, 0, sizeof(int), c->stream));
 
   CsimLvxArgs a;
   a.src = csim_src(src, frames_of(src, reinterpret_cast<const int64_t*>(d + o_doff),
@@ -471,9 +484,9 @@ int csim_lvx_encode(mc_ctx* c, int version, const Source& src, int32_t F, const 
   a.frame_pos = reinterpret_cast<const int64_t*>(d + o_pos);
   a.ts_ns = reinterpret_cast<const uint64_t*>(d + o_ts);
   a.out = static_cast<char*>(d_out);
-  a.err = c->d_codec_err;
+  a.err = codec_of(c).err;
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     const bool empty_frame = std::any_of(counts, counts + F, [](int64_t n) { return n == 0; });
     const dim3 fgrid((F + kCodecBlock - 1) / kCodecBlock), ugrid((uint32_t)n_units), blk(kCodecBlock);
     if (F > 0 && empty_frame) {
@@ -487,7 +500,7 @@ int csim_lvx_encode(mc_ctx* c, int version, const Source& src, int32_t F, const 
   }
   HIPCHK(hipGetLastError());
   int err = 0;
-  HIPCHK(hipMemcpyAsync(&err, c->d_codec_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&err, codec_of(c).err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (err)
     return fail(MC_ERR_INVALID, ver == 1 ? "a coordinate overflows float32, or an intensity is NaN or outside 0..255"
@@ -527,7 +540,7 @@ int csim_text_encode(mc_ctx* c, int format, const Source& src, int32_t F, const 
   char* d = nullptr;
   if (int r = codec_scratch(c, blob.size(), &d)) return r;
   HIPCHK(hipMemcpyAsync(d, blob.data(), o_tb, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemsetAsync(c->d_codec_err, 0, sizeof(int), c->stream));
+  HIPCHK(hipMemsetAsync(codec_of(c).err, 0, sizeof(int), c->stream));
   CsimTextArgs a;
   a.src = csim_src(src, frames_of(src, reinterpret_cast<const int64_t*>(d + o_doff),
                                   reinterpret_cast<const int64_t*>(d + o_unit), F, n_tiles), nullptr);
@@ -535,10 +548,10 @@ int csim_text_encode(mc_ctx* c, int format, const Source& src, int32_t F, const 
   a.tile_bytes = reinterpret_cast<int32_t*>(d + o_tb);
   a.tile_pos = reinterpret_cast<const int64_t*>(d + o_tp);
   a.out = static_cast<char*>(d_out);
-  a.err = c->d_codec_err;
+  a.err = codec_of(c).err;
   const dim3 grid((uint32_t)n_tiles), blk(kPcdBlock);
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     if (line.ncols == 3) hipLaunchKernelGGL(k_csim_text_measure<3>, grid, blk, 0, c->stream, a);
     else hipLaunchKernelGGL(k_csim_text_measure<5>, grid, blk, 0, c->stream, a);
   }
@@ -546,7 +559,7 @@ int csim_text_encode(mc_ctx* c, int format, const Source& src, int32_t F, const 
   std::vector<int32_t> tb((size_t)n_tiles);
   int err = 0;
   HIPCHK(hipMemcpyAsync(tb.data(), a.tile_bytes, tb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(&err, c->d_codec_err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(&err, codec_of(c).err, sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   if (err) return fail(MC_ERR_INVALID, "a value has |v| >= 2^107, beyond the device %%.6f / %%.0f formatters");
   std::vector<int64_t> tpos((size_t)n_tiles);
@@ -561,7 +574,7 @@ int csim_text_encode(mc_ctx* c, int format, const Source& src, int32_t F, const 
   CHECK_ARG(d_out, "d_out is NULL");
   HIPCHK(hipMemcpyAsync(d + o_tp, tpos.data(), tpos.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     if (line.ncols == 3) hipLaunchKernelGGL(k_csim_text_write<3>, grid, blk, 0, c->stream, a);
     else hipLaunchKernelGGL(k_csim_text_write<5>, grid, blk, 0, c->stream, a);
   }
@@ -685,7 +698,7 @@ int lvx_decode(mc_ctx* c, int format, const void* d_file, int64_t bytes, int32_t
   a.tags = d_tags;
   const dim3 grid((uint32_t)n_units), blk(kCodecBlock);
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     if (out) {
       if (format == MC_LVX_V11) hipLaunchKernelGGL((k_lvx_decode<0, true>), grid, blk, 0, c->stream, a);
       else if (format == MC_CSIM_LVX_LEGACY) hipLaunchKernelGGL((k_lvx_decode<1, true>), grid, blk, 0, c->stream, a);
@@ -716,7 +729,7 @@ int text_count(mc_ctx* c, const void* d_text, int64_t bytes, std::vector<int64_t
   char* d = nullptr;
   if (int r = codec_scratch(c, (size_t)T * sizeof(int32_t), &d)) return r;
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     hipLaunchKernelGGL(k_text_count, dim3((uint32_t)T), dim3(kPcdBlock), 0, c->stream, static_cast<const char*>(d_text),
                        bytes, reinterpret_cast<int32_t*>(d));
   }
@@ -786,7 +799,7 @@ int text_decode(mc_ctx* c, int sep, int32_t n_cols, const void* d_text, int64_t 
   if (with_t && frame_start_ns)
     if (int r = mc_batch_set_frame_start_ns(out, frame_start_ns)) return r;
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     hipLaunchKernelGGL(k_text_starts, dim3((uint32_t)T), dim3(kPcdBlock), 0, c->stream, a.text, bytes,
                        reinterpret_cast<const int64_t*>(d + o_off), reinterpret_cast<int64_t*>(d + o_st));
     if (with_t && !frame_start_ns && out->F > 0)
@@ -872,7 +885,7 @@ int mc_lvx_count(mc_ctx* c, int format, const void* d_file, int64_t bytes, int32
   if (int r = codec_scratch(c, o_cnt + (size_t)F * 8, &d)) return r;
   HIPCHK(hipMemcpyAsync(d, frame_pos, ((size_t)F + 1) * 8, hipMemcpyHostToDevice, c->stream));
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     hipLaunchKernelGGL(k_lvx_trim, dim3((F + 3) / 4), dim3(kCodecBlock), 0, c->stream,
                        static_cast<const uint8_t*>(d_file), reinterpret_cast<const int64_t*>(d), F,
                        reinterpret_cast<int64_t*>(d + o_cnt));
@@ -981,7 +994,7 @@ int las_encode(mc_ctx* c, const Source& src, int64_t n, const LasWrite& p, void*
     const dim3 grid((uint32_t)tiles), blk(kCodecBlock);
     const dim3 rgrid((uint32_t)std::min<int64_t>((tiles + kCodecBlock - 1) / kCodecBlock, kLasReduceGrid));
     {
-      TimedRegion tr(c, &c->codec_ev, c->stream);
+      TimedRegion tr(c, &codec_of(c).ev, c->stream);
       if (src.batch) hipLaunchKernelGGL(k_las_encode<true>, grid, blk, 0, c->stream, a);
       else hipLaunchKernelGGL(k_las_encode<false>, grid, blk, 0, c->stream, a);
       hipLaunchKernelGGL(k_las_minmax, rgrid, blk, 0, c->stream, (const int32_t*)a.tile_mm, tiles,
@@ -1051,7 +1064,7 @@ int las_decode(mc_ctx* c, const void* d_file, int64_t bytes, int fmt, int64_t re
   a.bad = reinterpret_cast<unsigned long long*>(d);
   const dim3 grid((uint32_t)((n + kLasDecTile - 1) / kLasDecTile)), blk(kLasDecTile);
   {
-    TimedRegion tr(c, &c->codec_ev, c->stream);
+    TimedRegion tr(c, &codec_of(c).ev, c->stream);
     if (out && !frame_start_ns)
       hipLaunchKernelGGL(k_las_frame_start, dim3((out->F + kCodecBlock - 1) / kCodecBlock), dim3(kCodecBlock), 0,
                          c->stream, a);
@@ -1153,9 +1166,7 @@ extern "C" {
 
 int mc_timing_read_codec(mc_ctx* c, double* ms, int64_t* n) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  return sum_events(c, c->codec_ev, ms, n);
+  return read_timing(c, codec_of(c).ev, ms, n);
 }
 
 }  // extern "C"

@@ -163,3 +163,26 @@ static inline int sum_events(mc_ctx* c, EventPairs& v, double* ms, int64_t* n) {
   ev_recycle(c, v);
   return MC_OK;
 }
+
+// a mc_timing_read_* of one list: total ms and launches since the last read
+static inline int read_timing(mc_ctx* c, EventPairs& v, double* ms, int64_t* n) {
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  return sum_events(c, v, ms, n);
+}
+
+// ------------------------------------------------------------------------------------------------
+// a feature's state in its slot of the context (internal.hpp CtxExt)
+// ------------------------------------------------------------------------------------------------
+// the unit's state S (nullptr: none yet and !create)
+template <typename S>
+static inline S* ctx_ext(mc_ctx* c, mcimpl::CtxSlot slot, bool create) {
+  auto& p = c->ext[slot];
+  if (!p && create) p.reset(new S());
+  return static_cast<S*>(p.get());
+}
+// in a state's destructor: its timing pairs nobody read (the context's pool is not its to fill then)
+static inline void ev_destroy(EventPairs& v) {
+  for (auto& p : v) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+  v.clear();
+}

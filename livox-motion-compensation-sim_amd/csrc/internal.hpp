@@ -1,4 +1,7 @@
-// internal.hpp — the opaque handles of include/mcdeskew.h (shared by mcdeskew.hip and comm.cpp).
+// internal.hpp — the opaque handles of include/mcdeskew.h, shared by every translation unit of the
+// library: mcdeskew.hip (the context, the batches, the deskew paths and, for now, the host side of the
+// two scanners), comm.cpp, codecs.hip and voxel.hip.  What only one feature reads — the scanners', the
+// codecs' and the voxel filter's state — is not here: it sits in that feature's slot of the context.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>
@@ -92,9 +95,10 @@ struct CtxQueues {
 };
 using EventPairs = std::vector<std::pair<hipEvent_t, hipEvent_t>>;
 
-// State another translation unit keeps in a context (voxel.hip): destroyed with the context's buffers,
-// before the event pool and the streams.
+// State a feature's translation unit keeps in a context, one slot each (hostutil.hpp ctx_ext): only that
+// unit defines the type.  Destroyed with the context's buffers, before the event pool and the streams.
 struct CtxExt { virtual ~CtxExt() = default; };
+enum CtxSlot { kSlotVoxel, kSlotScan, kSlotRay, kSlotCodec, kCtxSlots };
 }  // namespace mcimpl
 using mcimpl::DevBuf;
 using mcimpl::EventPairs;
@@ -147,46 +151,6 @@ struct mc_ctx : mcimpl::CtxQueues {
   DevBuf<int64_t> d_imu_ts;
   DevBuf<double> d_gyro;
   DevBuf<mc::ImuSeg> d_imu_seg;        // 2 * M_cap (double buffer)
-  // scan_environment state (LMC:701-770): scene, per-frame f64 poses, per-(frame, tile) counts
-  int64_t E = 0;
-  DevBuf<double> d_env;   // the scene as columns (scan.hpp scene_cols)
-  int32_t scan_F = 0, scan_tiles = 0;
-  DevBuf<double> d_scan_pose;
-  DevBuf<int32_t> d_scan_tcount;
-  DevBuf<int64_t> d_scan_toff;
-  DevBuf<int64_t> d_scan_nvis;
-  DevBuf<uint32_t> d_scan_bits;       // pass-1 visibility words
-  std::vector<int64_t> scan_counts;   // final per-frame counts of the last mc_scan_count
-  double scan_par[4] = {0, 0, 0, 0};  // range_min, range_max^2, fov_h/2, fov_v/2
-  int64_t scan_cap = 0;
-  // the visibility words / tile offsets above describe the scene of version scan_env_ver; a pass 2
-  // on any other scene is refused (the poses were copied to d_scan_pose by the count itself)
-  uint64_t env_ver = 0, scan_env_ver = 0;
-  bool scan_valid = false;
-  EventPairs scan_ev;
-  // ray-march scanner state (CSIM:1011-1146, raymarch.hpp): the scene of point objects as columns
-  // plus each point's object, then what the last mc_ray_count left for its emit
-  int64_t ray_E = 0;
-  DevBuf<double> d_ray_scene;               // x, y, z, intensity columns
-  DevBuf<int32_t> d_ray_obj;                // object (list position) of every scene point
-  std::vector<int64_t> ray_obj_start;       // first scene index of every object (n_objects + 1)
-  uint64_t ray_scene_ver = 0, ray_count_ver = 0;
-  bool ray_valid = false;
-  int32_t ray_F = 0, ray_n = 0, ray_K = 0;
-  DevBuf<double> d_ray_frame;               // per frame: origin (3), R (9)
-  DevBuf<double> d_ray_dirs;
-  DevBuf<double> d_ray_steps;
-  DevBuf<char> d_ray_part;                  // per-chunk keys (RayKey) of the count pass
-  DevBuf<char> d_ray_hit;                   // RayHit per (frame, ray)
-  std::vector<int64_t> ray_counts;          // hits per frame of the last mc_ray_count
-  std::vector<int32_t> ray_hits;            // (F * n_rays, 3): step, object, point index in the object
-  EventPairs ray_ev;
-  // output codecs: per-call frame / unit tables carved from one scratch buffer, error flag
-  DevBuf<char> d_codec;
-  DevBuf<int> d_codec_err;
-  EventPairs codec_ev;
-  // mc_deskew_pcd: ASCII PCD text bytes per 256-point output block, written by the deskew kernel
-  DevBuf<int32_t> d_pcd_len;
   // segment table of the float64 per-point path (mc_deskew_points_f64): built by k_prep for one mode
   // and the trajectory / IMU upload it came from (seg64_ver), rebuilt when either changes
   DevBuf<char> d_seg64;
@@ -209,8 +173,9 @@ struct mc_ctx : mcimpl::CtxQueues {
   DevBuf<unsigned long long> d_span;
   int32_t span_used = 0;
   EventPairs main_ev, prep_ev, layout_ev;
-  // the voxel-grid filter's state (voxel.hip; freed early by mc_voxel_release)
-  std::unique_ptr<mcimpl::CtxExt> voxel;
+  // the features' own state, made on demand by their units (the voxel filter's is freed early by
+  // mc_voxel_release).  The last member: destroyed first.
+  std::unique_ptr<mcimpl::CtxExt> ext[mcimpl::kCtxSlots];
 };
 
 struct mc_batch {

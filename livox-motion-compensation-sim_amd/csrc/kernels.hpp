@@ -25,6 +25,7 @@
 #include <limits.h>
 #include <type_traits>
 
+#include "block.hpp"
 #include "layout.hpp"
 #include "relfold.hpp"
 
@@ -45,7 +46,7 @@ constexpr int kStorePol = 2;       // st_pol policy of the deskew kernels' outpu
 constexpr int kPointsWaves = 4;    // __launch_bounds__ waves / SIMD of k_deskew_points
 constexpr int kFastMaxW = 2;       // frames spanning <= this many segments take the SGPR (no-LDS) path
 
-constexpr int kBlock = 256;                    // 4 waves of 64
+// kBlock (256 threads, 4 waves of 64) is in block.hpp
 constexpr int kIters = 2;                      // float4 groups per thread per tile (k_affine_w)
 constexpr int kTileGroups = kBlock * kIters;   // 512 groups = 2048 points per tile
 constexpr int kSub = kTileGroups / kBlock;     // per-point modes: sub-tiles of kBlock groups
@@ -1018,27 +1019,7 @@ __global__ __launch_bounds__(kBlock) void k_deskew_frame(const DeskewArgs a) {
 // Path A with the ASCII PCD text bytes of every output block (mc_deskew_pcd)
 __global__ __launch_bounds__(kBlock) void k_deskew_frame_pcd(const DeskewArgs a) { deskew_frame_quad<true>(a, 0u); }
 
-// ---- float64 rows: the reference's own arrays, bit for bit ---------------------------------------
-// R p + t (LMC:775: (R @ p.T).T + t) the way numpy's matmul accumulates it: per output an ascending
-// FMA chain over k, fma(R[i][2], z, fma(R[i][1], y, R[i][0] * x)), then + t[i] rounded on its own
-// (numpy's dgemm, measured on the reference's box: tools/fma_order.py).  P = {R row-major | t}; with
-// the host's scipy-faithful R (rot.cpp) the result equals the reference's float64 value exactly.
-// A one-point frame is a matrix-vector product for numpy (its dgemv), which accumulates
-// fma(R[i][2], z, fma(R[i][0], x, R[i][1] * y)) instead (tools/fma_order.py, single-row cases): `single`.
-__device__ __forceinline__ void frame_apply(const double* __restrict__ P, double x, double y, double z, double& ox,
-                                            double& oy, double& oz, bool single = false) {
-#pragma clang fp contract(off)
-  if (single) {
-    ox = __builtin_fma(P[2], z, __builtin_fma(P[0], x, P[1] * y)) + P[9];
-    oy = __builtin_fma(P[5], z, __builtin_fma(P[3], x, P[4] * y)) + P[10];
-    oz = __builtin_fma(P[8], z, __builtin_fma(P[6], x, P[7] * y)) + P[11];
-  } else {
-    ox = __builtin_fma(P[2], z, __builtin_fma(P[1], y, P[0] * x)) + P[9];
-    oy = __builtin_fma(P[5], z, __builtin_fma(P[4], y, P[3] * x)) + P[10];
-    oz = __builtin_fma(P[8], z, __builtin_fma(P[7], y, P[6] * x)) + P[11];
-  }
-}
-
+// ---- float64 rows: the reference's own arrays, bit for bit (frame_apply: block.hpp) ---------------
 // the frame of row `row`: last f with doff[f] <= row
 __device__ __forceinline__ int32_t row_frame(const int64_t* __restrict__ doff, int32_t F, int64_t row) {
   int32_t lo = 0, hi = F;

@@ -129,11 +129,60 @@ static void with_mode(int mode, F&& f) {
   else f(std::integral_constant<int, MC_MODE_IMU>{});
 }
 
-// The recorded timing pairs go back to the pool; the members then free every buffer, and the base the
-// pooled events and the two streams.
+// The context's own recorded timing pairs go back to the pool; the members then free the features'
+// states (with their pairs) and every buffer, and the base the pooled events and the two streams.
 mc_ctx::~mc_ctx() {
-  for (EventPairs* v : {&codec_ev, &main_ev, &scan_ev, &ray_ev, &prep_ev, &layout_ev}) ev_recycle(this, *v);
+  for (EventPairs* v : {&main_ev, &prep_ev, &layout_ev}) ev_recycle(this, *v);
 }
+
+// The two scanners' states are CtxExts in their slots of the context, as the codecs' and the voxel
+// filter's are; their host code stays in this unit for now ("The scanners' unit").
+// scan_environment's state (LMC:701-770): scene, per-frame f64 poses, per-(frame, tile) counts
+struct ScanState : mcimpl::CtxExt {
+  int64_t E = 0;
+  DevBuf<double> d_env;   // the scene as columns (block.hpp scene_cols)
+  int32_t F = 0, tiles = 0;
+  DevBuf<double> d_pose;
+  DevBuf<int32_t> d_tcount;
+  DevBuf<int64_t> d_toff;
+  DevBuf<int64_t> d_nvis;
+  DevBuf<uint32_t> d_bits;       // pass-1 visibility words
+  std::vector<int64_t> counts;   // final per-frame counts of the last mc_scan_count
+  double par[4] = {0, 0, 0, 0};  // range_min, range_max^2, fov_h/2, fov_v/2
+  int64_t cap = 0;
+  // the visibility words / tile offsets above describe the scene of version count_env_ver; a pass 2
+  // on any other scene is refused (the poses were copied to d_pose by the count itself)
+  uint64_t env_ver = 0, count_env_ver = 0;
+  bool valid = false;
+  EventPairs ev;
+  ~ScanState() override { ev_destroy(ev); }
+};
+
+static ScanState& scan_state(mc_ctx* c) { return *ctx_ext<ScanState>(c, mcimpl::kSlotScan, true); }
+
+// the ray-march scanner's state (CSIM:1011-1146, raymarch.hpp), the CtxExt in the context's ray slot:
+// the scene of point objects as columns plus each point's object, then what the last mc_ray_count
+// left for its emit
+struct RayState : mcimpl::CtxExt {
+  int64_t E = 0;
+  DevBuf<double> d_scene;               // x, y, z, intensity columns
+  DevBuf<int32_t> d_obj;                // object (list position) of every scene point
+  std::vector<int64_t> obj_start;       // first scene index of every object (n_objects + 1)
+  uint64_t scene_ver = 0, count_ver = 0;
+  bool valid = false;
+  int32_t F = 0, n = 0, K = 0;
+  DevBuf<double> d_frame;               // per frame: origin (3), R (9)
+  DevBuf<double> d_dirs;
+  DevBuf<double> d_steps;
+  DevBuf<char> d_part;                  // per-chunk keys (RayKey) of the count pass
+  DevBuf<char> d_hit;                   // RayHit per (frame, ray)
+  std::vector<int64_t> counts;          // hits per frame of the last mc_ray_count
+  std::vector<int32_t> hits;            // (F * n_rays, 3): step, object, point index in the object
+  EventPairs ev;
+  ~RayState() override { ev_destroy(ev); }
+};
+
+static RayState& ray_state(mc_ctx* c) { return *ctx_ext<RayState>(c, mcimpl::kSlotRay, true); }
 
 // ------------------------------------------------------------------------------------------------
 extern "C" {
@@ -1652,23 +1701,24 @@ int mc_set_environment(mc_ctx* c, int64_t n, const double* env, int64_t ld) {
   CHECK_ARG(n == 0 || env, "scene pointer is NULL");
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
-  ++c->env_ver;              // any earlier mc_scan_count's state is now stale
-  c->scan_valid = false;
-  c->d_env.reset();
-  c->E = 0;
+  ScanState& s = scan_state(c);
+  ++s.env_ver;              // any earlier mc_scan_count's state is now stale
+  s.valid = false;
+  s.d_env.reset();
+  s.E = 0;
   // scan.hpp's column layout: x, y, z, intensity float64, transposed here once per scene
   const size_t words = scene_words(n);
-  if (int r = c->d_env.alloc(std::max<size_t>(words, 1))) return r;
+  if (int r = s.d_env.alloc(std::max<size_t>(words, 1))) return r;
   if (n > 0) {
     std::vector<double> h(words);
     for (int64_t i = 0; i < n; ++i) {
       const double* q = env + i * ld;
       h[i] = q[0]; h[n + i] = q[1]; h[2 * n + i] = q[2]; h[3 * n + i] = q[3];
     }
-    HIPCHK(hipMemcpyAsync(c->d_env, h.data(), words * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s.d_env, h.data(), words * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
-  c->E = n;
+  s.E = n;
   return MC_OK;
 }
 
@@ -1684,57 +1734,58 @@ int mc_scan_count(mc_ctx* c, int32_t F, const double* frame_times, int pose_sele
   CHECK_ARG(pose_select == MC_POSE_DIRECT || F == 0 || frame_times, "frame times are NULL");
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
-  const int32_t tiles = (int32_t)((c->E + kScanTile - 1) / kScanTile);
-  c->d_scan_pose.reset(); c->d_scan_tcount.reset(); c->d_scan_toff.reset();
-  c->d_scan_nvis.reset();
-  c->scan_F = 0;
-  c->scan_valid = false;
-  if (int r = c->d_scan_pose.alloc(12 * (size_t)std::max(F, 1))) return r;
+  ScanState& s = scan_state(c);
+  const int32_t tiles = (int32_t)((s.E + kScanTile - 1) / kScanTile);
+  s.d_pose.reset(); s.d_tcount.reset(); s.d_toff.reset();
+  s.d_nvis.reset();
+  s.F = 0;
+  s.valid = false;
+  if (int r = s.d_pose.alloc(12 * (size_t)std::max(F, 1))) return r;
   const int32_t Fp = scan_fpad(F);   // per-tile rows of counts / offsets, frames padded to kScanFrames
-  if (int r = c->d_scan_tcount.alloc((size_t)std::max(Fp, 1) * std::max(tiles, 1))) return r;
-  if (int r = c->d_scan_toff.alloc((size_t)std::max(Fp, 1) * std::max(tiles, 1))) return r;
-  if (int r = c->d_scan_nvis.alloc(std::max(F, 1))) return r;
-  c->scan_par[0] = params[0];
-  c->scan_par[1] = params[1] * params[1];   // LMC:715 max_range_sq
-  c->scan_par[2] = params[2] / 2;           // LMC:740
-  c->scan_par[3] = params[3] / 2;           // LMC:741
-  c->scan_cap = cap;
-  c->scan_counts.assign(F, 0);
-  c->scan_F = F;
-  c->scan_tiles = tiles;
-  c->scan_env_ver = c->env_ver;
+  if (int r = s.d_tcount.alloc((size_t)std::max(Fp, 1) * std::max(tiles, 1))) return r;
+  if (int r = s.d_toff.alloc((size_t)std::max(Fp, 1) * std::max(tiles, 1))) return r;
+  if (int r = s.d_nvis.alloc(std::max(F, 1))) return r;
+  s.par[0] = params[0];
+  s.par[1] = params[1] * params[1];   // LMC:715 max_range_sq
+  s.par[2] = params[2] / 2;           // LMC:740
+  s.par[3] = params[3] / 2;           // LMC:741
+  s.cap = cap;
+  s.counts.assign(F, 0);
+  s.F = F;
+  s.tiles = tiles;
+  s.count_env_ver = s.env_ver;
   if (F == 0) {
-    c->scan_valid = true;
+    s.valid = true;
     return MC_OK;
   }
   // per-frame sensor pose {R | t} (LMC:804-812; R as scipy computes it, LMC:726), host-side
   std::vector<double> pose(12 * (size_t)F);
   mcrot::frame_poses(c->h_time.data(), c->h_pos.data(), c->h_rpy.data(), c->T, frame_times, F, pose_select,
                      pose.data());
-  HIPCHK(hipMemcpyAsync(c->d_scan_pose, pose.data(), pose.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.d_pose, pose.data(), pose.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   std::vector<int64_t> nvis(F, 0), toff((size_t)Fp * std::max(tiles, 1), 0);
   if (tiles > 0) {
-    const ScanParams sp = make_scan_params(c->scan_par, cap);
+    const ScanParams sp = make_scan_params(s.par, cap);
     const size_t words = (size_t)tiles * ((F + kScanFrames - 1) / kScanFrames) * kBlock;
-    if (int r = ctx_reserve(c, c->d_scan_bits, words)) return r;
+    if (int r = ctx_reserve(c, s.d_bits, words)) return r;
     {
-      TimedRegion tr(c, &c->scan_ev, c->stream);
+      TimedRegion tr(c, &s.ev, c->stream);
       const uint32_t units = (uint32_t)tiles * (uint32_t)((F + kScanFrames - 1) / kScanFrames);
-      hipLaunchKernelGGL(k_scan_count, dim3(units), dim3(kBlock), 0, c->stream, c->d_env, c->E, tiles,
-                         c->d_scan_pose, F, sp, c->d_scan_tcount, c->d_scan_bits);
+      hipLaunchKernelGGL(k_scan_count, dim3(units), dim3(kBlock), 0, c->stream, s.d_env, s.E, tiles,
+                         s.d_pose, F, sp, s.d_tcount, s.d_bits);
     }
     HIPCHK(hipGetLastError());
     std::vector<int32_t> tc((size_t)Fp * tiles);
-    HIPCHK(hipMemcpyAsync(tc.data(), c->d_scan_tcount, tc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(tc.data(), s.d_tcount, tc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     for (int32_t t = 0; t < tiles; ++t) {   // tile-major rows: the frames' running sums side by side
       const size_t row = (size_t)t * Fp;
       for (int32_t f = 0; f < F; ++f) { toff[row + f] = nvis[f]; nvis[f] += tc[row + f]; }
     }
-    HIPCHK(hipMemcpyAsync(c->d_scan_toff, toff.data(), toff.size() * sizeof(int64_t), hipMemcpyHostToDevice,
+    HIPCHK(hipMemcpyAsync(s.d_toff, toff.data(), toff.size() * sizeof(int64_t), hipMemcpyHostToDevice,
                           c->stream));
   }
-  HIPCHK(hipMemcpyAsync(c->d_scan_nvis, nvis.data(), F * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.d_nvis, nvis.data(), F * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int32_t f = 0; f < F; ++f) {
     // LMC:757-762: every (n // cap)-th visible point, at most cap of them
@@ -1744,37 +1795,38 @@ int mc_scan_count(mc_ctx* c, int32_t F, const double* frame_times, int pose_sele
       const int64_t step = n / cap;
       k = std::min<int64_t>(cap, (n + step - 1) / step);
     }
-    c->scan_counts[f] = k;
+    s.counts[f] = k;
     counts_out[f] = k;
   }
-  c->scan_valid = true;
+  s.valid = true;
   return MC_OK;
 }
 
 // pass 2 of the last mc_scan_count: the batch's float32 columns (out != nullptr) or the reference's
 // float64 rows (local, aligned: device (N, 4) arrays, aligned may be nullptr)
 static int scan_emit(mc_ctx* c, mc_batch* out, const double* noise, double* d_local, double* d_aligned) {
-  if (!c->scan_valid || c->scan_env_ver != c->env_ver)
+  ScanState& s = scan_state(c);
+  if (!s.valid || s.count_env_ver != s.env_ver)
     return fail(MC_ERR_STATE, "no mc_scan_count for the current scene (mc_set_environment since the count?)");
   std::vector<int64_t> doff;
-  if (int r = frame_offsets(c->scan_counts.data(), c->scan_F, &doff)) return r;
-  const int64_t N = doff[c->scan_F];
-  if (c->scan_F == 0 || N == 0 || c->scan_tiles == 0) return MC_OK;
+  if (int r = frame_offsets(s.counts.data(), s.F, &doff)) return r;
+  const int64_t N = doff[s.F];
+  if (s.F == 0 || N == 0 || s.tiles == 0) return MC_OK;
   DeviceGuard g(c->device);
   // staging: [noise (N, 3) | doff (F + 1)] (the rows path has no batch offsets of its own)
   const size_t noise_w = noise ? 3 * (size_t)N : 0;
   void* st = nullptr;
-  if (int r = ctx_stage(c, (noise_w + (size_t)c->scan_F + 1) * 8, &st)) return r;
+  if (int r = ctx_stage(c, (noise_w + (size_t)s.F + 1) * 8, &st)) return r;
   double* d_noise = noise ? static_cast<double*>(st) : nullptr;
   int64_t* d_doff = reinterpret_cast<int64_t*>(static_cast<double*>(st) + noise_w);
   if (noise) HIPCHK(hipMemcpyAsync(d_noise, noise, noise_w * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if (!out) HIPCHK(hipMemcpyAsync(d_doff, doff.data(), doff.size() * 8, hipMemcpyHostToDevice, c->stream));
   ScanEmitArgs ea;
   std::memset(&ea, 0, sizeof(ea));
-  ea.env = c->d_env; ea.E = c->E; ea.n_tiles = c->scan_tiles;
-  ea.pose = c->d_scan_pose; ea.F = c->scan_F;
-  ea.sp = make_scan_params(c->scan_par, c->scan_cap);
-  ea.tile_off = c->d_scan_toff; ea.nvis = c->d_scan_nvis; ea.vis_bits = c->d_scan_bits; ea.noise = d_noise;
+  ea.env = s.d_env; ea.E = s.E; ea.n_tiles = s.tiles;
+  ea.pose = s.d_pose; ea.F = s.F;
+  ea.sp = make_scan_params(s.par, s.cap);
+  ea.tile_off = s.d_toff; ea.nvis = s.d_nvis; ea.vis_bits = s.d_bits; ea.noise = d_noise;
   if (out) {
     ea.poff = out->d_poff; ea.doff = out->d_doff; ea.cols = out->d_cols; ea.C = out->C;
     out->wrote(false);
@@ -1784,8 +1836,8 @@ static int scan_emit(mc_ctx* c, mc_batch* out, const double* noise, double* d_lo
     ea.doff = d_doff; ea.local = d_local; ea.aligned = d_aligned;
   }
   {
-    TimedRegion tr(c, &c->scan_ev, c->stream);
-    const uint32_t units = (uint32_t)c->scan_tiles * (uint32_t)((c->scan_F + kScanFrames - 1) / kScanFrames);
+    TimedRegion tr(c, &s.ev, c->stream);
+    const uint32_t units = (uint32_t)s.tiles * (uint32_t)((s.F + kScanFrames - 1) / kScanFrames);
     if (out) hipLaunchKernelGGL(k_scan_emit<false>, dim3(units), dim3(kBlock), 0, c->stream, ea);
     else hipLaunchKernelGGL(k_scan_emit<true>, dim3(units), dim3(kBlock), 0, c->stream, ea);
   }
@@ -1798,7 +1850,7 @@ static int scan_emit(mc_ctx* c, mc_batch* out, const double* noise, double* d_lo
 int mc_scan_emit(mc_ctx* c, mc_batch* out, const double* noise) {
   CHECK_ARG(c && out, "NULL argument");
   CHECK_ARG(out->ctx == c, "batch belongs to another context");
-  if (out->counts != c->scan_counts)
+  if (out->counts != scan_state(c).counts)
     return fail(MC_ERR_INVALID, "output batch frame counts differ from the last mc_scan_count");
   return scan_emit(c, out, noise, nullptr, nullptr);
 }
@@ -1810,9 +1862,7 @@ int mc_scan_emit_f64(mc_ctx* c, const double* noise, double* d_local, double* d_
 
 int mc_timing_read_scan(mc_ctx* c, double* ms, int64_t* n) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  return sum_events(c, c->scan_ev, ms, n);
+  return read_timing(c, scan_state(c).ev, ms, n);
 }
 
 // ---- LiDARSimulator.simulate_scan, the ray-march scanner (CSIM:1011-1146) --------------------
@@ -1826,12 +1876,13 @@ int mc_set_ray_scene(mc_ctx* c, int32_t n_objects, const int64_t* counts, const 
   CHECK_ARG(n == 0 || rows, "scene pointer is NULL");
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
-  ++c->ray_scene_ver;        // any earlier mc_ray_count's result is now stale
-  c->ray_valid = false;
-  c->d_ray_scene.reset(); c->d_ray_obj.reset();
-  c->ray_E = 0;
-  if (int r = c->d_ray_scene.alloc(std::max<size_t>(scene_words(n), 1))) return r;
-  if (int r = c->d_ray_obj.alloc(std::max<size_t>((size_t)n, 1))) return r;
+  RayState& s = ray_state(c);
+  ++s.scene_ver;        // any earlier mc_ray_count's result is now stale
+  s.valid = false;
+  s.d_scene.reset(); s.d_obj.reset();
+  s.E = 0;
+  if (int r = s.d_scene.alloc(std::max<size_t>(scene_words(n), 1))) return r;
+  if (int r = s.d_obj.alloc(std::max<size_t>((size_t)n, 1))) return r;
   if (n > 0) {
     std::vector<double> h(scene_words(n));
     std::vector<int32_t> ho((size_t)n);
@@ -1841,12 +1892,12 @@ int mc_set_ray_scene(mc_ctx* c, int32_t n_objects, const int64_t* counts, const 
         h[i] = q[0]; h[n + i] = q[1]; h[2 * n + i] = q[2]; h[3 * n + i] = q[3];
         ho[i] = o;
       }
-    HIPCHK(hipMemcpyAsync(c->d_ray_scene, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_ray_obj, ho.data(), ho.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s.d_scene, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s.d_obj, ho.data(), ho.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
-  c->ray_obj_start = std::move(start);
-  c->ray_E = n;
+  s.obj_start = std::move(start);
+  s.E = n;
   return MC_OK;
 }
 
@@ -1864,20 +1915,21 @@ int mc_ray_count(mc_ctx* c, int32_t F, const double* origins, const double* R, i
   CHECK_ARG(units <= (1 << 22), "too many rays for one launch");
   DeviceGuard g(c->device);
   if (int r = sync_all(c)) return r;
-  c->ray_valid = false;
-  c->d_ray_frame.reset(); c->d_ray_dirs.reset(); c->d_ray_steps.reset(); c->d_ray_hit.reset();
-  if (int r = c->d_ray_frame.alloc(12 * (size_t)std::max(F, 1))) return r;
-  if (int r = c->d_ray_dirs.alloc(3 * (size_t)std::max(n_rays, 1))) return r;
-  if (int r = c->d_ray_steps.alloc((size_t)std::max(n_steps, 1))) return r;
-  if (int r = c->d_ray_hit.alloc(std::max<size_t>((size_t)NR, 1) * sizeof(RayHit))) return r;
-  c->ray_F = F; c->ray_n = n_rays; c->ray_K = n_steps;
-  c->ray_counts.assign(F, 0);
-  c->ray_hits.assign(3 * (size_t)NR, -1);
-  c->ray_count_ver = c->ray_scene_ver;
+  RayState& s = ray_state(c);
+  s.valid = false;
+  s.d_frame.reset(); s.d_dirs.reset(); s.d_steps.reset(); s.d_hit.reset();
+  if (int r = s.d_frame.alloc(12 * (size_t)std::max(F, 1))) return r;
+  if (int r = s.d_dirs.alloc(3 * (size_t)std::max(n_rays, 1))) return r;
+  if (int r = s.d_steps.alloc((size_t)std::max(n_steps, 1))) return r;
+  if (int r = s.d_hit.alloc(std::max<size_t>((size_t)NR, 1) * sizeof(RayHit))) return r;
+  s.F = F; s.n = n_rays; s.K = n_steps;
+  s.counts.assign(F, 0);
+  s.hits.assign(3 * (size_t)NR, -1);
+  s.count_ver = s.scene_ver;
   for (int32_t f = 0; f < F; ++f) counts_out[f] = 0;
-  const int32_t n_tiles = (int32_t)((c->ray_E + kRayTile - 1) / kRayTile);
+  const int32_t n_tiles = (int32_t)((s.E + kRayTile - 1) / kRayTile);
   if (NR == 0 || n_steps == 0 || n_tiles == 0) {   // nothing to march or nothing to hit: all misses
-    c->ray_valid = true;
+    s.valid = true;
     return MC_OK;
   }
   std::vector<double> frame(12 * (size_t)F);
@@ -1885,9 +1937,9 @@ int mc_ray_count(mc_ctx* c, int32_t F, const double* origins, const double* R, i
     std::memcpy(&frame[12 * (size_t)f], origins + 3 * (size_t)f, 3 * sizeof(double));
     std::memcpy(&frame[12 * (size_t)f + 3], R + 9 * (size_t)f, 9 * sizeof(double));
   }
-  HIPCHK(hipMemcpyAsync(c->d_ray_frame, frame.data(), frame.size() * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_ray_dirs, dirs, 3 * (size_t)n_rays * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(c->d_ray_steps, steps, (size_t)n_steps * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.d_frame, frame.data(), frame.size() * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.d_dirs, dirs, 3 * (size_t)n_rays * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(s.d_steps, steps, (size_t)n_steps * 8, hipMemcpyHostToDevice, c->stream));
   // scene chunks: enough workgroups to fill the device (or mc_set_launch's cap); the merged result does
   // not depend on the choice
   const int64_t target = c->max_grid > 0 ? c->max_grid : 8192;
@@ -1895,23 +1947,23 @@ int mc_ray_count(mc_ctx* c, int32_t F, const double* origins, const double* R, i
   const int32_t chunk_tiles = (n_tiles + n_chunks - 1) / n_chunks;
   n_chunks = (n_tiles + chunk_tiles - 1) / chunk_tiles;
   const size_t part_bytes = (size_t)NR * n_chunks * sizeof(RayKey);
-  if (int r = ctx_reserve(c, c->d_ray_part, part_bytes)) return r;
+  if (int r = ctx_reserve(c, s.d_part, part_bytes)) return r;
   RayCountArgs a;
-  a.scene = c->d_ray_scene; a.E = c->ray_E; a.obj = c->d_ray_obj;
-  a.frame = c->d_ray_frame; a.dirs = c->d_ray_dirs; a.n_rays = n_rays;
-  a.steps = c->d_ray_steps; a.m = make_ray_march(steps, n_steps, step_size);
+  a.scene = s.d_scene; a.E = s.E; a.obj = s.d_obj;
+  a.frame = s.d_frame; a.dirs = s.d_dirs; a.n_rays = n_rays;
+  a.steps = s.d_steps; a.m = make_ray_march(steps, n_steps, step_size);
   a.F = F; a.n_groups = (int32_t)units; a.n_chunks = n_chunks;
   a.chunk_pts = (int64_t)chunk_tiles * kRayTile;
-  a.partial = c->d_ray_part.as<RayKey>();
+  a.partial = s.d_part.as<RayKey>();
   {
-    TimedRegion tr(c, &c->ray_ev, c->stream);
+    TimedRegion tr(c, &s.ev, c->stream);
     hipLaunchKernelGGL(k_ray_count, dim3((uint32_t)(units * n_chunks)), dim3(kBlock), 0, c->stream, a);
     hipLaunchKernelGGL(k_ray_merge, dim3((uint32_t)((NR + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
-                       a.partial, NR, n_chunks, c->d_ray_hit.as<RayHit>());
+                       a.partial, NR, n_chunks, s.d_hit.as<RayHit>());
   }
   HIPCHK(hipGetLastError());
   std::vector<RayHit> hit((size_t)NR);
-  HIPCHK(hipMemcpyAsync(hit.data(), c->d_ray_hit, hit.size() * sizeof(RayHit), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(hit.data(), s.d_hit, hit.size() * sizeof(RayHit), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int32_t f = 0; f < F; ++f) {
     int64_t n = 0;
@@ -1919,31 +1971,33 @@ int mc_ray_count(mc_ctx* c, int32_t F, const double* origins, const double* R, i
       const RayHit& h = hit[(size_t)f * n_rays + i];
       if (h.step < 0) continue;
       ++n;
-      int32_t* q = &c->ray_hits[3 * ((size_t)f * n_rays + i)];
-      q[0] = h.step; q[1] = h.obj; q[2] = (int32_t)(h.idx - c->ray_obj_start[h.obj]);
+      int32_t* q = &s.hits[3 * ((size_t)f * n_rays + i)];
+      q[0] = h.step; q[1] = h.obj; q[2] = (int32_t)(h.idx - s.obj_start[h.obj]);
     }
-    c->ray_counts[f] = n;
+    s.counts[f] = n;
     counts_out[f] = n;
   }
-  c->ray_valid = true;
+  s.valid = true;
   return MC_OK;
 }
 
 int mc_ray_hits(mc_ctx* c, int32_t* hits_out) {
   CHECK_ARG(c, "ctx is NULL");
-  if (!c->ray_valid) return fail(MC_ERR_STATE, "no mc_ray_count result");
-  CHECK_ARG(c->ray_hits.empty() || hits_out, "output pointer is NULL");
-  if (!c->ray_hits.empty()) std::memcpy(hits_out, c->ray_hits.data(), c->ray_hits.size() * sizeof(int32_t));
+  RayState& s = ray_state(c);
+  if (!s.valid) return fail(MC_ERR_STATE, "no mc_ray_count result");
+  CHECK_ARG(s.hits.empty() || hits_out, "output pointer is NULL");
+  if (!s.hits.empty()) std::memcpy(hits_out, s.hits.data(), s.hits.size() * sizeof(int32_t));
   return MC_OK;
 }
 
 // pass 2 of the last mc_ray_count: a batch's float32 columns (out != nullptr) or host float64 rows
 static int ray_emit(mc_ctx* c, mc_batch* out, const double* rinv, const double* noise, double* rows_out) {
-  if (!c->ray_valid || c->ray_count_ver != c->ray_scene_ver)
+  RayState& s = ray_state(c);
+  if (!s.valid || s.count_ver != s.scene_ver)
     return fail(MC_ERR_STATE, "no mc_ray_count for the current scene (mc_set_ray_scene since the count?)");
-  const int32_t F = c->ray_F;
+  const int32_t F = s.F;
   std::vector<int64_t> doff;
-  if (int r = frame_offsets(c->ray_counts.data(), F, &doff)) return r;
+  if (int r = frame_offsets(s.counts.data(), F, &doff)) return r;
   const int64_t H = doff[F];
   if (H == 0) return MC_OK;
   CHECK_ARG(rinv, "R_inv is NULL");
@@ -1963,9 +2017,9 @@ static int ray_emit(mc_ctx* c, mc_batch* out, const double* rinv, const double* 
   if (noise) HIPCHK(hipMemcpyAsync(d_noise, noise, w_noise * 8, hipMemcpyHostToDevice, c->stream));
   RayEmitArgs ea;
   std::memset(&ea, 0, sizeof(ea));
-  ea.scene = c->d_ray_scene; ea.E = c->ray_E;
-  ea.frame = c->d_ray_frame; ea.rinv = d_rinv; ea.dirs = c->d_ray_dirs; ea.n_rays = c->ray_n;
-  ea.steps = c->d_ray_steps; ea.hit = c->d_ray_hit.as<RayHit>();
+  ea.scene = s.d_scene; ea.E = s.E;
+  ea.frame = s.d_frame; ea.rinv = d_rinv; ea.dirs = s.d_dirs; ea.n_rays = s.n;
+  ea.steps = s.d_steps; ea.hit = s.d_hit.as<RayHit>();
   ea.noise = noise ? d_noise : nullptr;
   ea.doff = d_doff;
   if (out) {
@@ -1977,7 +2031,7 @@ static int ray_emit(mc_ctx* c, mc_batch* out, const double* rinv, const double* 
     ea.rows = d_rows;
   }
   {
-    TimedRegion tr(c, &c->ray_ev, c->stream);
+    TimedRegion tr(c, &s.ev, c->stream);
     if (out) hipLaunchKernelGGL(k_ray_emit<false>, dim3((uint32_t)F), dim3(kBlock), 0, c->stream, ea);
     else hipLaunchKernelGGL(k_ray_emit<true>, dim3((uint32_t)F), dim3(kBlock), 0, c->stream, ea);
   }
@@ -1995,7 +2049,8 @@ static int ray_emit(mc_ctx* c, mc_batch* out, const double* rinv, const double* 
 int mc_ray_emit(mc_ctx* c, mc_batch* out, const double* R_inv, const double* noise) {
   CHECK_ARG(c && out, "NULL argument");
   CHECK_ARG(out->ctx == c, "batch belongs to another context");
-  if (c->ray_valid && out->counts != c->ray_counts)
+  RayState& s = ray_state(c);
+  if (s.valid && out->counts != s.counts)
     return fail(MC_ERR_INVALID, "output batch frame counts differ from the last mc_ray_count");
   return ray_emit(c, out, R_inv, noise, nullptr);
 }
@@ -2007,16 +2062,12 @@ int mc_ray_emit_f64(mc_ctx* c, const double* R_inv, const double* noise, double*
 
 int mc_timing_read_ray(mc_ctx* c, double* ms, int64_t* n) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  return sum_events(c, c->ray_ev, ms, n);
+  return read_timing(c, ray_state(c).ev, ms, n);
 }
 
 int mc_timing_read_layout(mc_ctx* c, double* ms, int64_t* n) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  return sum_events(c, c->layout_ev, ms, n);
+  return read_timing(c, c->layout_ev, ms, n);
 }
 
 }  // extern "C"

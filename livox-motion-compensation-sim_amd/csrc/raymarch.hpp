@@ -146,8 +146,8 @@ RM_HD inline double ray_s_max(const RayMarch& m, const double* steps, const RayK
 // RAYMARCH_CORE_END
 
 #if defined(__HIPCC__)
-#include "kernels.hpp"
-#include "scan.hpp"
+#include "block.hpp"
+#include "layout.hpp"
 
 namespace mc {
 using namespace mcray;
@@ -162,7 +162,7 @@ struct RayHit {
 };
 
 struct RayCountArgs {
-  const double* scene; int64_t E;   // columns x, y, z, intensity (scan.hpp scene_cols)
+  const double* scene; int64_t E;   // columns x, y, z, intensity (block.hpp scene_cols)
   const int32_t* obj;               // object of every scene point
   const double* frame;              // per frame: origin (3), R (9)
   const double* dirs; int32_t n_rays;   // sensor-frame unit directions (n_rays, 3)

@@ -25,7 +25,10 @@
 // host (rot.cpp frame_poses); per-(tile, frame) counts and offsets tile-major with the frames padded
 // to kScanFrames, so a workgroup's 8 frames are one 32 / 64-byte run.
 #pragma once
-#include "kernels.hpp"
+#include <cmath>
+
+#include "block.hpp"
+#include "layout.hpp"
 
 namespace mc {
 
@@ -113,14 +116,7 @@ __device__ __forceinline__ bool scan_visible(const double* __restrict__ P, doubl
 }
 // SCAN_CORE_END
 
-// the scene columns x, y, z, intensity (float64) in one allocation of scene_words(E) doubles
-inline size_t scene_words(int64_t E) { return 4 * (size_t)E; }
-struct SceneCols {
-  const double* x; const double* y; const double* z; const double* w;
-};
-__host__ __device__ inline SceneCols scene_cols(const double* env, int64_t E) {
-  return SceneCols{env, env + E, env + 2 * E, env + 3 * E};
-}
+// the scene's columns: block.hpp scene_cols
 __host__ __device__ inline int32_t scan_fpad(int32_t F) { return (F + kScanFrames - 1) / kScanFrames * kScanFrames; }
 
 // the workgroup's scene tile, kScanRounds points per thread, in registers
@@ -199,7 +195,7 @@ struct ScanEmitArgs {
   const uint32_t* vis_bits;  // pass 1's visibility words
   const double* noise;       // (N_out, 3) in the batch's dense order, or nullptr
   const int64_t* poff; const int64_t* doff;
-  float* cols; int32_t C;   // the output batch's blocked columns (kernels.hpp bidx)
+  float* cols; int32_t C;   // the output batch's blocked columns (layout.hpp bidx)
   double* local;            // ROWS: (N_out, 4) float64 sensor-frame rows (LMC:770), dense order
   double* aligned;          // ROWS: (N_out, 4) float64 R p + t of those rows (LMC:831), or nullptr
   int32_t* pcd_len;         // columns, MC_BATCH_WITH_PCD_LEN: per-block ASCII PCD bytes (zeroed), or nullptr

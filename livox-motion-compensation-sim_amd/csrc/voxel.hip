@@ -1,8 +1,8 @@
 // voxel.hip — host side of the voxel-grid filter (include/mcdeskew.h mc_voxel_*; kernels in voxel.hpp).
 //
 // The filter's state (the key table, the per-point slots, the per-voxel sums and what the last build
-// left for its emits) hangs from the context as its CtxExt (internal.hpp): the deskew and codec
-// translation units see only that hook.  mc_voxel_release frees it early; mc_destroy frees what is left.
+// left for its emits) is the CtxExt in the context's voxel slot (internal.hpp): the other translation
+// units see only that hook.  mc_voxel_release frees it early; mc_destroy frees what is left.
 #include "../../include/mcdeskew.h"
 #include "voxel.hpp"
 #include "internal.hpp"
@@ -35,16 +35,12 @@ struct VoxState : mcimpl::CtxExt {
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
-    for (auto& v : ev)
-      for (auto& p : v) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
+    for (auto& v : ev) ev_destroy(v);
   }
 };
 
 // the context's state (made on demand)
-VoxState* state_of(mc_ctx* c, bool create) {
-  if (!c->voxel && create) c->voxel.reset(new VoxState());
-  return static_cast<VoxState*>(c->voxel.get());
-}
+VoxState* state_of(mc_ctx* c, bool create) { return ctx_ext<VoxState>(c, mcimpl::kSlotVoxel, create); }
 
 int check_grid(double voxel, const double* origin) {
   CHECK_ARG(std::isfinite(voxel) && voxel > 0.0, "voxel must be finite and > 0 (got %g)", voxel);
@@ -251,7 +247,7 @@ int mc_voxel_release(mc_ctx* c) {
   DeviceGuard g(c->device);
   (void)sync_all(c);
   for (auto& v : s->ev) ev_recycle(c, v);
-  c->voxel.reset();
+  c->ext[mcimpl::kSlotVoxel].reset();
   return MC_OK;
 }
 

@@ -61,6 +61,7 @@ def ray_count(m, ctx, F, n_rays, seed):
     p, cd, ci = m._lib.ptr, m._lib.c_double, m._lib.c_int64
     m._lib.check(ctx.lib.mc_ray_count(ctx.handle, F, p(pos, cd), p(R, cd), n_rays, p(dirs, cd), len(steps), p(steps, cd),
                                       0.5, p(counts, ci)), "ray_count")
+    return counts
 
 
 def test_destroy_alone_frees_all_a_context_can_own():
@@ -187,5 +188,61 @@ def test_voxel_state_is_per_context_and_dies_with_it():
     assert cloud.n_voxels == len(want["rows"])
     assert np.array_equal(cloud.keys(), want["keys"]) and np.array_equal(cloud.point_counts(), want["counts"])
     assert np.array_equal(cloud.rows().view(np.uint64), want["rows"].view(np.uint64))
+    destroy_only(m, b)
+    assert live(m) == start
+
+
+def test_scan_ray_and_codec_state_is_per_context_and_dies_with_it():
+    m = pkg()
+    lib, check, p = m._lib.load(), m._lib.check, m._lib.ptr
+    cd, ci, ci32 = m._lib.c_double, m._lib.c_int64, m._lib.c_int32
+    scene = cloud_rows(600, 11, spread=30.0)
+    objs, oc = cloud_rows(300, 12, spread=8.0), np.array([150, 150], np.int64)
+    counts, rows = [300, 0, 5], cloud_rows(305, 13)
+    t, pos, rpy, _, _ = table(12, 14)
+    F_ray, n_rays = 2, 64
+
+    def three(ctx):
+        """a scan's columns, a ray count's counts and hits, a PCD encode's bytes"""
+        ctx.set_trajectory(t, pos, rpy)
+        ctx.set_environment(scene)
+        sb = ctx.scan([0.2, 0.5, 0.9], dict(CFG, points_per_frame=200))
+        scan = (np.array(sb.counts), sb.download_aos())
+        sb.close()
+        check(lib.mc_set_ray_scene(ctx.handle, 2, p(oc, ci), p(objs, cd), 4), "set_ray_scene")
+        hit_counts = ray_count(m, ctx, F_ray, n_rays, 15)
+        hits = np.full(3 * F_ray * n_rays, -7, np.int32)
+        check(lib.mc_ray_hits(ctx.handle, p(hits, ci32)), "ray_hits")
+        pb = ctx.batch(counts)
+        pb.upload_aos(rows)
+        pcd = m.codecs.encode_pcd_batch(pb)
+        pb.close()
+        return scan, hit_counts, hits, pcd
+
+    gc.collect()
+    start = live(m)
+    a = fresh_context(m)
+    a.timing(True)
+    got_a = three(a)
+    assert got_a[0][0].sum() > 0 and got_a[1].sum() > 0   # the scan saw points, rays hit
+    destroy_only(m, a)       # its scan, ray and codec timing pairs were never read
+    assert live(m) == start
+    # a new context, at A's address or not, has no count of either scanner and no timed launches
+    b = fresh_context(m)
+    buf = b.device_buffer(64)
+    assert lib.mc_scan_emit_f64(b.handle, None, buf.ptr, None) == m._lib.MC_ERR_STATE
+    buf.close()
+    r_inv = np.ascontiguousarray(np.tile(np.eye(3).ravel(), F_ray))
+    assert lib.mc_ray_emit_f64(b.handle, p(r_inv, cd), None, p(np.zeros(5 * F_ray * n_rays), cd)) == m._lib.MC_ERR_STATE
+    assert lib.mc_ray_hits(b.handle, p(np.zeros(3 * F_ray * n_rays, np.int32), ci32)) == m._lib.MC_ERR_STATE
+    for name in ("scan", "ray", "codec"):
+        ms, n = cd(-1.0), ci(-1)
+        check(getattr(lib, f"mc_timing_read_{name}")(b.handle, ctypes.byref(ms), ctypes.byref(n)), f"timing_read_{name}")
+        assert n.value == 0 and ms.value == 0.0, name
+    got_b = three(b)
+    assert np.array_equal(got_a[0][0], got_b[0][0])
+    assert np.array_equal(got_a[0][1].view(np.uint64), got_b[0][1].view(np.uint64))
+    assert np.array_equal(got_a[1], got_b[1]) and np.array_equal(got_a[2], got_b[2])
+    assert got_a[3] == got_b[3]
     destroy_only(m, b)
     assert live(m) == start
