@@ -24,6 +24,7 @@ struct PoseSeg;
 struct FrameRow;
 struct ImuSeg;
 struct FrameWin;
+struct TimeRule;
 }  // namespace mc
 
 namespace mcimpl {
@@ -166,6 +167,9 @@ struct mc_ctx : mcimpl::CtxQueues {
   DevBuf<char> d_stage;
   // launch knobs / timing
   int32_t max_grid = 0;
+  // evenly timed input batches take the deskew kernels that generate t_ns (mc_set_time_rule;
+  // MCDESKEW_TIME_RULE=0 starts a context with it off)
+  bool time_rule = true;
   bool timing = false;
   double wall_khz = 0.0;   // wall_clock64() rate
   // workgroup spans of timed deskew launches (DeskewArgs::span): kSpanSlots slots of 1 + kSpanTail
@@ -206,6 +210,11 @@ struct mc_batch {
   // k_prep outputs, double-buffered (ctx->buf selects the half): F entries per half
   DevBuf<mc::FrameRow> d_frame_tbl;   // 3 float64 rows per frame (R row, t)
   DevBuf<int2> d_trange;             // per-frame [min, max] t_ns (valid when trange_valid)
+  // the evenly-timed rule (time_rule.hpp), written by the same pass and valid exactly when trange_valid
+  // is: per frame its ramp, and whether every valid point is on it ([F]: some frame of the batch is not)
+  DevBuf<mc::TimeRule> d_trule;
+  DevBuf<int32_t> d_teven;           // F + 1
+  bool time_even = false;            // every non-empty frame is evenly timed (read back by compute_trange)
   DevBuf<mc::FrameWin> d_fwin;       // per-frame segment window
   DevBuf<char> d_frec;               // 2 frame-specialised pose/IMU records per frame
   size_t frec_half = 0;              // bytes per half of d_frec

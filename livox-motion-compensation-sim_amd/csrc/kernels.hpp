@@ -9,7 +9,7 @@
 //                       LERP of the pose table at each point's time, fused rotate-then-translate.
 //   k_deskew_points<2>  Path B, CSIM:1435-1536: gyro LERP at the point timestamp,
 //                       theta = w*dt, p' = Rx(-tx) Ry(-ty) Rz(-tz) p.
-//   k_deskew_points<1, false, false, RelArgs>  the SLERP mode into the sensor frame at a reference
+//   k_deskew_points<1, false, false, RULE, RelArgs>  the SLERP mode into the sensor frame at a reference
 //                       time: the same kernel over the per-frame relative table (relative.hpp).
 //   k_trange / k_synth / k_checksum / layout converters: staging, not the per-step path.
 //
@@ -28,6 +28,7 @@
 #include "block.hpp"
 #include "layout.hpp"
 #include "relfold.hpp"
+#include "time_rule.hpp"
 
 namespace mc {
 
@@ -118,7 +119,10 @@ struct DeskewArgs {
   int32_t n_tiles;
   int32_t xcd_order;       // sub-tiles in XCD-contiguous order (1) or dealt (0): the mode's default or
                            // what mc_tune_order measured faster on this device (deskew_plan)
-  const FrameRow* frame_tbl; // frame mode: 3 rows per frame (R row i, t_i), float64
+  union {                  // (one slot: the kernel-argument layout is the one the kernels were measured with)
+    const FrameRow* frame_tbl; // frame mode: 3 rows per frame (R row i, t_i), float64
+    const TimeRule* trule;     // per-point modes, RULE kernels: the input frames' time ramps (time_rule.hpp)
+  };
   const double* frame_time;
   const int64_t* frame_start;
   const FrameWin* fwin;    // per-point modes
@@ -1417,7 +1421,13 @@ struct RelArgs {
   const int64_t* roff;    // F + 1 offsets into rel
 };
 
-template <int MODE, bool NEXT = false, bool PCD = false, typename... REL>
+// RULE: every frame of the input batch is evenly timed (time_rule.hpp; k_trange tested every valid
+// point), so load_sub issues no load of the time column: a point's time is its frame's ramp at its
+// frame-local index, two integer instructions per point in place of 4 of the 20 bytes read.  Padding
+// slots take the frame's last valid index, so their times stay inside the frame's span (no extra peel,
+// no overflow); where t_ns is passed through (copy_t) they are written as 0, the stored padding value
+// of every producer.  Everything after load_sub is the same text.
+template <int MODE, bool NEXT = false, bool PCD = false, bool RULE = false, typename... REL>
 __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const DeskewArgs a, const PrepArgs pn,
                                                                          const uint32_t pre, const REL... rel) {
   constexpr bool kRel = sizeof...(REL) != 0;
@@ -1448,7 +1458,18 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
     const int g = g0 + tid;
     const int gl = g < tl.ngroups ? g : (g0 < tl.ngroups ? g0 : 0);
     const float* q = a.in + bidx((int)a.in_C, 0, tl.pstart + 4 * (int64_t)gl);
-    Tq = ld4(reinterpret_cast<const int32_t*>(q + 4 * kBlkPts));
+    if constexpr (RULE) {
+      const TimeRule tr = ldu(a.trule + tl.frame);
+      const uint32_t last = (uint32_t)ldu(a.fcount + tl.frame) - 1u;            // (n >= 1: the tile has groups)
+      const uint32_t i0 = (uint32_t)(tl.pstart - tr.poff) + 4u * (uint32_t)gl;  // the group's first local index
+      const int32_t tb = time_rule_at(tr.t0, tr.dt, i0), t_last = time_rule_at(tr.t0, tr.dt, last);
+      Tq.x = i0 <= last ? tb : t_last;
+      Tq.y = i0 + 1u <= last ? (int32_t)((uint32_t)tb + (uint32_t)tr.dt) : t_last;
+      Tq.z = i0 + 2u <= last ? (int32_t)((uint32_t)tb + 2u * (uint32_t)tr.dt) : t_last;
+      Tq.w = i0 + 3u <= last ? (int32_t)((uint32_t)tb + 3u * (uint32_t)tr.dt) : t_last;
+    } else {
+      Tq = ld4(reinterpret_cast<const int32_t*>(q + 4 * kBlkPts));
+    }
     X = ld4(q);
     Y = ld4(q + kBlkPts);
     Z = ld4(q + 2 * kBlkPts);
@@ -1564,7 +1585,14 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
       st_out(o + kBlkPts, Y);
       st_out(o + 2 * kBlkPts, Z);
       st_out(o + 3 * kBlkPts, I);
-      if (a.copy_t) st_out(o + 4 * kBlkPts, __builtin_bit_cast(float4, Tq));
+      if (a.copy_t) {
+        int4 To = Tq;
+        if constexpr (RULE) {   // padding slots: the stored 0, not the clamped ramp
+          const int64_t left = ldu(a.fcount + f) - (p - ldu(&a.trule[f].poff));
+          To.y = left > 1 ? To.y : 0; To.z = left > 2 ? To.z : 0; To.w = left > 3 ? To.w : 0;
+        }
+        st_out(o + 4 * kBlkPts, __builtin_bit_cast(float4, To));
+      }
     }
     if constexpr (PCD) {
       const int64_t i0 = p - ldu(a.fpoff + f), n = ldu(a.fcount + f);
@@ -1862,16 +1890,29 @@ __global__ __launch_bounds__(kBlock) void k_column(const LayoutArgs a, int c, co
 }
 
 // per-frame [min, max] of t_ns over the valid points (feeds k_prep's frame windows)
-__global__ __launch_bounds__(kBlock) void k_trange_init(int2* tr, int32_t F) {
+// ... and the frame's time ramp (time_rule.hpp) from its first two stored times; even[f] = 1 until
+// k_trange finds a valid point off the ramp, even[F] = 0 until it finds one anywhere in the batch
+__global__ __launch_bounds__(kBlock) void k_trange_init(const LayoutArgs a, int2* tr, int32_t F, TimeRule* rule,
+                                                        int32_t* even) {
   const int64_t f = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-  if (f < F) tr[f] = make_int2(INT_MAX, INT_MIN);
+  if (f < F) {
+    tr[f] = make_int2(INT_MAX, INT_MIN);
+    const int64_t p0 = a.poff[f], n = a.counts[f];
+    const int32_t t0 = n > 0 ? a.tns(p0) : 0;
+    rule[f] = TimeRule{p0, t0, n > 1 ? time_rule_step(t0, a.tns(p0 + 1)) : 0};
+    even[f] = 1;
+  }
+  if (f == 0) even[F] = 0;
 }
 // ... and per sub-tile (kBlock float4 groups), feeding k_prep's sub-tile windows
-__global__ __launch_bounds__(kBlock) void k_trange(const LayoutArgs a, int2* tr, int2* str) {
+__global__ __launch_bounds__(kBlock) void k_trange(const LayoutArgs a, int2* tr, int2* str, const TimeRule* rule,
+                                                   int32_t* even, int32_t F) {
   __shared__ int s_lo[kSub][kBlock / 64], s_hi[kSub][kBlock / 64];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   for (int64_t tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
     const Tile tl = a.tiles[tile];
+    const TimeRule r = rule[tl.frame];
+    bool off = false;   // a valid point of this lane is off its frame's ramp
     int flo = INT_MAX, fhi = INT_MIN;
 #pragma unroll
     for (int j = 0; j < kSub; ++j) {
@@ -1879,10 +1920,12 @@ __global__ __launch_bounds__(kBlock) void k_trange(const LayoutArgs a, int2* tr,
       const int e_end = min(4 * tl.ngroups, (j + 1) * 4 * kBlock);
       for (int e = j * 4 * kBlock + threadIdx.x; e < e_end; e += kBlock) {
         const int64_t p = tl.pstart + e;
-        if (local_index(a, tl, p) >= 0) {
+        const int64_t i = local_index(a, tl, p);
+        if (i >= 0) {
           const int t = a.tns(p);
           lo = min(lo, t);
           hi = max(hi, t);
+          off |= !time_rule_holds(r.t0, r.dt, i, t);
         }
       }
       lo = wave_min(lo);
@@ -1894,6 +1937,10 @@ __global__ __launch_bounds__(kBlock) void k_trange(const LayoutArgs a, int2* tr,
     if (lane == 0 && flo <= fhi) {
       atomicMin(&tr[tl.frame].x, flo);
       atomicMax(&tr[tl.frame].y, fhi);
+    }
+    if (off) {   // (every writer stores the same value)
+      even[tl.frame] = 0;
+      even[F] = 1;
     }
     __syncthreads();
     if (threadIdx.x < kSub) {

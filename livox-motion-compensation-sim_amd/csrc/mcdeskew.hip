@@ -100,11 +100,18 @@ static int download_column(mc_batch* b, int col, T* dst) {
 static int compute_trange(mc_batch* b) {
   mc_ctx* c = b->ctx;
   if (b->F == 0 || !b->has_t()) { b->trange_valid = true; return MC_OK; }
-  hipLaunchKernelGGL(k_trange_init, dim3((b->F + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, b->d_trange, b->F);
+  b->time_even = false;
+  hipLaunchKernelGGL(k_trange_init, dim3((b->F + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, layout_of(b),
+                     b->d_trange, b->F, b->d_trule, b->d_teven);
   if (b->n_tiles > 0)
     hipLaunchKernelGGL(k_trange, dim3(launch_grid(c, b->n_tiles)), dim3(kBlock), 0, c->stream, layout_of(b),
-                       b->d_trange, b->d_strange);
+                       b->d_trange, b->d_strange, b->d_trule, b->d_teven, b->F);
   HIPCHK(hipGetLastError());
+  // one word back: does any frame leave its ramp?  (One synchronisation per write of the time column.)
+  int32_t uneven = 1;
+  HIPCHK(hipMemcpyAsync(&uneven, b->d_teven + b->F, sizeof(uneven), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  b->time_even = uneven == 0;
   b->trange_valid = true;
   ++b->prep_ver;
   return MC_OK;
@@ -119,6 +126,13 @@ static void launch(bool ext, uint32_t grid, hipStream_t s, hipEvent_t e0, hipEve
                    const Args&... args) {
   if (!ext && !e0 && !flags) hipLaunchKernelGGL(K, dim3(grid), dim3(kBlock), 0, s, args...);
   else hipExtLaunchKernelGGL(K, dim3(grid), dim3(kBlock), 0, s, e0, e1, flags, args...);
+}
+
+// f(std::bool_constant<RULE>) for a plan's per-point kernel (StepPlan::rule)
+template <typename F>
+static void with_rule(bool rule, F&& f) {
+  if (rule) f(std::true_type{});
+  else f(std::false_type{});
 }
 
 // f(std::integral_constant<int, MODE>) for a plan's kernel
@@ -228,6 +242,7 @@ int mc_create(int device, mc_ctx** out) {
                 device, prop.gcnArchName);
   std::unique_ptr<mc_ctx> c(new mc_ctx());   // a failure below frees what was created so far
   c->device = device;
+  if (const char* v = std::getenv("MCDESKEW_TIME_RULE")) c->time_rule = std::atoi(v) != 0;   // diagnostic
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->row_d2h, hipStreamNonBlocking);
   if (e != hipSuccess) return fail(MC_ERR_HIP, "stream/event creation: %s", hipGetErrorString(e));
@@ -250,6 +265,13 @@ int mc_sync(mc_ctx* c) {
   CHECK_ARG(c, "ctx is NULL");
   DeviceGuard g(c->device);
   return sync_all(c);
+}
+
+int mc_set_time_rule(mc_ctx* c, int enable) {
+  CHECK_ARG(c, "ctx is NULL");
+  // (speculated tables stay valid: k_prep's outputs do not depend on which kernel reads them)
+  c->time_rule = enable != 0;
+  return MC_OK;
 }
 
 int mc_set_launch(mc_ctx* c, int32_t max_grid) {
@@ -352,6 +374,10 @@ int mc_batch_create(mc_ctx* c, int32_t F, const int64_t* counts, uint32_t flags,
   // k_prep outputs: two halves (double buffer, see mc_deskew)
   if ((r = b->d_frame_tbl.alloc(2 * 3 * (size_t)F))) return r;
   if ((r = b->d_trange.alloc(F))) return r;
+  if (b->has_t()) {
+    if ((r = b->d_trule.alloc(std::max<size_t>(F, 1)))) return r;
+    if ((r = b->d_teven.alloc((size_t)F + 1))) return r;
+  }
   if ((r = b->d_fwin.alloc(2 * (size_t)F))) return r;
   b->frec_half = 2 * (size_t)std::max<int>(F, 1) * std::max(sizeof(PoseWin), sizeof(ImuSeg));
   if ((r = b->d_frec.alloc(2 * b->frec_half))) return r;
@@ -728,6 +754,8 @@ struct StepPlan {
   uint32_t prep_blocks;
   uint32_t grid;
   int32_t kernel;   // -1: no deskew launch (no tiles); else the mode
+  bool rule;        // per-point modes: the input batch is evenly timed throughout (time_rule.hpp) and the
+                    // context allows it, so the launch takes the kernel that generates t_ns
 };
 
 constexpr int64_t kSlerpXcdMinPoints = 200000000;
@@ -776,7 +804,12 @@ void deskew_plan(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pos
   da.copy_t = mode != MC_MODE_FRAME && out != in && out->has_t();
   da.tiles = in->d_tiles; da.n_tiles = in->n_tiles;
   da.fpoff = out->d_poff; da.fcount = out->d_counts;   // (the PCD kernels' valid-point test)
-  da.frame_tbl = frame_tbl;
+  if (mode == MC_MODE_FRAME) {
+    da.frame_tbl = frame_tbl;
+  } else {   // (begin_steps made the spans, and the rule with them, current)
+    sp->rule = c->time_rule && in->trange_valid && in->time_even;
+    da.trule = in->d_trule;
+  }
   da.frame_time = pb->d_frame_time; da.frame_start = pb->d_frame_start;
   da.fwin = fwin; da.frec = frec;
   da.swin = swin;
@@ -817,8 +850,11 @@ void launch_main(const StepPlan& sp, hipStream_t s, hipEvent_t e0 = nullptr, hip
       if (pcd) launch<k_deskew_frame_pcd>(true, sp.grid, s, e0, e1, 0u, sp.da);
       else launch<k_deskew_frame>(false, sp.grid, s, e0, e1, 0u, sp.da);
     } else {
-      if (pcd) launch<k_deskew_points<M, false, true>>(true, sp.grid, s, e0, e1, 0u, sp.da, sp.pa, 0u);
-      else launch<k_deskew_points<M>>(false, sp.grid, s, e0, e1, 0u, sp.da, sp.pa, 0u);
+      with_rule(sp.rule, [&](auto rule) {
+        constexpr bool R = decltype(rule)::value;
+        if (pcd) launch<k_deskew_points<M, false, true, R>>(true, sp.grid, s, e0, e1, 0u, sp.da, sp.pa, 0u);
+        else launch<k_deskew_points<M, false, false, R>>(false, sp.grid, s, e0, e1, 0u, sp.da, sp.pa, 0u);
+      });
     }
   });
 }
@@ -831,13 +867,16 @@ void launch_fused(const StepPlan& sp, const StepPlan& nx, hipStream_t s, hipEven
   with_mode(sp.kernel, [&](auto mode) {
     constexpr int M = decltype(mode)::value;
     if constexpr (M == MC_MODE_FRAME) launch<k_deskew_frame_next>(true, grid, s, e0, e1, 0u, sp.da, nx.pa, pre);
-    else launch<k_deskew_points<M, true>>(true, grid, s, e0, e1, 0u, sp.da, nx.pa, pre);
+    else with_rule(sp.rule, [&](auto rule) {
+      launch<k_deskew_points<M, true, false, decltype(rule)::value>>(true, grid, s, e0, e1, 0u, sp.da, nx.pa, pre);
+    });
   });
 }
 
 // What mc_deskew, mc_deskew_steps and mc_tune_order do before their first launch: the frame time
 // spans, derived lazily from t_ns, are queued on the main stream if stale (the prep is then ordered
-// after them); plan[i] is planned for table half h0 ^ i (plan[1] only if `both`); out is about to be
+// after them, and compute_trange waits for one word of them — is every frame evenly timed? — so a call
+// that finds the spans stale synchronises once; no later call on the same time column does); plan[i] is planned for table half h0 ^ i (plan[1] only if `both`); out is about to be
 // written.
 int begin_steps(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select, int h0, bool both,
                 StepPlan* plan) {
@@ -1190,7 +1229,10 @@ int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const doubl
   {
     LaunchEvents ev(c);
     if (ev.e0) sp.da.span = span_take(c);
-    launch<k_deskew_points<1, false, false, RelArgs>>(false, sp.grid, s, ev.e0, ev.e1, 0u, sp.da, sp.pa, 0u, rl);
+    with_rule(sp.rule, [&](auto rule) {
+      launch<k_deskew_points<1, false, false, decltype(rule)::value, RelArgs>>(false, sp.grid, s, ev.e0, ev.e1, 0u,
+                                                                               sp.da, sp.pa, 0u, rl);
+    });
     ev.keep(&c->main_ev);
   }
   HIPCHK(hipGetLastError());
@@ -1213,6 +1255,26 @@ int mc_batch_time_spans(mc_batch* b, int32_t* t_min, int32_t* t_max) {
   HIPCHK(hipMemcpyAsync(tr.data(), b->d_trange, tr.size() * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int32_t f = 0; f < b->F; ++f) { t_min[f] = tr[f].x; t_max[f] = tr[f].y; }
+  return MC_OK;
+}
+
+int mc_batch_time_rule(mc_batch* b, int8_t* even, int32_t* t0, int32_t* dt) {
+  CHECK_ARG(b, "batch is NULL");
+  if (!b->has_t()) return fail(MC_ERR_STATE, "batch was created without MC_BATCH_WITH_TIME");
+  if (b->F == 0) return MC_OK;
+  CHECK_ARG(even && t0 && dt, "NULL output");
+  mc_ctx* c = b->ctx;
+  DeviceGuard g(c->device);
+  if (!b->trange_valid) {
+    if (int r = compute_trange(b)) return r;
+    c->prep_fence = true;
+  }
+  std::vector<TimeRule> tr((size_t)b->F);
+  std::vector<int32_t> ev((size_t)b->F);
+  HIPCHK(hipMemcpyAsync(tr.data(), b->d_trule, tr.size() * sizeof(TimeRule), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(ev.data(), b->d_teven, ev.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int32_t f = 0; f < b->F; ++f) { even[f] = (int8_t)ev[f]; t0[f] = tr[f].t0; dt[f] = tr[f].dt; }
   return MC_OK;
 }
 

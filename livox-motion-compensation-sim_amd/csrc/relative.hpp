@@ -8,7 +8,7 @@
 //                         saturates at kWinMax + 1), which sizes the per-frame relative table;
 //   k_rel_compose         after k_prep: every record of every frame's [klo, khi], folded into the
 //                         frame's reference pose (relfold.hpp) and specialised to the frame time.
-// The deskew itself is k_deskew_points<1, false, false, RelArgs> (kernels.hpp): the global kernel with
+// The deskew itself is k_deskew_points<1, false, false, RULE, RelArgs> (kernels.hpp): the global kernel with
 // every record read from that per-frame table; the float64 rows by the direct formula are
 // k_points_f64<1, RefPoses>.
 #pragma once

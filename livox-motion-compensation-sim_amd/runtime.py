@@ -316,6 +316,12 @@ class Context:
     def set_max_grid(self, max_grid: int):
         check(self.lib.mc_set_launch(self.handle, int(max_grid)), "set_launch")
 
+    def time_rule(self, enable: bool = True):
+        """Let evenly timed input batches (:meth:`Batch.time_rule`) take the deskew kernels that form
+        t_ns from each frame's ramp without reading the column (the default); ``False`` forces the
+        loading kernels for every later launch (mc_set_time_rule).  The outputs are the same to the bit."""
+        check(self.lib.mc_set_time_rule(self.handle, int(bool(enable))), "set_time_rule")
+
     def timing(self, enable: bool = True):
         check(self.lib.mc_timing_enable(self.handle, int(bool(enable))), "timing_enable")
 
@@ -481,6 +487,16 @@ class Batch:
         hi = np.zeros(self.n_frames, np.int32)
         check(self.lib.mc_batch_time_spans(self.handle, ptr(lo, c_int32), ptr(hi, c_int32)), "time_spans")
         return lo, hi
+
+    def time_rule(self):
+        """Per frame: is it evenly timed — t_ns[i] == t0 + i * dt over its points, int32 wrap-around
+        (mc_batch_time_rule) — and its (t0, dt): (even bool, t0 int32, dt int32) arrays."""
+        even = np.zeros(self.n_frames, np.int8)
+        t0 = np.zeros(self.n_frames, np.int32)
+        dt = np.zeros(self.n_frames, np.int32)
+        check(self.lib.mc_batch_time_rule(self.handle, ptr(even, ctypes.c_int8), ptr(t0, c_int32), ptr(dt, c_int32)),
+              "time_rule")
+        return even.astype(bool), t0, dt
 
     def pcd_len_current(self) -> bool:
         """True when the per-block PCD text sums describe the current columns."""
