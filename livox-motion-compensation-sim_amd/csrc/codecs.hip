@@ -227,7 +227,7 @@ int mc_pcd_encode_batch(mc_ctx* c, const mc_batch* b, void* d_out, int64_t out_b
   src.batch = b;
   // MC_BATCH_WITH_PCD_LEN: the kernel that last wrote the columns left their text sums (no measure pass)
   return pcd_encode(c, src, b->F, b->counts.data(), d_out, out_bytes, body_pos,
-                    b->pcd_current() ? b->d_pcd_len : nullptr);
+                    b->state.sums_current() ? b->d_pcd_len : nullptr);
 }
 
 int mc_deskew_pcd(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select, void* d_out,
@@ -394,7 +394,7 @@ int csim_batch_source(mc_ctx* c, const mc_batch* b, Source* src) {
   CHECK_ARG(c && b, "NULL argument");
   CHECK_ARG(b->ctx == c, "batch belongs to another context");
   if (!b->has_t()) return fail(MC_ERR_STATE, "the CSIM encoders need a batch created with MC_BATCH_WITH_TIME");
-  if (!b->has_starts) return fail(MC_ERR_STATE, "the batch's frame starts are not set (mc_batch_set_frame_start_ns)");
+  if (!b->state.has_frame_starts()) return fail(MC_ERR_STATE, "the batch's frame starts are not set (mc_batch_set_frame_start_ns)");
   src->batch = b;
   return MC_OK;
 }
@@ -711,7 +711,7 @@ int lvx_decode(mc_ctx* c, int format, const void* d_file, int64_t bytes, int32_t
   }
   HIPCHK(hipGetLastError());
   if (out)
-    if (int r = mcimpl::batch_columns_written(out)) return r;
+    if (int r = mcimpl::batch_columns_written(out, mcimpl::kWroteAllQueued)) return r;
   HIPCHK(hipStreamSynchronize(c->stream));
   return MC_OK;
 }
@@ -815,13 +815,12 @@ int text_decode(mc_ctx* c, int sep, int32_t n_cols, const void* d_text, int64_t 
       std::vector<int64_t> fs((size_t)out->F);
       HIPCHK(hipMemcpyAsync(fs.data(), out->d_frame_start, fs.size() * 8, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
-      out->has_starts = true;
-      ++out->prep_ver;
+      out->state.frame_starts_set();   // (the kernel wrote them)
       if (frame_start_out) std::copy(fs.begin(), fs.end(), frame_start_out);
     } else if (with_t && frame_start_out) {
       std::copy_n(frame_start_ns, out->F, frame_start_out);
     }
-    if (int r = mcimpl::batch_columns_written(out)) return r;
+    if (int r = mcimpl::batch_columns_written(out, mcimpl::kWroteAllQueued)) return r;
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   for (int64_t t = 0; t < PT; ++t) {
@@ -1078,11 +1077,10 @@ int las_decode(mc_ctx* c, const void* d_file, int64_t bytes, int fmt, int64_t re
       std::vector<int64_t> fs((size_t)out->F);
       HIPCHK(hipMemcpyAsync(fs.data(), out->d_frame_start, fs.size() * 8, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
-      out->has_starts = true;
-      ++out->prep_ver;
+      out->state.frame_starts_set();   // (the kernel wrote them)
       if (frame_start_out) std::copy(fs.begin(), fs.end(), frame_start_out);
     }
-    if (int r = mcimpl::batch_columns_written(out)) return r;
+    if (int r = mcimpl::batch_columns_written(out, mcimpl::kWroteAllQueued)) return r;
   }
   HIPCHK(hipStreamSynchronize(c->stream));
   if (bad[0]) {
@@ -1135,7 +1133,7 @@ int mc_las_encode_batch(mc_ctx* c, const mc_batch* b, int point_format, const do
   CHECK_ARG(b->ctx == c, "batch belongs to another context");
   if (time_mul != 0.0) {
     if (!b->has_t()) return fail(MC_ERR_STATE, "a LAS time needs a batch created with MC_BATCH_WITH_TIME");
-    if (!b->has_starts) return fail(MC_ERR_STATE, "the batch's frame starts are not set (mc_batch_set_frame_start_ns)");
+    if (!b->state.has_frame_starts()) return fail(MC_ERR_STATE, "the batch's frame starts are not set (mc_batch_set_frame_start_ns)");
   }
   Source src;
   src.batch = b;

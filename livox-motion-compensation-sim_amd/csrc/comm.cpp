@@ -224,14 +224,13 @@ int mc_comm_gather_batch(mc_comm* c, const mc_batch* local, int root, mc_batch* 
   mcgather::Merged mg;
   if (is_root && merged) {
     mg.P = merged->P; mg.C = merged->C; mg.F = merged->F; mg.counts = merged->counts.data(); mg.cols = merged->d_cols;
-    merged->wrote(false);
+    mcimpl::batch_columns_written(merged, mcimpl::kWrotePoints | mcimpl::kWroteTime);   // (spans: on next use)
   }
   std::string msg;
   const int r = mcgather::run(T, root, sh, is_root && merged ? &mg : nullptr, &msg);
   if (foreign) return fail(MC_ERR_INVALID, "merged batch belongs to another context");
   if (r == mcgather::kBadPlan) return fail(MC_ERR_INVALID, "%s", msg.c_str());
   if (r) return r;   // the primitive recorded its message (mc_last_error)
-  if (is_root) merged->trange_valid = false;   // column 4 (t_ns) was written: its cached spans are stale
   return MC_OK;
 }
 
@@ -287,7 +286,7 @@ int mc_gather_batches(mc_ctx* ctx, int32_t n, const mc_batch* const* shards, int
   hipStream_t s = ctx->stream;
   DevBuf<float> stage;   // freed on every way out
   if (G.stage_values > 0) if (int r = stage.alloc((size_t)G.stage_values)) return r;
-  merged->wrote(false);
+  mcimpl::batch_columns_written(merged, mcimpl::kWrotePoints | mcimpl::kWroteTime);   // (spans: on next use)
   hipError_t e = hipSuccess;
   for (int32_t q = 0; q < n && e == hipSuccess; ++q) {
     if (q == root || P[q] == 0) continue;
@@ -297,7 +296,6 @@ int mc_gather_batches(mc_ctx* ctx, int32_t n, const mc_batch* const* shards, int
   if (e == hipSuccess) e = finish_on_device(G, n, root, P.data(), C.data(), merged, shards[root]->d_cols, stage, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return fail(MC_ERR_HIP, "gather_batches: %s", hipGetErrorString(e));
-  merged->trange_valid = false;
   return MC_OK;
 }
 

@@ -16,6 +16,7 @@
 #include <utility>
 #include <vector>
 
+#include "batch_state.hpp"
 #include "devbuf.hpp"
 
 namespace mc {
@@ -107,31 +108,9 @@ using mcimpl::EventPairs;
 struct mc_ctx : mcimpl::CtxQueues {
   ~mc_ctx();   // mcdeskew.hip, where the records the buffers hold are complete types
   int device = 0;
-  // per-step tables come in two halves: the next step's prep writes half `buf` while the previous
-  // step's deskew kernel still reads the other (see mc_deskew)
-  int buf = 0;
-  // true while the next k_prep must wait for everything queued before it (an ordinary, barrier
-  // launch): set by whatever leaves work queued that the prep must not overtake (t_ns spans, the
-  // stagers, table uploads, a speculative launch writing the same half); cleared by mc_deskew, whose
-  // deskew kernel then ends the queue, so the next prep may run any-order beside it (see mc_deskew)
-  bool prep_fence = true;
-  // Per-call speculation (mc_deskew): a call whose inputs equal the previous call's launches its
-  // deskew fused with the prep of an identical next call into the other table half (the pipelined
-  // launch of mc_deskew_steps); the next call, if its key still matches, finds its tables ready and
-  // issues no k_prep.  Keys: the input batch's uid, mode, pose selection and the versions of every
-  // prep input (trajectory, IMU, the batch's frame times / starts / t_ns spans).
-  struct PrepKey {
-    uint64_t batch = 0, traj = 0, imu = 0, frames = 0;
-    int mode = -1, pose_select = -1;
-    bool operator==(const PrepKey& o) const {
-      return batch == o.batch && traj == o.traj && imu == o.imu && frames == o.frames && mode == o.mode &&
-             pose_select == o.pose_select;
-    }
-  };
-  PrepKey last_call;            // the previous mc_deskew's key (batch 0: none)
-  PrepKey spec_key;             // what the tables in half spec_half were prepared for
-  bool spec_valid = false;
-  int spec_half = 0;
+  // which table half the next k_prep writes, whether it may be an any-order packet, and the per-call
+  // speculation of mc_deskew: batch_state.hpp
+  mcimpl::PrepSchedule sched;
   uint64_t traj_ver = 0, imu_ver = 0;   // bumped by mc_set_trajectory / mc_set_imu
   // sub-tile order per mode measured by mc_tune_order for batches of P padded points (-1: none)
   struct OrderTune {
@@ -185,7 +164,9 @@ struct mc_ctx : mcimpl::CtxQueues {
 struct mc_batch {
   mc_ctx* ctx = nullptr;
   uint64_t uid = 0;         // unique per batch ever created (a key can never match a new batch)
-  uint64_t prep_ver = 0;    // bumped whenever frame times, frame starts or the t_ns spans change
+  // what the caches below still describe (batch_state.hpp); mutable as they are: they belong to the
+  // batch a deskew call reads
+  mutable mcimpl::BatchState state;
   int32_t F = 0;
   int64_t N = 0;    // valid points
   int64_t P = 0;    // padded points (poff[F]; every frame starts on a kBlkPts boundary)
@@ -207,14 +188,13 @@ struct mc_batch {
   DevBuf<mc::Tile> d_tiles;
   DevBuf<double> d_frame_time;
   DevBuf<int64_t> d_frame_start;
-  // k_prep outputs, double-buffered (ctx->buf selects the half): F entries per half
+  // k_prep outputs, double-buffered (ctx->sched names the half): F entries per half
   DevBuf<mc::FrameRow> d_frame_tbl;   // 3 float64 rows per frame (R row, t)
-  DevBuf<int2> d_trange;             // per-frame [min, max] t_ns (valid when trange_valid)
-  // the evenly-timed rule (time_rule.hpp), written by the same pass and valid exactly when trange_valid
-  // is: per frame its ramp, and whether every valid point is on it ([F]: some frame of the batch is not)
+  DevBuf<int2> d_trange;             // per-frame [min, max] t_ns (valid while state.spans_current())
+  // the evenly-timed rule (time_rule.hpp), written by the same pass and valid exactly when the spans
+  // are: per frame its ramp, and whether every valid point is on it ([F]: some frame of the batch is not)
   DevBuf<mc::TimeRule> d_trule;
   DevBuf<int32_t> d_teven;           // F + 1
-  bool time_even = false;            // every non-empty frame is evenly timed (read back by compute_trange)
   DevBuf<mc::FrameWin> d_fwin;       // per-frame segment window
   DevBuf<char> d_frec;               // 2 frame-specialised pose/IMU records per frame
   size_t frec_half = 0;              // bytes per half of d_frec
@@ -223,31 +203,18 @@ struct mc_batch {
   DevBuf<int2> d_strange;            // per sub-tile [min, max] t_ns
   DevBuf<mc::FrameWin> d_swin;       // per sub-tile window, double-buffered (2 * n_sub)
   DevBuf<double> d_partial;
-  bool has_times = false, has_starts = false, trange_valid = false;
   // mc_deskew_relative: the per-frame relative segment table (relative.hpp) — frame f's records
-  // [d_roff[f], d_roff[f+1]) are its segments [klo, khi] folded into its reference pose.  Kept with
-  // the batch: the offsets hold while the trajectory upload (rel_traj) and the batch's frame times and
-  // t_ns spans (rel_frames = prep_ver) are the ones they were counted for, the records while the
-  // reference times are the same too (rel_own: each frame's own time; else rel_tref).
-  DevBuf<mc::PoseSeg> d_rel;
-  int64_t rel_total = 0;           // records in use (d_roff[F])
-  DevBuf<int64_t> d_roff;          // F + 1
-  DevBuf<int32_t> d_relw;          // F window widths (the count pass)
-  DevBuf<double> d_tref;           // F reference times
-  DevBuf<double> d_refpose;        // F reference quaternions (4 F), then F reference positions (3 F)
-  bool rel_offsets_valid = false, rel_valid = false, rel_own = false;
-  uint64_t rel_traj = 0, rel_frames = 0;
-  std::vector<double> rel_tref;
-  // MC_BATCH_WITH_PCD_LEN: ASCII PCD text bytes per 256-point block (layout.hpp PcdCount sums).
-  // data_ver counts the writes of the x|y|z|intensity columns; pcd_ver is the data_ver the sums
-  // were written with (current iff equal).
+  // [d_roff[f], d_roff[f+1]) are its segments [klo, khi] folded into its reference pose.  A cache kept
+  // with the input batch, as its k_prep outputs are; state says what of it can be reused.
+  mutable DevBuf<mc::PoseSeg> d_rel;
+  mutable int64_t rel_total = 0;           // records in use (d_roff[F])
+  mutable DevBuf<int64_t> d_roff;          // F + 1
+  mutable DevBuf<int32_t> d_relw;          // F window widths (the count pass)
+  mutable DevBuf<double> d_tref;           // F reference times
+  mutable DevBuf<double> d_refpose;        // F reference quaternions (4 F), then F reference positions (3 F)
+  // MC_BATCH_WITH_PCD_LEN: ASCII PCD text bytes per 256-point block (layout.hpp PcdCount sums),
+  // current while state.sums_current()
   DevBuf<int32_t> d_pcd_len;
-  uint64_t data_ver = 1, pcd_ver = 0;
-  void wrote(bool with_sums) {                               // after queueing a write of the columns
-    ++data_ver;
-    if (with_sums && d_pcd_len) pcd_ver = data_ver;
-  }
-  bool pcd_current() const { return d_pcd_len && pcd_ver == data_ver; }
 };
 
 namespace mcimpl {
@@ -256,6 +223,14 @@ namespace mcimpl {
 int deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select, int32_t* pcd_len);
 // the sub-tile order (0 dealt, 1 XCD-contiguous) mc_deskew's kernel takes for this mode and batch
 int deskew_order(const mc_ctx* c, const mc_batch* in, int mode);
-// a kernel of another file has queued a write of b's columns (t_ns included) on the context's stream
-int batch_columns_written(mc_batch* b);
+// The one way to say "this batch's columns were written" (DESIGN.md §4.1 lists who says what).  A
+// writer announces kWrotePoints before it queues its launch, so a launch that fails leaves the sums
+// stale, and adds kWroteSums once the launch that also wrote them is queued.  kWroteTime marks the
+// spans and the rule stale; with kSpansNow they are recomputed in the call (one synchronisation: the
+// only way the call fails), else by the next reader (ensure_spans).  kLeftQueued: the caller returns
+// with this work still on the stream, which the next k_prep must not overtake.
+enum : unsigned { kWrotePoints = 1, kWroteSums = 2, kWroteTime = 4, kSpansNow = 8, kLeftQueued = 16 };
+// a kernel that writes every column and leaves the stream running: the decoders, the voxel emit
+constexpr unsigned kWroteAllQueued = kWrotePoints | kWroteTime | kSpansNow | kLeftQueued;
+int batch_columns_written(mc_batch* b, unsigned what);
 }  // namespace mcimpl

@@ -30,6 +30,7 @@
 #include <vector>
 
 using namespace mc;
+using namespace mcimpl;
 
 namespace mcimpl {
 thread_local std::string g_err;
@@ -76,7 +77,7 @@ static int upload_column(mc_batch* b, const T* src, int col) {
   void* st = nullptr;
   if (int r = ctx_stage(c, (size_t)b->N * sizeof(T), &st)) return r;
   HIPCHK(hipMemcpyAsync(st, src, (size_t)b->N * sizeof(T), hipMemcpyHostToDevice, c->stream));
-  if (col < 4) b->wrote(false);
+  if (col < 4) batch_columns_written(b, kWrotePoints);
   hipLaunchKernelGGL((k_column<T, 0>), dim3(launch_grid(c, b->n_tiles)), dim3(kBlock), 0, c->stream,
                      layout_of(b), col, static_cast<const T*>(st), static_cast<T*>(nullptr));
   HIPCHK(hipGetLastError());
@@ -97,10 +98,9 @@ static int download_column(mc_batch* b, int col, T* dst) {
 }
 
 // per-frame t_ns span, recomputed whenever the t column is written (staging time, not per step)
-static int compute_trange(mc_batch* b) {
+static int compute_trange(const mc_batch* b) {
   mc_ctx* c = b->ctx;
-  if (b->F == 0 || !b->has_t()) { b->trange_valid = true; return MC_OK; }
-  b->time_even = false;
+  if (b->F == 0 || !b->has_t()) { b->state.spans_not_needed(); return MC_OK; }
   hipLaunchKernelGGL(k_trange_init, dim3((b->F + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, layout_of(b),
                      b->d_trange, b->F, b->d_trule, b->d_teven);
   if (b->n_tiles > 0)
@@ -111,10 +111,14 @@ static int compute_trange(mc_batch* b) {
   int32_t uneven = 1;
   HIPCHK(hipMemcpyAsync(&uneven, b->d_teven + b->F, sizeof(uneven), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  b->time_even = uneven == 0;
-  b->trange_valid = true;
-  ++b->prep_ver;
+  b->state.spans_computed(uneven == 0);
   return MC_OK;
+}
+// the spans and the rule, made current for a reader; the pass it queues must not be overtaken by a prep
+static int ensure_spans(const mc_batch* b) {
+  if (b->state.spans_current()) return MC_OK;
+  b->ctx->sched.work_in_flight();
+  return compute_trange(b);
 }
 
 // One launch of kernel K with optional hipExtLaunchKernel timing events (e0/e1 null: untimed) and
@@ -435,7 +439,7 @@ int mc_batch_padded_offsets(const mc_batch* b, int64_t* poff) {
 
 int mc_batch_pcd_len_current(const mc_batch* b, int32_t* current) {
   CHECK_ARG(b && current, "NULL argument");
-  *current = b->pcd_current() ? 1 : 0;
+  *current = b->state.sums_current() ? 1 : 0;
   return MC_OK;
 }
 
@@ -447,8 +451,7 @@ int mc_batch_set_frame_times(mc_batch* b, const double* t) {
     HIPCHK(hipMemcpyAsync(b->d_frame_time, t, b->F * sizeof(double), hipMemcpyHostToDevice, b->ctx->stream));
     HIPCHK(hipStreamSynchronize(b->ctx->stream));
   }
-  b->has_times = true;
-  ++b->prep_ver;
+  b->state.frame_times_set();
   return MC_OK;
 }
 
@@ -460,24 +463,18 @@ int mc_batch_set_frame_start_ns(mc_batch* b, const int64_t* s) {
     HIPCHK(hipMemcpyAsync(b->d_frame_start, s, b->F * sizeof(int64_t), hipMemcpyHostToDevice, b->ctx->stream));
     HIPCHK(hipStreamSynchronize(b->ctx->stream));
   }
-  b->has_starts = true;
-  ++b->prep_ver;
+  b->state.frame_starts_set();
   return MC_OK;
 }
 
-// Work this context queues on its stream and leaves running when the call returns must keep the next
-// mc_deskew's prep from being issued any-order: that prep may only overtake this
-// context's own deskew kernel.  Every API that returns with work in flight calls this.
-static inline void queued_async(mc_ctx* c) { c->prep_fence = true; }
-
-// After a kernel outside this file (the ingest decoders) queued a write of the batch's columns: the PCD
-// text sums are stale, the t_ns spans are recomputed, and the next prep must not overtake the write.
 extern "C++" {
 namespace mcimpl {
-int batch_columns_written(mc_batch* b) {
-  queued_async(b->ctx);
-  b->wrote(false);
-  return compute_trange(b);
+int batch_columns_written(mc_batch* b, unsigned what) {
+  if (what & kLeftQueued) b->ctx->sched.work_in_flight();
+  if (what & kWrotePoints) b->state.points_written();
+  if ((what & kWroteSums) && b->d_pcd_len) b->state.sums_written();
+  if (what & kWroteTime) b->state.time_written();
+  return (what & kSpansNow) ? compute_trange(b) : MC_OK;
 }
 }  // namespace mcimpl
 }
@@ -486,7 +483,7 @@ int batch_columns_written(mc_batch* b) {
 static int launch_stage(mc_batch* b, const double* d_aos, int64_t ld) {
   mc_ctx* c = b->ctx;
   if (b->n_tiles == 0) return MC_OK;
-  queued_async(c);
+  batch_columns_written(b, kWrotePoints | kLeftQueued);
   LayoutArgs a = layout_of(b);
   a.pcd_len = b->d_pcd_len;   // MC_BATCH_WITH_PCD_LEN: the stager sums each block's text bytes
   {
@@ -494,16 +491,15 @@ static int launch_stage(mc_batch* b, const double* d_aos, int64_t ld) {
     hipLaunchKernelGGL(k_aos_to_soa, dim3(launch_grid(c, stage_units(b->n_tiles, ld))), dim3(kBlock), 0, c->stream,
                        a, d_aos, ld);
   }
-  b->wrote(false);
   HIPCHK(hipGetLastError());
-  b->wrote(true);
+  batch_columns_written(b, kWroteSums);
   return MC_OK;
 }
 // batch columns -> device AoS (N,4) f64 (async, timed as a layout kernel)
 static int launch_fetch(mc_batch* b, double* d_aos) {
   mc_ctx* c = b->ctx;
   if (b->n_tiles == 0) return MC_OK;
-  queued_async(c);
+  c->sched.work_in_flight();
   {
     TimedRegion tr(c, &c->layout_ev, c->stream);
     hipLaunchKernelGGL(k_soa_to_aos, dim3(launch_grid(c, fetch_units(b->n_tiles))), dim3(kBlock), 0, c->stream,
@@ -607,7 +603,7 @@ int mc_batch_upload_time_ns(mc_batch* b, const int32_t* t) {
   CHECK_ARG(t, "t_ns is NULL");
   DeviceGuard g(b->ctx->device);
   if (int r = upload_column<int32_t>(b, t, 4)) return r;
-  if (int r = compute_trange(b)) return r;
+  if (int r = batch_columns_written(b, kWroteTime | kSpansNow)) return r;
   HIPCHK(hipStreamSynchronize(b->ctx->stream));
   return MC_OK;
 }
@@ -675,11 +671,11 @@ int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base) {
   if (b->n_tiles == 0) return MC_OK;
   mc_ctx* c = b->ctx;
   DeviceGuard g(c->device);
-  b->wrote(false);
+  batch_columns_written(b, kWrotePoints);
   hipLaunchKernelGGL(k_synth, dim3(launch_grid(c, b->n_tiles)), dim3(kBlock), 0, c->stream, layout_of(b), seed,
                      frame_id_base);
   HIPCHK(hipGetLastError());
-  if (int r = compute_trange(b)) return r;
+  if (int r = batch_columns_written(b, kWroteTime | kSpansNow)) return r;
   HIPCHK(hipStreamSynchronize(c->stream));
   return MC_OK;
 }
@@ -707,18 +703,11 @@ int mc_batch_checksum(mc_batch* b, double* sums) {
 // deskew kernel, so it runs beside that kernel's tail without a second queue; the deskew kernel after
 // it is an ordinary packet and waits for both.  (Rejected in rounds 1-2: the prep on a side stream one
 // step ahead with cross-queue events, ~7-10 us per step; serial on the main stream, +2 to +6 us.)
-// Identical consecutive calls are speculated (mc_ctx::PrepKey): a call's launch also runs the next
+// Identical consecutive calls are speculated (batch_state.hpp PrepSchedule): a call's launch also runs the next
 // identical call's prep in its first workgroups (k_deskew_points<MODE, true> / k_deskew_frame_next,
 // the same fused launch mc_deskew_steps' pipeline issues; for SLERP step wall 320.2-328.3 vs
 // 329.5-329.6 us with the prep as a separate packet, profiles/round3/s19).
 namespace {
-
-// Table halves written outside mc_deskew's key bookkeeping: no speculated tables stay valid, and the
-// next mc_deskew does not speculate from a key seen before this call.
-void forget_speculation(mc_ctx* c) {
-  c->spec_valid = false;
-  c->last_call = mc_ctx::PrepKey{};
-}
 
 int deskew_check(mc_ctx* c, const mc_batch* in, const mc_batch* out, int mode, int pose_select) {
   CHECK_ARG(c && in && out, "NULL argument");
@@ -732,15 +721,15 @@ int deskew_check(mc_ctx* c, const mc_batch* in, const mc_batch* out, int mode, i
     if (pose_select == MC_POSE_DIRECT && c->T != in->F)
       return fail(MC_ERR_INVALID, "MC_POSE_DIRECT needs one pose per frame (T=%lld, frames=%d)", (long long)c->T,
                   in->F);
-    if (pose_select == MC_POSE_SEARCHSORTED && !in->has_times)
+    if (pose_select == MC_POSE_SEARCHSORTED && !in->state.has_frame_times())
       return fail(MC_ERR_STATE, "frame times not set (mc_batch_set_frame_times)");
   } else if (mode == MC_MODE_POSE_SLERP) {
     if (c->T < 1) return fail(MC_ERR_STATE, "no trajectory uploaded (mc_set_trajectory)");
-    if (!in->has_times) return fail(MC_ERR_STATE, "frame times not set (mc_batch_set_frame_times)");
+    if (!in->state.has_frame_times()) return fail(MC_ERR_STATE, "frame times not set (mc_batch_set_frame_times)");
     if (!in->has_t()) return fail(MC_ERR_STATE, "input batch has no t_ns column");
   } else {
     if (c->M < 1) return fail(MC_ERR_STATE, "no IMU samples uploaded (mc_set_imu)");
-    if (!in->has_starts) return fail(MC_ERR_STATE, "frame start times not set (mc_batch_set_frame_start_ns)");
+    if (!in->state.has_frame_starts()) return fail(MC_ERR_STATE, "frame start times not set (mc_batch_set_frame_start_ns)");
     if (!in->has_t()) return fail(MC_ERR_STATE, "input batch has no t_ns column");
   }
   return MC_OK;
@@ -807,7 +796,7 @@ void deskew_plan(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pos
   if (mode == MC_MODE_FRAME) {
     da.frame_tbl = frame_tbl;
   } else {   // (begin_steps made the spans, and the rule with them, current)
-    sp->rule = c->time_rule && in->trange_valid && in->time_even;
+    sp->rule = c->time_rule && in->state.rule_usable();
     da.trule = in->d_trule;
   }
   da.frame_time = pb->d_frame_time; da.frame_start = pb->d_frame_start;
@@ -880,15 +869,12 @@ void launch_fused(const StepPlan& sp, const StepPlan& nx, hipStream_t s, hipEven
 // written.
 int begin_steps(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select, int h0, bool both,
                 StepPlan* plan) {
-  if (mode != MC_MODE_FRAME && !in->trange_valid) {
-    if (int r = compute_trange(const_cast<mc_batch*>(in))) return r;
-    c->prep_fence = true;
-  }
+  if (mode != MC_MODE_FRAME)
+    if (int r = ensure_spans(in)) return r;
   for (int i = 0; i <= (both ? 1 : 0); ++i) deskew_plan(c, in, out, mode, pose_select, h0 ^ i, &plan[i]);
   // a per-point deskew that carries t_ns into another batch rewrites that batch's time column:
-  // its cached [min, max] spans no longer describe it
-  if (plan[0].da.copy_t) out->trange_valid = false;
-  out->wrote(false);
+  // its cached [min, max] spans no longer describe it (recomputed by their next reader)
+  batch_columns_written(out, kWrotePoints | (plan[0].da.copy_t ? kWroteTime : 0u));
   return MC_OK;
 }
 }  // namespace
@@ -914,29 +900,18 @@ int mcimpl::deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, 
   hipStream_t s = c->stream;
   // Per-step tables come in two halves: this step's prep writes half h, which the deskew kernel
   // two calls back read; the previous call's kernel reads the other half.
-  const int h = c->buf;
+  const int h = c->sched.free_half();
   StepPlan sp;   // (the other half is planned only when this call speculates)
   if (int r = begin_steps(c, in, out, mode, pose_select, h, false, &sp)) return r;
-  c->buf ^= 1;
+  c->sched.take_half();
   sp.da.pcd_len = pcd_len;
-  // Speculation (see mc_ctx::PrepKey): h is the half the previous call's launch prepared for this
-  // key, if it did; then this call needs no k_prep at all.
-  const mc_ctx::PrepKey key{in->uid, c->traj_ver, c->imu_ver, in->prep_ver, mode, pose_select};
-  const bool hit = c->spec_valid && c->spec_half == h && c->spec_key == key;
-  // (the fused next-call launch has no PCD variant: a PCD call never speculates, it may hit)
-  const bool speculate = sp.kernel >= 0 && c->last_call == key && !pcd_len;
-  c->last_call = key;
-  c->spec_valid = false;
-  if (!hit) {
-    // One queue.  Any-order prep only right behind this context's own deskew
-    // kernel (prep_fence clear): the packets before it are then that kernel — still reading the
-    // other half — and, before it, work the kernel's barrier already waited for.  Everything else
-    // that could precede it either finished before its API call returned (trajectory / IMU / frame
-    // tables are uploaded synchronously) or set the fence (t_ns spans queued by begin_steps, the
-    // stagers, a speculative launch whose prep workgroups write this very half).  The deskew kernel's
-    // own packet keeps the barrier bit, so it waits for this prep, and anything queued after it waits
-    // for both.  With no kernel to follow (no tiles) the prep is ordinary.
-    const unsigned fl = (!c->prep_fence && sp.kernel >= 0) ? hipExtAnyOrderLaunch : 0u;
+  // Whether this call needs a k_prep at all (the previous call's launch may have prepared half h for
+  // this key), how the prep is issued and whether the launch speculates: PrepSchedule::decide.
+  // (The fused next-call launch has no PCD variant: a PCD call never speculates, it may hit.)
+  const PrepKey key{in->uid, c->traj_ver, c->imu_ver, in->state.prep_key(), mode, pose_select};
+  const PrepSchedule::Decision d = c->sched.decide(key, h, sp.kernel >= 0, !pcd_len);
+  if (d.prep) {
+    const unsigned fl = d.any_order ? hipExtAnyOrderLaunch : 0u;
     {
       LaunchEvents ev(c);
       launch_prep(sp, s, ev.e0, ev.e1, fl);
@@ -947,25 +922,20 @@ int mcimpl::deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, 
   if (sp.kernel >= 0) {
     LaunchEvents ev(c);
     if (ev.e0) sp.da.span = span_take(c);
-    if (speculate) {
+    if (d.speculate) {
       // this call's deskew with an identical next call's prep in the first workgroups (half h ^ 1,
       // which no queued work reads: the previous kernel read it and has finished before this launch)
       StepPlan nx;
       deskew_plan(c, in, out, mode, pose_select, h ^ 1, &nx);
       launch_fused(sp, nx, s, ev.e0, ev.e1);
-      c->spec_valid = true;
-      c->spec_half = h ^ 1;
-      c->spec_key = key;
     } else {
       launch_main(sp, s, ev.e0, ev.e1);
     }
     ev.keep(&c->main_ev);
     HIPCHK(hipGetLastError());
-    out->wrote(pcd_len != nullptr && pcd_len == out->d_pcd_len);
-    // after a speculative launch the next prep (on a miss) writes the half its prep workgroups write
-    c->prep_fence = speculate;
-  } else {
-    c->prep_fence = true;
+    if (pcd_len == out->d_pcd_len) batch_columns_written(out, kWroteSums);
+    if (d.speculate) c->sched.launched_speculative(key, h);
+    else c->sched.launched_plain();
   }
   // No event records here: a marker packet between this kernel and the next step's any-order prep
   // would hold that prep until this kernel completes.  Everything is on one queue, so the stream
@@ -979,15 +949,14 @@ namespace {
 // The launches of n steps over the two table halves of `plan` (step i reads half i & 1 of plan):
 // step 0's k_prep, then n deskew launches of which the first n - 1 carry the next step's prep.
 // Every `every`-th step's kernel (and prep) is timed.
+// ao: step 0's prep is an any-order packet (right behind this context's own deskew kernel, as in mc_deskew).
 // last_pcd: the last step's launch also writes the output blocks' PCD text bytes there (its output is
 // what the batch keeps; the launches before it have no PCD variant of the fused next-prep kernel).
-void issue_steps(mc_ctx* c, const StepPlan* plan, int32_t n_steps, int32_t every, int32_t* last_pcd) {
+void issue_steps(mc_ctx* c, const StepPlan* plan, int32_t n_steps, int32_t every, int32_t* last_pcd, bool ao) {
   hipStream_t s = c->stream;
   auto sampled = [&](int32_t i) { return every > 0 && i % every == every / 2; };
   for (int32_t i = 0; i < n_steps; ++i) {
     if (i == 0) {
-      // any-order right behind this context's own deskew kernel, as in mc_deskew
-      const bool ao = !c->prep_fence;
       LaunchEvents ev(c, sampled(i));
       launch_prep(plan[i & 1], s, ev.e0, ev.e1, ao ? hipExtAnyOrderLaunch : 0u);
       ev.keep(&c->prep_ev);
@@ -1010,15 +979,14 @@ void issue_steps(mc_ctx* c, const StepPlan* plan, int32_t n_steps, int32_t every
 // before the step that reads it, as in mc_deskew.  Step i reads half h0 ^ (i & 1).
 int deskew_steps_pipelined(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select,
                            int32_t n_steps, int32_t every) {
-  forget_speculation(c);
-  const int h0 = c->buf;
+  c->sched.forget_speculation();
+  const int h0 = c->sched.free_half();
   StepPlan plan[2];
   if (int r = begin_steps(c, in, out, mode, pose_select, h0, true, plan)) return r;
-  issue_steps(c, plan, n_steps, every, plan[0].kernel >= 0 ? out->d_pcd_len : nullptr);
+  issue_steps(c, plan, n_steps, every, plan[0].kernel >= 0 ? out->d_pcd_len : nullptr, c->sched.prep_may_overtake());
   HIPCHK(hipGetLastError());
-  if (plan[0].kernel >= 0 && n_steps > 0) out->wrote(true);
-  c->buf = h0 ^ (n_steps & 1);   // the half the last launch did not read
-  c->prep_fence = false;
+  if (plan[0].kernel >= 0 && n_steps > 0) batch_columns_written(out, kWroteSums);
+  c->sched.steps_issued(h0, n_steps);
   return MC_OK;
 }
 }  // namespace
@@ -1045,9 +1013,8 @@ int mc_tune_order(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
   // the candidates run as the steps of mc_deskew_steps do (issue_steps: fused next-step launches);
   // plain kernels only: any PCD text sums of out go stale
   StepPlan plan[2];
-  if (int r = begin_steps(c, in, out, mode, pose_select, c->buf, true, plan)) return r;
-  forget_speculation(c);
-  c->prep_fence = true;   // the first prep is an ordinary packet: waits for everything queued before it
+  if (int r = begin_steps(c, in, out, mode, pose_select, c->sched.free_half(), true, plan)) return r;
+  c->sched.tuner_ran();   // whichever way this call ends, the next prep is an ordinary packet
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIPCHK(hipEventCreate(&e0));
   if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail(MC_ERR_HIP, "event create"); }
@@ -1060,12 +1027,10 @@ int mc_tune_order(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
       const int cand = (r & 1) ? 1 - k : k;
       plan[0].da.xcd_order = plan[1].da.xcd_order = cand;
       // the previous round's last launch may read either half (odd `launches`): the warm-up's first
-      // prep is an ordinary packet, so it waits for that launch
-      c->prep_fence = true;
-      issue_steps(c, plan, 2, 0, nullptr);   // untimed: this order's own steady state
-      c->prep_fence = false;
+      // prep is an ordinary packet, so it waits for that launch and for everything queued before it
+      issue_steps(c, plan, 2, 0, nullptr, false);   // untimed: this order's own steady state
       e = hipEventRecord(e0, s);
-      issue_steps(c, plan, launches, 0, nullptr);
+      issue_steps(c, plan, launches, 0, nullptr, true);
       if (e == hipSuccess) e = hipEventRecord(e1, s);
       if (e == hipSuccess) e = hipEventSynchronize(e1);
       float ms = 0.f;
@@ -1089,7 +1054,6 @@ int mc_tune_order(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
   const int def = default_order(mode, in->P), other = 1 - def;
   const int best = med[other] < med[def] * (1.0 - kTuneMargin) ? other : def;
   c->order_tune[mode] = mc_ctx::OrderTune{in->P, best};
-  c->prep_fence = true;   // the next prep is an ordinary packet
   if (us_out) { us_out[0] = med[0]; us_out[1] = med[1]; }
   if (chosen) *chosen = best;
   return MC_OK;
@@ -1134,21 +1098,18 @@ int check_t_ref(const double* t_ref, int32_t F) {
 // the table already holds these references over these tables; the offsets (a count pass and one
 // synchronisation to size the table) are redone only when the trajectory, the frame times or the
 // t_ns spans changed.
-int rel_table(mc_ctx* c, mc_batch* b, const StepPlan& sp, const double* t_ref) {
+int rel_table(mc_ctx* c, const mc_batch* b, const StepPlan& sp, const double* t_ref) {
   hipStream_t s = c->stream;
   const int32_t F = b->F;
-  const bool same_tab = b->rel_offsets_valid && b->rel_traj == c->traj_ver && b->rel_frames == b->prep_ver;
-  const bool same_ref = b->rel_own == (t_ref == nullptr) &&
-                        (!t_ref || (b->rel_tref.size() == (size_t)F && std::equal(t_ref, t_ref + F, b->rel_tref.begin())));
-  if (same_tab && b->rel_valid && same_ref) return MC_OK;
-  b->rel_valid = false;
+  if (b->state.rel_reusable(c->traj_ver, t_ref, (size_t)F)) return MC_OK;
+  const bool same_tab = b->state.rel_offsets_reusable(c->traj_ver);
+  b->state.rel_rebuilding(!same_tab);
   RelTableArgs ra;
   std::memset(&ra, 0, sizeof(ra));
   ra.F = F;
   ra.frame_time = b->d_frame_time; ra.trange = b->d_trange;
   ra.pose_time = c->d_time; ra.T = c->T; ra.nseg = sp.pa.nseg;
   if (!same_tab) {
-    b->rel_offsets_valid = false;
     if (!b->d_roff) {
       if (int r = b->d_roff.alloc((size_t)F + 1)) return r;
       if (int r = b->d_relw.alloc((size_t)F)) return r;
@@ -1173,9 +1134,7 @@ int rel_table(mc_ctx* c, mc_batch* b, const StepPlan& sp, const double* t_ref) {
     HIPCHK(hipMemcpyAsync(b->d_roff, roff.data(), roff.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
     b->rel_total = roff[F];
-    b->rel_traj = c->traj_ver;
-    b->rel_frames = b->prep_ver;
-    b->rel_offsets_valid = true;
+    b->state.rel_offsets_built(c->traj_ver);
   }
   const double* d_t = b->d_frame_time;
   if (t_ref) {
@@ -1195,9 +1154,7 @@ int rel_table(mc_ctx* c, mc_batch* b, const StepPlan& sp, const double* t_ref) {
     hipLaunchKernelGGL(k_rel_compose, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(kBlock), 0, s, ra);
   }
   HIPCHK(hipGetLastError());
-  b->rel_own = t_ref == nullptr;
-  if (t_ref) b->rel_tref.assign(t_ref, t_ref + F); else b->rel_tref.clear();
-  b->rel_valid = true;
+  b->state.rel_built(t_ref, (size_t)F);
   return MC_OK;
 }
 }  // namespace
@@ -1210,12 +1167,12 @@ int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const doubl
   hipStream_t s = c->stream;
   // No speculation, no fused next-prep launch, no any-order prep (deskew_steps_pipelined's treatment
   // of itself): ordinary in-order launches of prep, compose and the kernel into table half h.
-  forget_speculation(c);
-  const int h = c->buf;
+  c->sched.forget_speculation();
+  const int h = c->sched.free_half();
   StepPlan sp;
   if (int r = begin_steps(c, in, out, MC_MODE_POSE_SLERP, MC_POSE_SEARCHSORTED, h, false, &sp)) return r;
-  c->buf ^= 1;
-  c->prep_fence = true;
+  c->sched.take_half();
+  c->sched.work_in_flight();
   {
     LaunchEvents ev(c);
     launch_prep(sp, s, ev.e0, ev.e1, 0u);
@@ -1223,9 +1180,8 @@ int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const doubl
   }
   HIPCHK(hipGetLastError());
   if (sp.kernel < 0) return MC_OK;
-  mc_batch* b = const_cast<mc_batch*>(in);   // the table is cached with the input batch, as its k_prep outputs are
-  if (int r = rel_table(c, b, sp, t_ref)) return r;
-  const RelArgs rl{b->d_rel, b->d_roff};
+  if (int r = rel_table(c, in, sp, t_ref)) return r;   // (cached with the input batch)
+  const RelArgs rl{in->d_rel, in->d_roff};
   {
     LaunchEvents ev(c);
     if (ev.e0) sp.da.span = span_take(c);
@@ -1236,7 +1192,6 @@ int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const doubl
     ev.keep(&c->main_ev);
   }
   HIPCHK(hipGetLastError());
-  out->wrote(false);
   return MC_OK;
 }
 
@@ -1247,10 +1202,7 @@ int mc_batch_time_spans(mc_batch* b, int32_t* t_min, int32_t* t_max) {
   CHECK_ARG(t_min && t_max, "NULL output");
   mc_ctx* c = b->ctx;
   DeviceGuard g(c->device);
-  if (!b->trange_valid) {
-    if (int r = compute_trange(b)) return r;
-    c->prep_fence = true;
-  }
+  if (int r = ensure_spans(b)) return r;
   std::vector<int2> tr((size_t)b->F);
   HIPCHK(hipMemcpyAsync(tr.data(), b->d_trange, tr.size() * sizeof(int2), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1265,10 +1217,7 @@ int mc_batch_time_rule(mc_batch* b, int8_t* even, int32_t* t0, int32_t* dt) {
   CHECK_ARG(even && t0 && dt, "NULL output");
   mc_ctx* c = b->ctx;
   DeviceGuard g(c->device);
-  if (!b->trange_valid) {
-    if (int r = compute_trange(b)) return r;
-    c->prep_fence = true;
-  }
+  if (int r = ensure_spans(b)) return r;
   std::vector<TimeRule> tr((size_t)b->F);
   std::vector<int32_t> ev((size_t)b->F);
   HIPCHK(hipMemcpyAsync(tr.data(), b->d_trule, tr.size() * sizeof(TimeRule), hipMemcpyDeviceToHost, c->stream));
@@ -1667,20 +1616,19 @@ int mc_transform_affine(mc_ctx* c, const mc_batch* in, mc_batch* out, int32_t n_
   DeviceGuard g(c->device);
   hipStream_t s = c->stream;
   // the frame table half not used by the last mc_deskew; main-stream order protects the previous
-  // reader of this half, and the fence (queued_async) keeps the next prep behind this call's kernel
-  const int h = c->buf;
-  c->buf ^= 1;
-  forget_speculation(c);   // half h is overwritten below
+  // reader of this half, and the fence (work_in_flight) keeps the next prep behind this call's kernel
+  const int h = c->sched.take_half();
+  c->sched.forget_speculation();   // half h is overwritten below
   std::vector<FrameRow> tbl(3 * (size_t)in->F);
   for (int32_t f = 0; f < in->F; ++f) {
     const double* m = mats + 12 * (size_t)(n_mats == 1 ? 0 : f);
     for (int r = 0; r < 3; ++r) tbl[3 * (size_t)f + r] = FrameRow{m[4 * r], m[4 * r + 1], m[4 * r + 2], m[4 * r + 3]};
   }
   FrameRow* frame_tbl = in->d_frame_tbl + 3 * (size_t)in->F * h;
-  queued_async(c);
+  c->sched.work_in_flight();
   HIPCHK(hipMemcpyAsync(frame_tbl, tbl.data(), tbl.size() * sizeof(FrameRow), hipMemcpyHostToDevice, s));
   if (in->n_tiles > 0) {
-    out->wrote(false);
+    batch_columns_written(out, kWrotePoints);
     DeskewArgs da;
     std::memset(&da, 0, sizeof(da));
     da.in = in->d_cols; da.in_C = in->C;
@@ -1891,7 +1839,7 @@ static int scan_emit(mc_ctx* c, mc_batch* out, const double* noise, double* d_lo
   ea.tile_off = s.d_toff; ea.nvis = s.d_nvis; ea.vis_bits = s.d_bits; ea.noise = d_noise;
   if (out) {
     ea.poff = out->d_poff; ea.doff = out->d_doff; ea.cols = out->d_cols; ea.C = out->C;
-    out->wrote(false);
+    batch_columns_written(out, kWrotePoints);
     ea.pcd_len = out->d_pcd_len;   // MC_BATCH_WITH_PCD_LEN: per-point atomic adds into zeroed slots
     if (ea.pcd_len) HIPCHK(hipMemsetAsync(ea.pcd_len, 0, (size_t)(out->P / kBlkPts) * sizeof(int32_t), c->stream));
   } else {
@@ -1905,7 +1853,7 @@ static int scan_emit(mc_ctx* c, mc_batch* out, const double* noise, double* d_lo
   }
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (out) out->wrote(true);
+  if (out) batch_columns_written(out, kWroteSums);
   return MC_OK;
 }
 
@@ -2086,7 +2034,7 @@ static int ray_emit(mc_ctx* c, mc_batch* out, const double* rinv, const double* 
   ea.doff = d_doff;
   if (out) {
     ea.poff = out->d_poff; ea.cols = out->d_cols; ea.C = out->C;
-    out->wrote(false);
+    batch_columns_written(out, kWrotePoints);
     ea.pcd_len = out->d_pcd_len;   // MC_BATCH_WITH_PCD_LEN: per-point atomic adds into zeroed slots
     if (ea.pcd_len) HIPCHK(hipMemsetAsync(ea.pcd_len, 0, (size_t)(out->P / kBlkPts) * sizeof(int32_t), c->stream));
   } else {
@@ -2100,9 +2048,8 @@ static int ray_emit(mc_ctx* c, mc_batch* out, const double* rinv, const double* 
   HIPCHK(hipGetLastError());
   if (!out) HIPCHK(hipMemcpyAsync(rows_out, d_rows, w_rows * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (out) {
-    out->wrote(true);
-    if (out->has_t()) if (int r = compute_trange(out)) return r;   // the t_ns column was written
+  if (out) {   // (the t_ns column was written too)
+    if (int r = batch_columns_written(out, kWroteSums | (out->has_t() ? kWroteTime | kSpansNow : 0u))) return r;
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return MC_OK;

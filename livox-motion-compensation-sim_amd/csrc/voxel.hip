@@ -206,7 +206,7 @@ int mc_voxel_emit_batch(mc_ctx* c, mc_batch* out) {
   a.cols = out->d_cols;
   a.C = out->C;
   if (int r = emit(c, s, a, true, out->P)) return r;
-  return mcimpl::batch_columns_written(out);
+  return mcimpl::batch_columns_written(out, mcimpl::kWroteAllQueued);
 }
 
 int mc_voxel_emit_f64(mc_ctx* c, double* d_rows, int32_t* d_counts, int32_t* d_keys) {
