@@ -490,8 +490,27 @@ int mc_batch_checksum(mc_batch* b, double* sums5);
 /* out must have the same frame counts as in (it may be the same batch: in-place).
  * Per-point modes: when the input's time column was written since its spans were last computed, the
  * call first queues the span pass and waits for one word of it (is every frame evenly timed?
- * mc_batch_time_rule): one synchronisation per write of the time column, none on later calls. */
+ * mc_batch_time_rule): one synchronisation per write of the time column, none on later calls.
+ *
+ * The intensity column.  Every deskew passes it through unchanged.  A per-point launch (mc_deskew,
+ * mc_deskew_steps, mc_deskew_relative, mc_tune_order) into a batch without MC_BATCH_WITH_PCD_LEN and
+ * without a pcd_len target neither reads nor writes the column when the output already holds it:
+ *   - out == in (in place), from the first call;
+ *   - out received a deskew of `in` before (any mode) and neither batch's x|y|z|intensity columns have
+ *     been written since by anything else: the same scans deskewed again after mc_set_trajectory, in
+ *     another mode, with another t_ref, or the later steps of mc_deskew_steps.
+ * Such a launch moves 24 bytes per point instead of 32 (28 instead of 36 when the time column is read);
+ * the output is the same to the byte, padding slots included.  The first deskew of a fresh (in, out)
+ * pair moves what it always did.  Every write of either batch's point columns (uploads, synth, the
+ * stagers, affine, decoders, emits, gathers, a deskew of another input into out) ends the state; a new
+ * batch never matches an old one.  Frame mode always moves the column.
+ * mc_batch_holds_intensity_of(out, in): 1 when out holds in's intensity column right now, else 0 (< 0:
+ * a NULL argument); a pure query of host state, nothing is queued or waited for.
+ * mc_set_keep_intensity(ctx, 0) makes every later launch of the context take the full kernels (1: back
+ * to the default); the environment variable MCDESKEW_KEEP_INTENSITY=0 creates contexts with it off. */
 int mc_deskew(mc_ctx* ctx, const mc_batch* in, mc_batch* out, int mode, int pose_select);
+int mc_batch_holds_intensity_of(const mc_batch* out, const mc_batch* in);
+int mc_set_keep_intensity(mc_ctx* ctx, int enable);
 
 /* The SLERP deskew into the SENSOR frame at a reference time per frame (build-added, as SURVEY §8a
  * row a11 is): with (R_ref, pos_ref) = the SLERP / LERP pose of the trajectory at t_ref[f] (seconds,

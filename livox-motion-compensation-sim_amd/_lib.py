@@ -151,6 +151,8 @@ _SIGS = {
     "mc_batch_time_spans": (c_int, [c_void_p, _pi32, _pi32]),
     "mc_batch_time_rule": (c_int, [c_void_p, POINTER(ctypes.c_int8), _pi32, _pi32]),
     "mc_set_time_rule": (c_int, [c_void_p, c_int]),
+    "mc_set_keep_intensity": (c_int, [c_void_p, c_int]),
+    "mc_batch_holds_intensity_of": (c_int, [c_void_p, c_void_p]),
     # frames / outs: arrays of row pointers (passed as the address of a uintp array)
     "mc_align_frames_host_f64": (c_int, [c_void_p, c_int32, c_void_p, _pi64, _pi64, _pd, c_int, c_void_p]),
     "mc_timing_enable": (c_int, [c_void_p, c_int]),

@@ -17,7 +17,9 @@ namespace mcimpl {
 // What is cached about a batch's columns, and whether it still describes them.
 //   sums   the ASCII PCD text bytes per block (MC_BATCH_WITH_PCD_LEN), written by some kernels
 //          together with the x|y|z|intensity columns
-//   spans  per frame and per sub-tile [min, max] of t_ns, and with them the evenly-timed rule
+//   intensity  whose intensity column this batch holds: a deskew passes the input's through unchanged, so
+//          a later deskew of the same input into this batch need not move it while neither was written
+//   spans per frame and per sub-tile [min, max] of t_ns, and with them the evenly-timed rule
 //          (time_rule.hpp): one pass makes both, so the rule is valid exactly when the spans are
 //   key    the version of everything k_prep reads from the batch: frame times, frame starts, spans
 //   rel    mc_deskew_relative's table: its offsets hold for a (trajectory, key), its records for
@@ -30,6 +32,13 @@ class BatchState {
   void points_written() { ++data_ver_; }
   // the write announced last also wrote the sums (the caller knows the batch has a sums buffer)
   void sums_written() { sums_ver_ = data_ver_; }
+  // the write announced last left this batch's intensity column equal to that of the batch `src_uid`
+  // at its points version `src_ver` (a deskew out of that batch: the column is passed through)
+  void intensity_copied_from(uint64_t src_uid, uint64_t src_ver) {
+    int_uid_ = src_uid;
+    int_src_ver_ = src_ver;
+    int_own_ver_ = data_ver_;
+  }
   // the t_ns column was written: spans and rule describe another column until spans_computed().  The
   // key moves there, not here: every reader of the spans (the per-point modes' k_prep, the relative
   // table) recomputes them first, and frame mode's prep does not read them.
@@ -65,6 +74,12 @@ class BatchState {
 
   // ---- queries ----
   bool sums_current() const { return sums_ver_ == data_ver_; }
+  uint64_t points_version() const { return data_ver_; }   // what a holder of this batch's intensity records
+  // does this batch hold the intensity of batch `src_uid` as of its points version `src_ver`?  Neither
+  // batch's point columns were written since the copy (uid 0 is no batch: nothing copied yet)
+  bool holds_intensity_of(uint64_t src_uid, uint64_t src_ver) const {
+    return int_uid_ != 0 && int_uid_ == src_uid && int_src_ver_ == src_ver && int_own_ver_ == data_ver_;
+  }
   bool spans_current() const { return spans_valid_; }
   bool rule_usable() const { return spans_valid_ && time_even_; }
   bool has_frame_times() const { return has_times_; }
@@ -82,6 +97,8 @@ class BatchState {
  private:
   // data_ver_ counts the writes of the point columns; sums_ver_ is the one the sums came with
   uint64_t data_ver_ = 1, sums_ver_ = 0;
+  // whose intensity the column holds: the source's uid and points version, and data_ver_ as of the copy
+  uint64_t int_uid_ = 0, int_src_ver_ = 0, int_own_ver_ = 0;
   uint64_t prep_ver_ = 0;
   bool spans_valid_ = false, time_even_ = false;
   bool has_times_ = false, has_starts_ = false;

@@ -149,6 +149,9 @@ struct mc_ctx : mcimpl::CtxQueues {
   // evenly timed input batches take the deskew kernels that generate t_ns (mc_set_time_rule;
   // MCDESKEW_TIME_RULE=0 starts a context with it off)
   bool time_rule = true;
+  // a per-point deskew into a batch that already holds the input's intensity column takes the kernels
+  // that do not move it (mc_set_keep_intensity; MCDESKEW_KEEP_INTENSITY=0 starts a context with it off)
+  bool keep_intensity = true;
   bool timing = false;
   double wall_khz = 0.0;   // wall_clock64() rate
   // workgroup spans of timed deskew launches (DeskewArgs::span): kSpanSlots slots of 1 + kSpanTail
@@ -229,8 +232,11 @@ int deskew_order(const mc_ctx* c, const mc_batch* in, int mode);
 // spans and the rule stale; with kSpansNow they are recomputed in the call (one synchronisation: the
 // only way the call fails), else by the next reader (ensure_spans).  kLeftQueued: the caller returns
 // with this work still on the stream, which the next k_prep must not overtake.
-enum : unsigned { kWrotePoints = 1, kWroteSums = 2, kWroteTime = 4, kSpansNow = 8, kLeftQueued = 16 };
+// kHoldsIntensity, once a deskew of `src` into b is queued: b's intensity column is src's as it stands.
+enum : unsigned {
+  kWrotePoints = 1, kWroteSums = 2, kWroteTime = 4, kSpansNow = 8, kLeftQueued = 16, kHoldsIntensity = 32
+};
 // a kernel that writes every column and leaves the stream running: the decoders, the voxel emit
 constexpr unsigned kWroteAllQueued = kWrotePoints | kWroteTime | kSpansNow | kLeftQueued;
-int batch_columns_written(mc_batch* b, unsigned what);
+int batch_columns_written(mc_batch* b, unsigned what, const mc_batch* src = nullptr);
 }  // namespace mcimpl

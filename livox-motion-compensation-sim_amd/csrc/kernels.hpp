@@ -1427,12 +1427,20 @@ struct RelArgs {
 // slots take the frame's last valid index, so their times stay inside the frame's span (no extra peel,
 // no overflow); where t_ns is passed through (copy_t) they are written as 0, the stored padding value
 // of every producer.  Everything after load_sub is the same text.
-template <int MODE, bool NEXT = false, bool PCD = false, bool RULE = false, typename... REL>
+//
+// KEEPI: the output batch already holds the input's intensity column (the host knows: BatchState::
+// holds_intensity_of, or out == in), so load_sub issues no load of column 3, sub_tile no store of it, and
+// the body carries no registers for it: 24 of the 32 bytes per point move (28 of 36 with the time
+// column read).  Never with PCD, whose text sums read the intensity.  Everything else is the same text.
+struct NoColumn {};
+template <int MODE, bool NEXT = false, bool PCD = false, bool RULE = false, bool KEEPI = false, typename... REL>
 __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const DeskewArgs a, const PrepArgs pn,
                                                                          const uint32_t pre, const REL... rel) {
   constexpr bool kRel = sizeof...(REL) != 0;
   static_assert(sizeof...(REL) <= 1 && (std::is_same_v<REL, RelArgs> && ...), "REL is empty or RelArgs");
   static_assert(!kRel || (MODE == 1 && !NEXT && !PCD), "the relative variant is SLERP only, without NEXT and PCD");
+  static_assert(!(KEEPI && PCD), "the PCD text sums read the intensity column");
+  using ICol = std::conditional_t<KEEPI, NoColumn, float4>;   // the intensity group, where the kernel moves it
   const RelArgs ra{rel...};   // (null when not relative, and never read)
   span_start(a.span);
   if constexpr (NEXT) {
@@ -1453,7 +1461,7 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
   // group, an empty sub-tile's lanes the tile's first group; their results are never stored): no
   // divergent load block, so nothing makes the point loads wait for the window records, and the
   // records stay scalar loads in uniform control flow
-  auto load_sub = [&](int64_t st, const Tile& tl, int4& Tq, float4& X, float4& Y, float4& Z, float4& I) {
+  auto load_sub = [&](int64_t st, const Tile& tl, int4& Tq, float4& X, float4& Y, float4& Z, ICol& I) {
     const int g0 = (int)(st % kSub) * kBlock;
     const int g = g0 + tid;
     const int gl = g < tl.ngroups ? g : (g0 < tl.ngroups ? g0 : 0);
@@ -1473,11 +1481,11 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
     X = ld4(q);
     Y = ld4(q + kBlkPts);
     Z = ld4(q + 2 * kBlkPts);
-    I = ld4(q + 3 * kBlkPts);
+    if constexpr (!KEEPI) I = ld4(q + 3 * kBlkPts);
   };
   // one non-empty sub-tile whose points are loaded: records, per-point math, stores
   auto sub_tile = [&](const int64_t st, const Tile& tl, const FrameWin& fw_first, const int4& Tq, float4 X, float4 Y,
-                      float4 Z, const float4& I) {
+                      float4 Z, const ICol& I) {
     const int g0 = (int)(st % kSub) * kBlock;
     const int f = tl.frame;
     const int g = g0 + tid;
@@ -1584,7 +1592,7 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
       st_out(o, X);
       st_out(o + kBlkPts, Y);
       st_out(o + 2 * kBlkPts, Z);
-      st_out(o + 3 * kBlkPts, I);
+      if constexpr (!KEEPI) st_out(o + 3 * kBlkPts, I);
       if (a.copy_t) {
         int4 To = Tq;
         if constexpr (RULE) {   // padding slots: the stored 0, not the clamped ramp
@@ -1621,7 +1629,8 @@ __global__ __launch_bounds__(kBlock, kPointsWaves) void k_deskew_points(const De
     const Tile tl = ldu(a.tiles + st / kSub);
     if ((int)(st % kSub) * kBlock >= tl.ngroups) continue;  // uniform: empty sub-tile of a short tile
     int4 Tq;
-    float4 X, Y, Z, I;
+    float4 X, Y, Z;
+    ICol I;
     load_sub(st, tl, Tq, X, Y, Z, I);
     sub_tile(st, tl, w, Tq, X, Y, Z, I);
   }

@@ -139,6 +139,13 @@ static void with_rule(bool rule, F&& f) {
   else f(std::false_type{});
 }
 
+// f(std::bool_constant<KEEPI>) for a plan's per-point kernel (StepPlan::keep_i)
+template <typename F>
+static void with_keep(bool keep, F&& f) {
+  if (keep) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 // f(std::integral_constant<int, MODE>) for a plan's kernel
 template <typename F>
 static void with_mode(int mode, F&& f) {
@@ -247,6 +254,7 @@ int mc_create(int device, mc_ctx** out) {
   std::unique_ptr<mc_ctx> c(new mc_ctx());   // a failure below frees what was created so far
   c->device = device;
   if (const char* v = std::getenv("MCDESKEW_TIME_RULE")) c->time_rule = std::atoi(v) != 0;   // diagnostic
+  if (const char* v = std::getenv("MCDESKEW_KEEP_INTENSITY")) c->keep_intensity = std::atoi(v) != 0;   // diagnostic
   hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->row_d2h, hipStreamNonBlocking);
   if (e != hipSuccess) return fail(MC_ERR_HIP, "stream/event creation: %s", hipGetErrorString(e));
@@ -276,6 +284,17 @@ int mc_set_time_rule(mc_ctx* c, int enable) {
   // (speculated tables stay valid: k_prep's outputs do not depend on which kernel reads them)
   c->time_rule = enable != 0;
   return MC_OK;
+}
+
+int mc_set_keep_intensity(mc_ctx* c, int enable) {
+  CHECK_ARG(c, "ctx is NULL");
+  c->keep_intensity = enable != 0;
+  return MC_OK;
+}
+
+int mc_batch_holds_intensity_of(const mc_batch* out, const mc_batch* in) {
+  CHECK_ARG(out && in, "NULL argument");
+  return out->state.holds_intensity_of(in->uid, in->state.points_version()) ? 1 : 0;
 }
 
 int mc_set_launch(mc_ctx* c, int32_t max_grid) {
@@ -469,10 +488,11 @@ int mc_batch_set_frame_start_ns(mc_batch* b, const int64_t* s) {
 
 extern "C++" {
 namespace mcimpl {
-int batch_columns_written(mc_batch* b, unsigned what) {
+int batch_columns_written(mc_batch* b, unsigned what, const mc_batch* src) {
   if (what & kLeftQueued) b->ctx->sched.work_in_flight();
   if (what & kWrotePoints) b->state.points_written();
   if ((what & kWroteSums) && b->d_pcd_len) b->state.sums_written();
+  if ((what & kHoldsIntensity) && src) b->state.intensity_copied_from(src->uid, src->state.points_version());
   if (what & kWroteTime) b->state.time_written();
   return (what & kSpansNow) ? compute_trange(b) : MC_OK;
 }
@@ -745,6 +765,8 @@ struct StepPlan {
   int32_t kernel;   // -1: no deskew launch (no tiles); else the mode
   bool rule;        // per-point modes: the input batch is evenly timed throughout (time_rule.hpp) and the
                     // context allows it, so the launch takes the kernel that generates t_ns
+  bool keep_i;      // per-point modes, no PCD sums: out is in, or already holds in's intensity column
+                    // (begin_steps), so the launch takes the kernel that neither reads nor writes it
 };
 
 constexpr int64_t kSlerpXcdMinPoints = 200000000;
@@ -842,7 +864,10 @@ void launch_main(const StepPlan& sp, hipStream_t s, hipEvent_t e0 = nullptr, hip
       with_rule(sp.rule, [&](auto rule) {
         constexpr bool R = decltype(rule)::value;
         if (pcd) launch<k_deskew_points<M, false, true, R>>(true, sp.grid, s, e0, e1, 0u, sp.da, sp.pa, 0u);
-        else launch<k_deskew_points<M, false, false, R>>(false, sp.grid, s, e0, e1, 0u, sp.da, sp.pa, 0u);
+        else with_keep(sp.keep_i, [&](auto keep) {
+          launch<k_deskew_points<M, false, false, R, decltype(keep)::value>>(false, sp.grid, s, e0, e1, 0u, sp.da,
+                                                                             sp.pa, 0u);
+        });
       });
     }
   });
@@ -857,7 +882,10 @@ void launch_fused(const StepPlan& sp, const StepPlan& nx, hipStream_t s, hipEven
     constexpr int M = decltype(mode)::value;
     if constexpr (M == MC_MODE_FRAME) launch<k_deskew_frame_next>(true, grid, s, e0, e1, 0u, sp.da, nx.pa, pre);
     else with_rule(sp.rule, [&](auto rule) {
-      launch<k_deskew_points<M, true, false, decltype(rule)::value>>(true, grid, s, e0, e1, 0u, sp.da, nx.pa, pre);
+      with_keep(sp.keep_i, [&](auto keep) {
+        launch<k_deskew_points<M, true, false, decltype(rule)::value, decltype(keep)::value>>(true, grid, s, e0, e1,
+                                                                                              0u, sp.da, nx.pa, pre);
+      });
     });
   });
 }
@@ -867,15 +895,33 @@ void launch_fused(const StepPlan& sp, const StepPlan& nx, hipStream_t s, hipEven
 // after them, and compute_trange waits for one word of them — is every frame evenly timed? — so a call
 // that finds the spans stale synchronises once; no later call on the same time column does); plan[i] is planned for table half h0 ^ i (plan[1] only if `both`); out is about to be
 // written.
-int begin_steps(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select, int h0, bool both,
-                StepPlan* plan) {
+//
+// The intensity column (StepPlan::keep_i).  A per-point launch without PCD sums (pcd: the call has a
+// pcd_len target, the output batch's own included) need not move it when out is in, or when out still
+// holds in's column from an earlier deskew of in into out (BatchState::holds_intensity_of, asked before
+// this call's own write is announced).  A run of launches (first_full given) that finds the column not
+// held runs its first launch in full, *first_full, and the rest keeping: the plans say keep_i.
+int begin_steps(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int pose_select, int h0, bool both, bool pcd,
+                StepPlan* plan, bool* first_full = nullptr) {
   if (mode != MC_MODE_FRAME)
     if (int r = ensure_spans(in)) return r;
-  for (int i = 0; i <= (both ? 1 : 0); ++i) deskew_plan(c, in, out, mode, pose_select, h0 ^ i, &plan[i]);
+  const bool may_keep = mode != MC_MODE_FRAME && !pcd && c->keep_intensity;
+  const bool held = out == in || out->state.holds_intensity_of(in->uid, in->state.points_version());
+  if (first_full) *first_full = may_keep && !held;
+  for (int i = 0; i <= (both ? 1 : 0); ++i) {
+    deskew_plan(c, in, out, mode, pose_select, h0 ^ i, &plan[i]);
+    plan[i].keep_i = may_keep && (held || first_full != nullptr);
+  }
   // a per-point deskew that carries t_ns into another batch rewrites that batch's time column:
   // its cached [min, max] spans no longer describe it (recomputed by their next reader)
   batch_columns_written(out, kWrotePoints | (plan[0].da.copy_t ? kWroteTime : 0u));
   return MC_OK;
+}
+
+// the deskew launches of in into out announced by begin_steps are queued: every mode passes the
+// intensity column through, so out now holds in's (in place there is nothing to record)
+void intensity_passed(const mc_batch* in, mc_batch* out) {
+  if (out != in) batch_columns_written(out, mcimpl::kHoldsIntensity, in);
 }
 }  // namespace
 
@@ -902,7 +948,7 @@ int mcimpl::deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, 
   // two calls back read; the previous call's kernel reads the other half.
   const int h = c->sched.free_half();
   StepPlan sp;   // (the other half is planned only when this call speculates)
-  if (int r = begin_steps(c, in, out, mode, pose_select, h, false, &sp)) return r;
+  if (int r = begin_steps(c, in, out, mode, pose_select, h, false, pcd_len != nullptr, &sp)) return r;
   c->sched.take_half();
   sp.da.pcd_len = pcd_len;
   // Whether this call needs a k_prep at all (the previous call's launch may have prepared half h for
@@ -934,6 +980,7 @@ int mcimpl::deskew_call(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, 
     ev.keep(&c->main_ev);
     HIPCHK(hipGetLastError());
     if (pcd_len == out->d_pcd_len) batch_columns_written(out, kWroteSums);
+    intensity_passed(in, out);
     if (d.speculate) c->sched.launched_speculative(key, h);
     else c->sched.launched_plain();
   }
@@ -952,7 +999,9 @@ namespace {
 // ao: step 0's prep is an any-order packet (right behind this context's own deskew kernel, as in mc_deskew).
 // last_pcd: the last step's launch also writes the output blocks' PCD text bytes there (its output is
 // what the batch keeps; the launches before it have no PCD variant of the fused next-prep kernel).
-void issue_steps(mc_ctx* c, const StepPlan* plan, int32_t n_steps, int32_t every, int32_t* last_pcd, bool ao) {
+// first_full: step 0's launch moves the intensity column whatever the plans say (begin_steps).
+void issue_steps(mc_ctx* c, const StepPlan* plan, int32_t n_steps, int32_t every, int32_t* last_pcd, bool ao,
+                 bool first_full) {
   hipStream_t s = c->stream;
   auto sampled = [&](int32_t i) { return every > 0 && i % every == every / 2; };
   for (int32_t i = 0; i < n_steps; ++i) {
@@ -963,6 +1012,7 @@ void issue_steps(mc_ctx* c, const StepPlan* plan, int32_t n_steps, int32_t every
     }
     LaunchEvents ev(c, sampled(i));
     StepPlan sp = plan[i & 1];
+    if (i == 0 && first_full) sp.keep_i = false;
     if (ev.e0) sp.da.span = span_take(c);
     if (i + 1 < n_steps) {
       launch_fused(sp, plan[(i + 1) & 1], s, ev.e0, ev.e1);
@@ -982,10 +1032,16 @@ int deskew_steps_pipelined(mc_ctx* c, const mc_batch* in, mc_batch* out, int mod
   c->sched.forget_speculation();
   const int h0 = c->sched.free_half();
   StepPlan plan[2];
-  if (int r = begin_steps(c, in, out, mode, pose_select, h0, true, plan)) return r;
-  issue_steps(c, plan, n_steps, every, plan[0].kernel >= 0 ? out->d_pcd_len : nullptr, c->sched.prep_may_overtake());
+  bool first_full = false;
+  if (int r = begin_steps(c, in, out, mode, pose_select, h0, true, out->d_pcd_len != nullptr, plan, &first_full))
+    return r;
+  issue_steps(c, plan, n_steps, every, plan[0].kernel >= 0 ? out->d_pcd_len : nullptr, c->sched.prep_may_overtake(),
+              first_full);
   HIPCHK(hipGetLastError());
-  if (plan[0].kernel >= 0 && n_steps > 0) batch_columns_written(out, kWroteSums);
+  if (plan[0].kernel >= 0 && n_steps > 0) {
+    batch_columns_written(out, kWroteSums);
+    intensity_passed(in, out);
+  }
   c->sched.steps_issued(h0, n_steps);
   return MC_OK;
 }
@@ -1012,8 +1068,13 @@ int mc_tune_order(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
   hipStream_t s = c->stream;
   // the candidates run as the steps of mc_deskew_steps do (issue_steps: fused next-step launches);
   // plain kernels only: any PCD text sums of out go stale
+  // (and they follow the intensity rule of the caller's next calls: the very first launch in full if
+  // out does not hold in's column yet, every later one keeping)
   StepPlan plan[2];
-  if (int r = begin_steps(c, in, out, mode, pose_select, c->sched.free_half(), true, plan)) return r;
+  bool first_full = false;
+  if (int r = begin_steps(c, in, out, mode, pose_select, c->sched.free_half(), true, out->d_pcd_len != nullptr, plan,
+                          &first_full))
+    return r;
   c->sched.tuner_ran();   // whichever way this call ends, the next prep is an ordinary packet
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIPCHK(hipEventCreate(&e0));
@@ -1028,9 +1089,10 @@ int mc_tune_order(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
       plan[0].da.xcd_order = plan[1].da.xcd_order = cand;
       // the previous round's last launch may read either half (odd `launches`): the warm-up's first
       // prep is an ordinary packet, so it waits for that launch and for everything queued before it
-      issue_steps(c, plan, 2, 0, nullptr, false);   // untimed: this order's own steady state
+      issue_steps(c, plan, 2, 0, nullptr, false, first_full);   // untimed: this order's own steady state
+      first_full = false;
       e = hipEventRecord(e0, s);
-      issue_steps(c, plan, launches, 0, nullptr, true);
+      issue_steps(c, plan, launches, 0, nullptr, true, false);
       if (e == hipSuccess) e = hipEventRecord(e1, s);
       if (e == hipSuccess) e = hipEventSynchronize(e1);
       float ms = 0.f;
@@ -1041,6 +1103,7 @@ int mc_tune_order(mc_ctx* c, const mc_batch* in, mc_batch* out, int mode, int po
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
   if (e != hipSuccess) return fail(MC_ERR_HIP, "tune_order: %s", hipGetErrorString(e));
+  intensity_passed(in, out);
   double med[2];
   for (int k = 0; k < 2; ++k) {
     std::sort(t[k].begin(), t[k].end());
@@ -1170,7 +1233,9 @@ int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const doubl
   c->sched.forget_speculation();
   const int h = c->sched.free_half();
   StepPlan sp;
-  if (int r = begin_steps(c, in, out, MC_MODE_POSE_SLERP, MC_POSE_SEARCHSORTED, h, false, &sp)) return r;
+  if (int r = begin_steps(c, in, out, MC_MODE_POSE_SLERP, MC_POSE_SEARCHSORTED, h, false, out->d_pcd_len != nullptr,
+                          &sp))
+    return r;
   c->sched.take_half();
   c->sched.work_in_flight();
   {
@@ -1186,12 +1251,15 @@ int mc_deskew_relative(mc_ctx* c, const mc_batch* in, mc_batch* out, const doubl
     LaunchEvents ev(c);
     if (ev.e0) sp.da.span = span_take(c);
     with_rule(sp.rule, [&](auto rule) {
-      launch<k_deskew_points<1, false, false, decltype(rule)::value, RelArgs>>(false, sp.grid, s, ev.e0, ev.e1, 0u,
-                                                                               sp.da, sp.pa, 0u, rl);
+      with_keep(sp.keep_i, [&](auto keep) {
+        launch<k_deskew_points<1, false, false, decltype(rule)::value, decltype(keep)::value, RelArgs>>(
+            false, sp.grid, s, ev.e0, ev.e1, 0u, sp.da, sp.pa, 0u, rl);
+      });
     });
     ev.keep(&c->main_ev);
   }
   HIPCHK(hipGetLastError());
+  intensity_passed(in, out);
   return MC_OK;
 }
 

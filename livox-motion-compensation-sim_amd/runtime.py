@@ -322,6 +322,13 @@ class Context:
         loading kernels for every later launch (mc_set_time_rule).  The outputs are the same to the bit."""
         check(self.lib.mc_set_time_rule(self.handle, int(bool(enable))), "set_time_rule")
 
+    def keep_intensity(self, enable: bool = True):
+        """Let a per-point deskew into a batch that already holds the input's intensity column
+        (:meth:`Batch.holds_intensity_of`, or in place) take the kernels that neither read nor write it
+        (the default); ``False`` forces the full kernels for every later launch (mc_set_keep_intensity).
+        The outputs are the same to the byte."""
+        check(self.lib.mc_set_keep_intensity(self.handle, int(bool(enable))), "set_keep_intensity")
+
     def timing(self, enable: bool = True):
         check(self.lib.mc_timing_enable(self.handle, int(bool(enable))), "timing_enable")
 
@@ -503,6 +510,13 @@ class Batch:
         v = c_int32()
         check(self.lib.mc_batch_pcd_len_current(self.handle, ctypes.byref(v)), "pcd_len_current")
         return bool(v.value)
+
+    def holds_intensity_of(self, src: "Batch") -> bool:
+        """True when this batch's intensity column is ``src``'s as it stands: it received a deskew of
+        ``src`` and neither batch's point columns were written since (mc_batch_holds_intensity_of)."""
+        r = self.lib.mc_batch_holds_intensity_of(self.handle, src.handle)
+        check(min(r, 0), "holds_intensity_of")
+        return r == 1
 
     def padded_offsets(self) -> np.ndarray:
         o = np.zeros(self.n_frames + 1, np.int64)
