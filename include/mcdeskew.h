@@ -480,6 +480,42 @@ int mc_voxel_emit_f64(mc_ctx* ctx, double* d_rows, int32_t* d_counts, int32_t* d
 int mc_timing_read_voxel(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 int mc_voxel_release(mc_ctx* ctx);
 
+/* ---- surface normals of the voxel cloud (csrc/normals_core.hpp, normals.hpp) ---------------------
+ * The reference's viewer runs, on every cloud without normals (read_pointcloud.py:81-84),
+ *   pcd.estimate_normals(search_param=KDTreeSearchParamHybrid(radius=0.1, max_nn=30))
+ * This is that estimate for the voxel points of the live build, defined so that it is a function of
+ * the voxel set alone: the same bit for bit whatever order the points arrived in.  Per voxel i with
+ * integer cell k_i and centroid c_i (the float64 c of the voxel filter above, those exact bits), with
+ * h the build's voxel size, R = ceil(radius / h) and r2 = radius * radius; every line ONE IEEE float64
+ * operation, no contraction:
+ *   candidates  the occupied cells k_j with max_axis |k_j - k_i| <= R, i itself included (open3d counts
+ *               the query point), walked dkx, dky, dkz ascending = ascending packed key.  The window is
+ *               part of the definition: rounding of a centroid at a cell face cannot change the set.  A
+ *               window cell with an index outside [-2^20, 2^20) on any axis does not exist.
+ *   radius      u = c_j - c_i     d2 = (u.x*u.x + u.y*u.y) + u.z*u.z     a neighbour when d2 <= r2
+ *   cap         max_nn != 0 and more than max_nn neighbours: the max_nn with the smallest (d2, packed
+ *               key) are kept (the key breaks ties; a voxel's place in the output never does)
+ *   moments     over the n kept neighbours in walk order:  s += u;  P += (u.x*u.x, u.x*u.y, u.x*u.z,
+ *               u.y*u.y, u.y*u.z, u.z*u.z);  then m = s / double(n), E = P / double(n),
+ *               C = E - (m.x*m.x, m.x*m.y, m.x*m.z, m.y*m.y, m.y*m.z, m.z*m.z) = xx, xy, xz, yy, yz, zz
+ *   normal      a unit eigenvector of C for its smallest eigenvalue (a cyclic Jacobi of + - * / sqrt)
+ *   sign        with a viewpoint: n . (viewpoint - c_i) >= 0; without: the component of largest
+ *               magnitude is positive (ties: the lower axis)
+ *   curvature   max(l0, 0) / (C.xx + C.yy + C.zz) with l0 = n^T C n; 0 when the trace is <= 0
+ *   n < 3       normal (0, 0, 1), curvature 0, whatever the viewpoint (open3d's answer); C as above
+ * d_normals (M, 4) float64 nx, ny, nz, curvature and d_cov (M, 6), 16-byte aligned; d_counts (M,) = n.
+ * Rows are in the cloud's order (mc_voxel_emit_f64).  Any number of calls per build, with any radii.
+ * MC_ERR_INVALID before any launch: radius not finite or <= 0, radius / h > 4 (voxelise coarser or
+ * shrink the radius), max_nn not 0 and not in 3..64, a viewpoint that is not finite.  No successful
+ * build: MC_ERR_STATE.  M = 0: MC_OK, nothing written.  Device memory, with the voxel filter's:
+ * 36 B per voxel (the centroids, written by the first call after a build, and the capped list). */
+int mc_voxel_normals(mc_ctx* ctx, double radius, int32_t max_nn, const double* viewpoint, double* d_normals,
+                     int32_t* d_counts, double* d_cov);
+/* event time (ms) of the timed phases since the last read: ms_phase[3] = centroids (once per build),
+ * window (every voxel; with the counter reset), cap (the voxels with more than max_nn neighbours;
+ * launched only when there are some); *launches = timed regions */
+int mc_timing_read_normals(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

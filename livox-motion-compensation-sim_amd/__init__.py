@@ -23,7 +23,9 @@ Drop-in surface (reference file:line in each docstring):
                          livox_mid70_complete_simulator.py:1671-1698): encode_las / write_las from rows
                          or a Batch, read_las / read_las_batch back, records packed and unpacked on the device
   voxel                  build-added: voxel_downsample(batch or rows, voxel, origin) -> VoxelCloud, the voxel-grid
-                         filter after a global deskew, with integer sums: bit-identical on every run
+                         filter after a global deskew, with integer sums: bit-identical on every run;
+                         VoxelCloud.normals(radius, max_nn=30, viewpoint, covariance) -> VoxelNormals, the viewer's
+                         estimate_normals (read_pointcloud.py:81-84) from the live build, a function of the voxel set
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
 from . import _lib, codecs, config, coords, csim_export, dist, ingest, las, raymarch, runtime, trajectory, voxel  # noqa: F401
@@ -38,6 +40,6 @@ from .config import default_config, validate_config  # noqa: F401
 from .raymarch import LiDARSimulator  # noqa: F401
 from .runtime import Batch, Context, default_context  # noqa: F401
 from .simulator import LiDARMotionSimulator  # noqa: F401
-from .voxel import VoxelCloud, voxel_downsample  # noqa: F401
+from .voxel import VoxelCloud, VoxelNormals, voxel_downsample  # noqa: F401
 
 __version__ = "0.1.0"

@@ -134,6 +134,9 @@ _SIGS = {
     "mc_voxel_emit_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "mc_timing_read_voxel": (c_int, [c_void_p, _pd, _pi64]),
     "mc_voxel_release": (c_int, [c_void_p]),
+    # the surface normals of the voxel cloud
+    "mc_voxel_normals": (c_int, [c_void_p, c_double, c_int32, _pd, c_void_p, c_void_p, c_void_p]),
+    "mc_timing_read_normals": (c_int, [c_void_p, _pd, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

@@ -2,9 +2,11 @@
 //
 // The filter's state (the key table, the per-point slots, the per-voxel sums and what the last build
 // left for its emits) is the CtxExt in the context's voxel slot (internal.hpp): the other translation
-// units see only that hook.  mc_voxel_release frees it early; mc_destroy frees what is left.
+// units see only that hook.  mc_voxel_release frees it early; mc_destroy frees what is left.  The surface
+// normals of the built cloud (mc_voxel_normals; kernels in normals.hpp) read that state and keep theirs in it.
 #include "../../include/mcdeskew.h"
 #include "voxel.hpp"
+#include "normals.hpp"
 #include "internal.hpp"
 #include "hostutil.hpp"
 
@@ -16,6 +18,7 @@ using namespace mc;
 namespace {
 
 enum { kInsert = 0, kRank = 1, kAccumulate = 2, kFinalise = 3, kPhases = 4 };
+enum { kNrmCentroids = 0, kNrmWindow = 1, kNrmCap = 2, kNrmPhases = 3 };
 
 struct VoxState : mcimpl::CtxExt {
   // table (a power of two of slots), per-point arrays (points / chunks), per-voxel records
@@ -31,11 +34,21 @@ struct VoxState : mcimpl::CtxExt {
   bool built = false;
   int64_t M = 0;
   double h = 0.0, o[3] = {0, 0, 0};
+  int shift = 0;
+  uint32_t mask = 0;
   EventPairs ev[kPhases];
+  // the normals of the last build: its centroids by voxel (written by the first mc_voxel_normals after the
+  // build), the voxels the cap applies to and their number
+  DevBuf<double> cent;
+  bool cent_current = false;
+  DevBuf<uint32_t> capped;
+  DevBuf<uint32_t> n_capped;
+  EventPairs nrm_ev[kNrmPhases];
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
     for (auto& v : ev) ev_destroy(v);
+    for (auto& v : nrm_ev) ev_destroy(v);
   }
 };
 
@@ -56,6 +69,7 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   *n_voxels = 0;
   VoxState* s = state_of(c, true);
   s->built = false;
+  s->cent_current = false;
   s->M = 0;
   s->h = src.h;
   std::copy_n(src.o, 3, s->o);
@@ -77,6 +91,8 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   t.shift = 64 - log2cap;
   t.mask = (uint32_t)(cap - 1);
   t.meta = s->meta;
+  s->shift = t.shift;
+  s->mask = t.mask;
   const dim3 blk(kVoxBlock), pgrid((uint32_t)((lanes + kVoxBlock - 1) / kVoxBlock)), cgrid((uint32_t)n_chunks);
   {
     TimedRegion tr(c, &s->ev[kInsert], c->stream);
@@ -240,6 +256,92 @@ int mc_timing_read_voxel(mc_ctx* c, double* ms_phase, int64_t* launches) {
   return MC_OK;
 }
 
+int mc_voxel_normals(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoint, double* d_normals,
+                     int32_t* d_counts, double* d_cov) {
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(std::isfinite(radius) && radius > 0.0, "radius must be finite and > 0 (got %g)", radius);
+  CHECK_ARG(max_nn == 0 || (max_nn >= kNormalsMinNN && max_nn <= kNormalsMaxNN),
+            "max_nn must be 0 (no cap) or in %d..%d (got %d)", kNormalsMinNN, kNormalsMaxNN, max_nn);
+  if (viewpoint)
+    for (int k = 0; k < 3; ++k)
+      CHECK_ARG(std::isfinite(viewpoint[k]), "viewpoint must be finite (axis %d: %g)", k, viewpoint[k]);
+  CHECK_ARG(((uintptr_t)d_normals & 15) == 0 && ((uintptr_t)d_cov & 15) == 0, "d_normals and d_cov must be 16-byte aligned");
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_normals needs a successful mc_voxel_build_* first");
+  CHECK_ARG(radius / s->h <= (double)kNormalsMaxR,
+            "radius %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius",
+            radius, radius / s->h, s->h, kNormalsMaxR);
+  const int64_t M = s->M;
+  if (M == 0) return MC_OK;
+  CHECK_ARG(d_normals, "d_normals is NULL");
+  DeviceGuard g(c->device);
+  if (int r = ctx_reserve(c, s->cent, kNormalsCent * (size_t)M)) return r;
+  if (int r = ctx_reserve(c, s->capped, (size_t)M)) return r;
+  if (!s->n_capped) if (int r = s->n_capped.alloc(1)) return r;
+  const dim3 blk(kVoxBlock), grid((uint32_t)((M + kVoxBlock - 1) / kVoxBlock));
+  if (!s->cent_current) {
+    VoxOut o = {};
+    o.keys = s->keys; o.vslot = s->vslot; o.sums = s->sums; o.cnt = s->cnt;
+    o.M = M;
+    o.h = s->h;
+    std::copy_n(s->o, 3, o.o);
+    {
+      TimedRegion tr(c, &s->nrm_ev[kNrmCentroids], c->stream);
+      hipLaunchKernelGGL(k_nrm_centroids, grid, blk, 0, c->stream, o, s->cent.get());
+    }
+    HIPCHK(hipGetLastError());
+    s->cent_current = true;
+  }
+  NrmArgs a = {};
+  a.g.keys = s->keys; a.g.vid = s->vid; a.g.cent = s->cent;
+  a.g.shift = s->shift; a.g.mask = s->mask;
+  a.vslot = s->vslot;
+  a.M = M;
+  a.q.R = std::max(1, (int)std::ceil(radius / s->h));
+  a.q.max_nn = max_nn;
+  a.q.r2 = radius * radius;
+  a.has_viewpoint = viewpoint ? 1 : 0;
+  if (viewpoint) std::copy_n(viewpoint, 3, a.viewpoint);
+  a.normals = d_normals; a.counts = d_counts; a.cov = d_cov;
+  a.capped = s->capped; a.n_capped = s->n_capped;
+  {
+    TimedRegion tr(c, &s->nrm_ev[kNrmWindow], c->stream);
+    HIPCHK(hipMemsetAsync(s->n_capped, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_nrm_window, grid, blk, 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  // the one synchronisation: how many voxels the cap applies to (none: no third launch)
+  uint32_t n_capped = 0;
+  HIPCHK(hipMemcpyAsync(&n_capped, s->n_capped, sizeof n_capped, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((int64_t)n_capped > M) return fail(MC_ERR_STATE, "voxel normals: %u capped voxels of %lld", n_capped, (long long)M);
+  if (n_capped) {
+    {
+      TimedRegion tr(c, &s->nrm_ev[kNrmCap], c->stream);
+      hipLaunchKernelGGL(k_nrm_cap, dim3((n_capped + kNrmCapBlock - 1) / kNrmCapBlock), dim3(kNrmCapBlock), 0, c->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  return MC_OK;
+}
+
+int mc_timing_read_normals(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  int64_t total = 0;
+  for (int k = 0; k < kNrmPhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
+  if (VoxState* s = state_of(c, false)) {
+    for (int k = 0; k < kNrmPhases; ++k) {
+      int64_t n = 0;
+      if (int r = sum_events(c, s->nrm_ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
+      total += n;
+    }
+  }
+  if (launches) *launches = total;
+  return MC_OK;
+}
+
 int mc_voxel_release(mc_ctx* c) {
   if (!c) return MC_OK;
   VoxState* s = state_of(c, false);
@@ -247,6 +349,7 @@ int mc_voxel_release(mc_ctx* c) {
   DeviceGuard g(c->device);
   (void)sync_all(c);
   for (auto& v : s->ev) ev_recycle(c, v);
+  for (auto& v : s->nrm_ev) ev_recycle(c, v);
   c->ext[mcimpl::kSlotVoxel].reset();
   return MC_OK;
 }

@@ -368,6 +368,13 @@ class Context:
         check(self.lib.mc_timing_read_voxel(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_voxel")
         return {"insert_ms": ms[0], "rank_ms": ms[1], "accumulate_ms": ms[2], "finalise_ms": ms[3], "regions": n.value}
 
+    def read_timing_normals(self) -> dict:
+        """Event time (ms) of the phases of VoxelCloud.normals since the last read (mc_timing_read_normals)."""
+        ms = np.zeros(3, np.float64)
+        n = c_int64()
+        check(self.lib.mc_timing_read_normals(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_normals")
+        return {"centroids_ms": ms[0], "window_ms": ms[1], "cap_ms": ms[2], "regions": n.value}
+
     def device_buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)
 

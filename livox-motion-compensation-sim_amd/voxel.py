@@ -4,6 +4,7 @@ of a drive are accumulated into one cloud and most points re-observe the same su
 
   voxel_downsample(batch_or_rows, voxel, origin=(0, 0, 0))  -> VoxelCloud
   VoxelCloud.n_voxels, .batch(), .rows(), .point_counts(), .keys(), .close()
+  VoxelCloud.normals(radius, max_nn=30, viewpoint=None, covariance=False)  -> VoxelNormals
 
 One output point per occupied voxel: the mean of the voxel's points and of their intensities.  The
 per-voxel sums are integers (the coordinate inside its voxel in 2^-32 voxel units, the intensity in
@@ -22,12 +23,23 @@ the default origin the grids of different calls coincide.
 Refused, never dropped silently: a coordinate or (v - o) / h that is not finite, a voxel index
 outside [-2^20, 2^20), an intensity that is not finite or beyond +-65536 — ValueError naming the
 lowest refused point (frame and index for a batch, the row for rows), and nothing is returned.
+
+Surface normals (csrc/normals_core.hpp, csrc/normals.hpp; ``mc_voxel_normals``): what the reference's
+viewer computes with open3d on every cloud without normals (read_pointcloud.py:81-84), here from the live
+build and a function of the voxel set alone.  The neighbours of voxel i are the voxels of the cells within
+R = ceil(radius / h) of its cell on every axis whose centroids are within the radius (i included); above
+max_nn of them, the max_nn nearest by (d2, packed key) are kept.  Their offsets u = c_j - c_i give, summed
+in ascending key order, the covariance C = E[u u^T] - E[u] E[u]^T; the normal is a unit eigenvector of C
+for its smallest eigenvalue, the curvature its Rayleigh quotient over the trace.  Refused with ValueError:
+a radius that is not finite and > 0 or exceeds 4 h, max_nn not 0 and not in 3..64, a viewpoint that is not
+three finite numbers.
 """
 from __future__ import annotations
 
 import ctypes
 import math
 from ctypes import c_double, c_int32, c_int64
+from typing import NamedTuple
 
 import numpy as np
 
@@ -51,13 +63,49 @@ def _grid(voxel, origin):
     return h, o
 
 
+MAX_RADIUS_VOXELS = 4      # the neighbour search is a window of (2 ceil(radius / h) + 1)^3 <= 9^3 table probes
+MAX_NN = 64
+
+
+class VoxelNormals(NamedTuple):
+    """What :meth:`VoxelCloud.normals` returns, rows in the cloud's order."""
+    normals: np.ndarray             # (M, 3) float64 unit normals
+    curvature: np.ndarray           # (M,) float64 surface variation l0 / (l0 + l1 + l2)
+    counts: np.ndarray              # (M,) int32 neighbours used, the voxel itself included
+    covariance: np.ndarray | None   # (M, 6) float64 xx, xy, xz, yy, yz, zz, when asked for
+
+
+def _normals_args(radius, max_nn, viewpoint, h):
+    """(radius, max_nn, viewpoint as 3 float64 or None), checked before a device is touched."""
+    try:
+        r = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError(f"radius must be a number > 0, got {radius!r}") from None
+    if not (math.isfinite(r) and r > 0.0):
+        raise ValueError(f"radius must be finite and > 0, got {radius!r}")
+    if h is not None and r / h > MAX_RADIUS_VOXELS:
+        raise ValueError(f"radius {r!r} is {r / h:.3g} voxels of {h!r} and the search window takes at most "
+                         f"{MAX_RADIUS_VOXELS}: voxelise coarser or shrink the radius")
+    if isinstance(max_nn, bool) or not isinstance(max_nn, (int, np.integer)) or not (max_nn == 0 or 3 <= max_nn <= MAX_NN):
+        raise ValueError(f"max_nn must be 0 (no cap) or an integer in 3..{MAX_NN}, got {max_nn!r}")
+    vp = None
+    if viewpoint is not None:
+        try:
+            vp = np.ascontiguousarray(viewpoint, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"viewpoint must be three finite numbers, got {viewpoint!r}") from None
+        if vp.shape != (3,) or not np.isfinite(vp).all():
+            raise ValueError(f"viewpoint must be three finite numbers, got {viewpoint!r}")
+    return r, int(max_nn), vp
+
+
 class VoxelCloud:
     """What the last :func:`voxel_downsample` of a context left on the device.  The outputs are produced
     on demand from the per-voxel sums, any number of times; the next ``voxel_downsample`` on the same
     context (or :meth:`close`) ends this object's validity."""
 
-    def __init__(self, ctx: Context, n_voxels: int, generation: int):
-        self.ctx, self.n_voxels, self._gen = ctx, int(n_voxels), generation
+    def __init__(self, ctx: Context, n_voxels: int, generation: int, voxel: float | None = None):
+        self.ctx, self.n_voxels, self._gen, self._h = ctx, int(n_voxels), generation, voxel
 
     def _live(self):
         if self.ctx._voxel_gen != self._gen:
@@ -97,6 +145,33 @@ class VoxelCloud:
     def keys(self) -> np.ndarray:
         """(M, 3) int32: kx, ky, kz."""
         return self._emit(np.int32, 3, 2)
+
+    def normals(self, radius, max_nn: int = 30, viewpoint=None, covariance: bool = False) -> "VoxelNormals":
+        """Surface normals of the voxel points, the reference viewer's
+        ``estimate_normals(KDTreeSearchParamHybrid(radius=0.1, max_nn=30))`` (read_pointcloud.py:81-84) as a
+        function of the voxel set alone (module docstring; include/mcdeskew.h ``mc_voxel_normals``).  Rows in
+        the cloud's order, as :meth:`rows` / :meth:`keys`; any number of calls, with any radii, on one live
+        cloud.  ``max_nn`` 0: no cap.  ``viewpoint``: normals face it; None: the component of largest
+        magnitude is positive.  A voxel with fewer than three neighbours (itself included) gets (0, 0, 1) and
+        curvature 0, and its count says so."""
+        r, nn, vp = _normals_args(radius, max_nn, viewpoint, self._h)
+        self._live()
+        M = self.n_voxels
+        if M == 0:
+            return VoxelNormals(np.zeros((0, 3)), np.zeros(0), np.zeros(0, np.int32), np.zeros((0, 6)) if covariance else None)
+        ctx = self.ctx
+        bufs = [ctx.device_buffer(M * 32), ctx.device_buffer(M * 4), ctx.device_buffer(M * 48) if covariance else None]
+        try:
+            check(ctx.lib.mc_voxel_normals(ctx.handle, r, nn, ptr(vp, c_double), bufs[0].ptr, bufs[1].ptr,
+                                           bufs[2].ptr if covariance else None), "normals")
+            out = bufs[0].to_host(np.float64, count=4 * M).reshape(M, 4)
+            counts = bufs[1].to_host(np.int32, count=M)
+            cov = bufs[2].to_host(np.float64, count=6 * M).reshape(M, 6) if covariance else None
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.close()
+        return VoxelNormals(np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]), counts, cov)
 
     def close(self):
         """Give the filter's device scratch back (a later call allocates it again)."""
@@ -141,4 +216,4 @@ def voxel_downsample(src, voxel, origin=(0.0, 0.0, 0.0), context: Context | None
             d_rows.close()
     ctx._voxel_serial += 1
     ctx._voxel_gen = ctx._voxel_serial
-    return VoxelCloud(ctx, m.value, ctx._voxel_gen)
+    return VoxelCloud(ctx, m.value, ctx._voxel_gen, h)
