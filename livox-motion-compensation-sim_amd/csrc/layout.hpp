@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "unit_order.hpp"
+
 namespace mc {
 
 // Blocked batch layout: block k = points 256k .. 256k+255 holds its C columns as C
@@ -11,32 +13,6 @@ namespace mc {
 constexpr int kBlkPts = 256;
 __host__ __device__ __forceinline__ int64_t bidx(int C, int c, int64_t p) {
   return ((p >> 8) * C + c) * kBlkPts + (p & (kBlkPts - 1));
-}
-
-// XCD-aware unit order.  Workgroups are dealt round-robin over the 8 XCDs (observed; speed only,
-// never correctness): unit order b -> contiguous runs per XCD, so the 16-byte per-unit records
-// (tiles, sub-tile windows) of neighbouring units share 128-byte lines inside one XCD's L2
-// instead of each workgroup fetching its own line.  A bijection on [0, n) for any n.
-constexpr int kXcds = 8;
-template <bool ON>
-__device__ __forceinline__ int64_t xcd_unit(int64_t b, int64_t n) {
-  if (!ON) return b;
-  const int64_t x = b % kXcds, i = b / kXcds, per = n / kXcds, rem = n % kXcds;
-  return x * per + (x < rem ? x : rem) + i;
-}
-
-// Stream order of a launch over n units (workgroup b -> unit): bit 1 = the 8 contiguous XCD ranges of
-// xcd_unit<true> (else in order), bit 0 = reversed (within each range).  Codec kernels take the order
-// that starts where the previous kernel over the same batch ended (mc_batch::hot_order), while those
-// points may still sit in the 256 MB Infinity Cache.  A bijection on [0, n) for any n.
-__device__ __forceinline__ int64_t stream_unit(int order, int64_t b, int64_t n) {
-  const bool rev = (order & 1) != 0;
-  if (order & 2) {
-    const int64_t x = b % kXcds, i = b / kXcds, per = n / kXcds, rem = n % kXcds;
-    const int64_t len = per + (x < rem ? 1 : 0), start = x * per + (x < rem ? x : rem);
-    return start + (rev ? len - 1 - i : i);
-  }
-  return rev ? n - 1 - b : b;
 }
 
 // 64-bit integer minimum (HIP's min / max templates resolve int64_t arguments through float64

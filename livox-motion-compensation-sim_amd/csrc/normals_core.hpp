@@ -1,6 +1,6 @@
 // normals_core.hpp — the scalar core of the voxel cloud's surface normals (normals.hpp), on plain values so
-// the same text compiles for the device and for the host (tests/test_normals_cpu.py builds the section
-// between the NORMALS_CORE markers, after voxel_core.hpp's, with g++ -ffp-contract=off).  No HIP include.
+// the same text compiles for the device and for the host (tests/host/normals_host.cpp includes it; built with
+// g++ -ffp-contract=off).  A core header (DESIGN.md "Core headers"); needs no stand-in.  No HIP include.
 //
 // The estimate of one voxel i is a function of the voxel set alone (include/mcdeskew.h "surface normals"):
 //   candidates  the occupied cells k_j with max_axis |k_j - k_i| <= R, i itself included, walked in the
@@ -23,7 +23,6 @@
 
 namespace mc {
 
-// NORMALS_CORE_BEGIN
 constexpr int32_t kNormalsMaxR = 4;      // radius <= 4 h: a window of at most 9^3 cells
 constexpr int32_t kNormalsMinNN = 3;     // max_nn is 0 (no cap) or in [3, 64]
 constexpr int32_t kNormalsMaxNN = 64;
@@ -52,7 +51,7 @@ struct NormalsMoments {
 };
 
 // the voxel of a key: the probe sequence of the build, until the key (true) or an empty slot (false)
-MC_VOXEL_FN bool normals_find(const NormalsGrid& g, uint64_t key, uint32_t* v) {
+MC_CORE_HD bool normals_find(const NormalsGrid& g, uint64_t key, uint32_t* v) {
   uint32_t at = voxel_slot_first(key, g.shift, g.mask);
   for (;;) {
     const uint64_t cur = g.keys[at];
@@ -69,9 +68,9 @@ MC_VOXEL_FN bool normals_find(const NormalsGrid& g, uint64_t key, uint32_t* v) {
 // cell's place in the window, ((dkx + R) (2R + 1) + dky + R) (2R + 1) + dkz + R, which ascends with the
 // packed key
 template <typename Fn>
-MC_VOXEL_FN void normals_neighbours(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
+MC_CORE_HD void normals_neighbours(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
                                     Fn&& fn) {
-  MC_VOXEL_NO_CONTRACT
+  MC_CORE_NO_CONTRACT
   const int32_t W = 2 * q.R + 1;
   int32_t ix = 0;
   for (int32_t dx = -q.R; dx <= q.R; ++dx) {
@@ -102,13 +101,13 @@ MC_VOXEL_FN void normals_neighbours(const NormalsGrid& g, const int32_t ki[3], c
   }
 }
 
-MC_VOXEL_FN void normals_clear(NormalsMoments* m) {
+MC_CORE_HD void normals_clear(NormalsMoments* m) {
   for (int c = 0; c < 3; ++c) m->s[c] = 0.0;
   for (int c = 0; c < 6; ++c) m->P[c] = 0.0;
 }
 
-MC_VOXEL_FN void normals_add(NormalsMoments* m, const double u[3]) {
-  MC_VOXEL_NO_CONTRACT
+MC_CORE_HD void normals_add(NormalsMoments* m, const double u[3]) {
+  MC_CORE_NO_CONTRACT
   m->s[0] = m->s[0] + u[0];
   m->s[1] = m->s[1] + u[1];
   m->s[2] = m->s[2] + u[2];
@@ -127,13 +126,13 @@ MC_VOXEL_FN void normals_add(NormalsMoments* m, const double u[3]) {
 }
 
 // (d2, ix) before (e2, jx): the order of the cap
-MC_VOXEL_FN bool normals_before(double d2, int32_t ix, double e2, int32_t jx) {
+MC_CORE_HD bool normals_before(double d2, int32_t ix, double e2, int32_t jx) {
   return d2 < e2 || (d2 == e2 && ix < jx);
 }
 
 // The common pass: the neighbours found, and the moments of the first max_nn of them (all of them
 // without a cap).  A return above max_nn != 0 means the cap applies and *m is not the answer.
-MC_VOXEL_FN int32_t normals_gather(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
+MC_CORE_HD int32_t normals_gather(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
                                    NormalsMoments* m) {
   int32_t found = 0;
   normals_clear(m);
@@ -146,7 +145,7 @@ MC_VOXEL_FN int32_t normals_gather(const NormalsGrid& g, const int32_t ki[3], co
 
 // The cap, first pass: the (d2, ix) of the last neighbour kept, through a list of max_nn entries
 // (entry e at list[e * stride]) that holds the max_nn smallest seen so far.
-MC_VOXEL_FN void normals_select(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
+MC_CORE_HD void normals_select(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
                                 double* list_d2, uint16_t* list_ix, int32_t stride, double* last_d2, int32_t* last_ix) {
   int32_t have = 0, worst = 0;
   normals_neighbours(g, ki, ci, q, [&](int32_t ix, const double*, double d2) {
@@ -168,7 +167,7 @@ MC_VOXEL_FN void normals_select(const NormalsGrid& g, const int32_t ki[3], const
 }
 
 // The cap, second pass: the moments of the neighbours up to (last_d2, last_ix), in walk order; -> kept
-MC_VOXEL_FN int32_t normals_gather_capped(const NormalsGrid& g, const int32_t ki[3], const double ci[3],
+MC_CORE_HD int32_t normals_gather_capped(const NormalsGrid& g, const int32_t ki[3], const double ci[3],
                                           const NormalsQuery& q, double last_d2, int32_t last_ix, NormalsMoments* m) {
   int32_t kept = 0;
   normals_clear(m);
@@ -182,8 +181,8 @@ MC_VOXEL_FN int32_t normals_gather_capped(const NormalsGrid& g, const int32_t ki
 }
 
 // C = xx, xy, xz, yy, yz, zz of n >= 1 kept neighbours
-MC_VOXEL_FN void normals_covariance(const NormalsMoments& m, int32_t n, double C[6]) {
-  MC_VOXEL_NO_CONTRACT
+MC_CORE_HD void normals_covariance(const NormalsMoments& m, int32_t n, double C[6]) {
+  MC_CORE_NO_CONTRACT
   const double dn = (double)n;
   const double mx = m.s[0] / dn;
   const double my = m.s[1] / dn;
@@ -211,9 +210,9 @@ MC_VOXEL_FN void normals_covariance(const NormalsMoments& m, int32_t n, double C
 // One Jacobi rotation in the (p, q) plane of a symmetric 3x3: app, aqq, apq its entries there, arp, arq
 // those of the third row, v.p / v.q the eigenvector columns.  From the fourth sweep an off-diagonal
 // entry below 2^-53 / 100 of both its diagonal entries is set to zero.
-MC_VOXEL_FN void normals_rotate(int sweep, double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
+MC_CORE_HD void normals_rotate(int sweep, double& app, double& aqq, double& apq, double& arp, double& arq, double& v0p,
                                 double& v0q, double& v1p, double& v1q, double& v2p, double& v2q) {
-  MC_VOXEL_NO_CONTRACT
+  MC_CORE_NO_CONTRACT
   if (apq == 0.0) return;
   const double g = 100.0 * fabs(apq);
   const double ap = fabs(app);
@@ -277,8 +276,8 @@ MC_VOXEL_FN void normals_rotate(int sweep, double& app, double& aqq, double& apq
 }
 
 // a unit eigenvector of C for its smallest eigenvalue (ties: the lowest Jacobi column)
-MC_VOXEL_FN void normals_eigenvector(const double C[6], double nrm[3]) {
-  MC_VOXEL_NO_CONTRACT
+MC_CORE_HD void normals_eigenvector(const double C[6], double nrm[3]) {
+  MC_CORE_NO_CONTRACT
   double a00 = C[0], a01 = C[1], a02 = C[2], a11 = C[3], a12 = C[4], a22 = C[5];
   double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
   for (int sweep = 0; sweep < kNormalsSweeps; ++sweep) {
@@ -306,9 +305,9 @@ MC_VOXEL_FN void normals_eigenvector(const double C[6], double nrm[3]) {
 
 // out = nx, ny, nz, curvature of a voxel with centroid ci, n kept neighbours and covariance C;
 // has_viewpoint: signed towards (vx, vy, vz); else the canonical sign
-MC_VOXEL_FN void normals_finish(const double C[6], int32_t n, const double ci[3], bool has_viewpoint, double vx, double vy,
+MC_CORE_HD void normals_finish(const double C[6], int32_t n, const double ci[3], bool has_viewpoint, double vx, double vy,
                                double vz, double out[4]) {
-  MC_VOXEL_NO_CONTRACT
+  MC_CORE_NO_CONTRACT
   if (n < 3) {
     out[0] = 0.0;
     out[1] = 0.0;
@@ -369,6 +368,5 @@ MC_VOXEL_FN void normals_finish(const double C[6], int32_t n, const double ci[3]
   out[2] = e[2];
   out[3] = tr > 0.0 ? top / tr : 0.0;
 }
-// NORMALS_CORE_END
 
 }  // namespace mc

@@ -10,17 +10,12 @@
 // (Theta, t0, inv_dt and tf are unchanged).  Quaternions are (x, y, z, w), as PoseSeg holds them.
 #pragma once
 
-#if defined(__HIPCC__)
-#define MC_RELFOLD_FN __host__ __device__ __forceinline__
-#else
-#define MC_RELFOLD_FN inline
-#endif
+#include "core_fn.hpp"
 
 namespace mc {
 
 // o = conj(r) (x) q (Hamilton product): R(o) = R(r)^T R(q)
-// REL_FOLD_BEGIN
-MC_RELFOLD_FN void quat_conj_mul(const double r[4], const double q[4], double o[4]) {
+MC_CORE_HD void quat_conj_mul(const double r[4], const double q[4], double o[4]) {
   const double ax = -r[0], ay = -r[1], az = -r[2], aw = r[3];
   o[0] = aw * q[0] + ax * q[3] + ay * q[2] - az * q[1];
   o[1] = aw * q[1] - ax * q[2] + ay * q[3] + az * q[0];
@@ -29,7 +24,7 @@ MC_RELFOLD_FN void quat_conj_mul(const double r[4], const double q[4], double o[
 }
 
 // o = R(r)^T v: v rotated by conj(r), v + 2 (w t + u x t) with u = -r.xyz, t = u x v (slerp_core's form)
-MC_RELFOLD_FN void quat_rot_inv(const double r[4], const double v[3], double o[3]) {
+MC_CORE_HD void quat_rot_inv(const double r[4], const double v[3], double o[3]) {
   const double ux = -r[0], uy = -r[1], uz = -r[2], w = r[3];
   const double tx = uy * v[2] - uz * v[1];
   const double ty = uz * v[0] - ux * v[2];
@@ -41,7 +36,7 @@ MC_RELFOLD_FN void quat_rot_inv(const double r[4], const double v[3], double o[3
 
 // the record (q0, v, p0, dp) of one pose segment, in place, into the frame of (q_ref, pos_ref); the
 // cancellation p0 - pos_ref happens here, once per record, in float64
-MC_RELFOLD_FN void rel_fold(const double q_ref[4], const double pos_ref[3], double q0[4], double v[4], double p0[3],
+MC_CORE_HD void rel_fold(const double q_ref[4], const double pos_ref[3], double q0[4], double v[4], double p0[3],
                             double dp[3]) {
   const double a[4] = {q0[0], q0[1], q0[2], q0[3]}, b[4] = {v[0], v[1], v[2], v[3]};
   const double d[3] = {p0[0] - pos_ref[0], p0[1] - pos_ref[1], p0[2] - pos_ref[2]};
@@ -51,6 +46,5 @@ MC_RELFOLD_FN void rel_fold(const double q_ref[4], const double pos_ref[3], doub
   quat_rot_inv(q_ref, d, p0);
   quat_rot_inv(q_ref, e, dp);
 }
-// REL_FOLD_END
 
 }  // namespace mc

@@ -17,11 +17,7 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define MC_TIME_RULE_FN __host__ __device__ __forceinline__
-#else
-#define MC_TIME_RULE_FN inline
-#endif
+#include "core_fn.hpp"
 
 namespace mc {
 
@@ -35,17 +31,16 @@ struct TimeRule {
 };
 static_assert(sizeof(TimeRule) == 16, "one s_load_dwordx4");
 
-// TIME_RULE_BEGIN
 // the step of a frame whose first two stored times are a, b
-MC_TIME_RULE_FN int32_t time_rule_step(int32_t a, int32_t b) { return (int32_t)((uint32_t)b - (uint32_t)a); }
+MC_CORE_HD int32_t time_rule_step(int32_t a, int32_t b) { return (int32_t)((uint32_t)b - (uint32_t)a); }
 
 // the time the rule generates for frame-local index i (0 <= i < 2^32; only its low 32 bits matter)
-MC_TIME_RULE_FN int32_t time_rule_at(int32_t t0, int32_t dt, int64_t i) {
+MC_CORE_HD int32_t time_rule_at(int32_t t0, int32_t dt, int64_t i) {
   return (int32_t)((uint32_t)t0 + (uint32_t)(uint64_t)i * (uint32_t)dt);
 }
 
 // does the stored time t of frame-local index i follow the rule?
-MC_TIME_RULE_FN bool time_rule_holds(int32_t t0, int32_t dt, int64_t i, int32_t t) {
+MC_CORE_HD bool time_rule_holds(int32_t t0, int32_t dt, int64_t i, int32_t t) {
   return time_rule_at(t0, dt, i) == t;
 }
 
@@ -58,6 +53,5 @@ inline int time_rule_frame(const int32_t* t, int64_t n, int32_t* t0, int32_t* dt
     if (!time_rule_holds(*t0, *dt, i, t[i])) return 0;
   return 1;
 }
-// TIME_RULE_END
 
 }  // namespace mc

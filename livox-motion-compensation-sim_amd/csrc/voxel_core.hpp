@@ -1,6 +1,6 @@
 // voxel_core.hpp — the scalar core of the voxel-grid filter (voxel.hpp), on plain values so the same
-// text compiles for the device and for the host (tests/test_voxel_cpu.py builds the section between
-// the VOXEL_CORE markers with g++ -ffp-contract=off).  No HIP include.
+// text compiles for the device and for the host (tests/host/voxel_host.cpp includes it; built with
+// g++ -ffp-contract=off).  A core header (DESIGN.md "Core headers"); needs no stand-in.  No HIP include.
 //
 // Every line of floating-point arithmetic is ONE IEEE float64 operation, never contracted:
 //   a = double(v) - o     g = a / h     k = floor(g)     f = g - k   (f may round up to 1.0)
@@ -16,20 +16,10 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define MC_VOXEL_FN __host__ __device__ __forceinline__
-#else
-#define MC_VOXEL_FN inline
-#endif
-#if defined(__clang__)
-#define MC_VOXEL_NO_CONTRACT _Pragma("clang fp contract(off)")
-#else
-#define MC_VOXEL_NO_CONTRACT
-#endif
+#include "core_fn.hpp"
 
 namespace mc {
 
-// VOXEL_CORE_BEGIN
 constexpr int32_t kVoxelKeyMin = -(1 << 20);      // keys in [-2^20, 2^20): 21 bits per axis
 constexpr int32_t kVoxelKeyEnd = 1 << 20;
 constexpr double kVoxelFrac = 4294967296.0;       // 2^32: the fixed point of a coordinate inside its voxel
@@ -45,11 +35,11 @@ struct VoxelPoint {
   int32_t bad;   // 1: refused (k, Q and QI are 0)
 };
 
-MC_VOXEL_FN bool voxel_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN
+MC_CORE_HD bool voxel_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN
 
 // one point: coordinates v (already float64), intensity, voxel size h > 0, origin o
-MC_VOXEL_FN VoxelPoint voxel_quantise(const double v[3], double intensity, double h, const double o[3]) {
-  MC_VOXEL_NO_CONTRACT
+MC_CORE_HD VoxelPoint voxel_quantise(const double v[3], double intensity, double h, const double o[3]) {
+  MC_CORE_NO_CONTRACT
   VoxelPoint r;
   r.bad = 0;
   for (int c = 0; c < 3; ++c) {
@@ -73,11 +63,11 @@ MC_VOXEL_FN VoxelPoint voxel_quantise(const double v[3], double intensity, doubl
 }
 
 // 63-bit key: 21 bits per axis, x highest; bit 63 stays clear (kVoxelEmpty has it set)
-MC_VOXEL_FN uint64_t voxel_pack(const int32_t k[3]) {
+MC_CORE_HD uint64_t voxel_pack(const int32_t k[3]) {
   return ((uint64_t)(uint32_t)(k[0] - kVoxelKeyMin) << 42) | ((uint64_t)(uint32_t)(k[1] - kVoxelKeyMin) << 21) |
          (uint64_t)(uint32_t)(k[2] - kVoxelKeyMin);
 }
-MC_VOXEL_FN void voxel_unpack(uint64_t key, int32_t k[3]) {
+MC_CORE_HD void voxel_unpack(uint64_t key, int32_t k[3]) {
   k[0] = (int32_t)((key >> 42) & 0x1FFFFFu) + kVoxelKeyMin;
   k[1] = (int32_t)((key >> 21) & 0x1FFFFFu) + kVoxelKeyMin;
   k[2] = (int32_t)(key & 0x1FFFFFu) + kVoxelKeyMin;
@@ -88,19 +78,19 @@ MC_VOXEL_FN void voxel_unpack(uint64_t key, int32_t k[3]) {
 // the per-point slot array, and a table of 2^32 slots (2^30 < N < 2^31 points) has a slot of that
 // index; the sequence passes over it, leaving 2^32 - 1 >= 2 N usable slots.
 constexpr uint32_t kVoxelNoSlot = 0xFFFFFFFFu;
-MC_VOXEL_FN uint32_t voxel_slot_next(uint32_t at, uint32_t mask) {
+MC_CORE_HD uint32_t voxel_slot_next(uint32_t at, uint32_t mask) {
   const uint32_t n = (at + 1u) & mask;
   return n == kVoxelNoSlot ? 0u : n;
 }
-MC_VOXEL_FN uint32_t voxel_slot_first(uint64_t key, int shift, uint32_t mask) {
+MC_CORE_HD uint32_t voxel_slot_first(uint64_t key, int shift, uint32_t mask) {
   const uint32_t at = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> shift) & mask;
   return at == kVoxelNoSlot ? 0u : at;
 }
 
 // one voxel: out = cx, cy, cz, intensity (n >= 1)
-MC_VOXEL_FN void voxel_finalise(const int32_t k[3], const int64_t S[3], int64_t SI, int64_t n, double h,
+MC_CORE_HD void voxel_finalise(const int32_t k[3], const int64_t S[3], int64_t SI, int64_t n, double h,
                                 const double o[3], double out[4]) {
-  MC_VOXEL_NO_CONTRACT
+  MC_CORE_NO_CONTRACT
   const double dn = (double)n;
   for (int c = 0; c < 3; ++c) {
     const double m = (double)S[c] / dn;
@@ -112,6 +102,5 @@ MC_VOXEL_FN void voxel_finalise(const int32_t k[3], const int64_t S[3], int64_t 
   const double mi = (double)SI / dn;
   out[3] = mi * kVoxelIntInv;
 }
-// VOXEL_CORE_END
 
 }  // namespace mc

@@ -1,8 +1,7 @@
-// Host build of the device text formatters behind the CSIM exports: the "%.6f" formatter of
-// livox-motion-compensation-sim_amd/csrc/codecs.hpp (FMT6_SECTION: `struct Fmt6` to `struct PcdArgs`)
-// and the "%.0f" formatter and line-descriptor prepare / emit of csrc/csim_codecs.hpp (CSIM_SECTION:
-// `u64_digits` to the end-of-section marker), spliced in by tests/test_csim_text_host.py, with host
-// stand-ins for the few device builtins they use.  Every value is compared with the C library's
+// Host build of the device text formatters behind the CSIM exports: the "%.6f" formatter
+// (csrc/fmt6_core.hpp) and the "%.0f" formatter and line-descriptor prepare / emit
+// (csrc/csim_text_core.hpp, which includes it), behind the host stand-ins for the few device builtins
+// they use, for tests/test_csim_text_host.py.  Every value is compared with the C library's
 // correctly rounded snprintf("%.0f") / ("%.6f") (the same digits as Python's formatting; a NaN prints
 // "nan" whatever its sign, as Python does), then whole lines of the three descriptors (PCD, XYZ, CSV)
 // are emitted back to back into a guarded buffer and compared.  Prints "bad <count>"; exit status
@@ -20,20 +19,8 @@
 #include <string>
 #include <vector>
 
-#define __device__
-#define __forceinline__ inline
-#define __noinline__
-static inline long long __double_as_longlong(double v) { long long b; std::memcpy(&b, &v, 8); return b; }
-static inline uint32_t __umul24(uint32_t a, uint32_t b) { return (a & 0xffffffu) * (b & 0xffffffu); }
-using std::fabs;
-using std::floor;
-using std::fma;
-using std::signbit;
-
-namespace mc {
-// FMT6_SECTION
-// CSIM_SECTION
-}  // namespace mc
+#include "device_standins.hpp"
+#include "csim_text_core.hpp"
 using namespace mc;
 
 static int bad = 0;

@@ -1,7 +1,5 @@
-// Host build of the device text-token parser behind the ingest decoders: the section of
-// livox-motion-compensation-sim_amd/csrc/ingest.hpp from `struct IngestTok {` to the end-of-section
-// marker (TOKEN_SECTION), spliced in by tests/test_ingest_host.py, with host stand-ins for the device
-// qualifiers.  Every in-window token is compared bit for bit with the C library's correctly rounded
+// Host build of the device text-token parser behind the ingest decoders (csrc/ingest_token_core.hpp), for
+// tests/test_ingest_host.py.  Every in-window token is compared bit for bit with the C library's correctly rounded
 // strtod (Python's float()); out-of-window tokens must be flagged and carry no value.  argv[1] =
 // random tokens per (significant digits, fractional digits) pair.  Prints "bad <count>"; exit status
 // = min(count, 255).
@@ -17,13 +15,7 @@
 #include <string>
 #include <vector>
 
-#define __device__
-#define __forceinline__ inline
-using std::ldexp;
-
-namespace mc {
-// TOKEN_SECTION
-}  // namespace mc
+#include "ingest_token_core.hpp"
 using namespace mc;
 
 static int bad = 0;

@@ -1,6 +1,5 @@
-// Host build of the device "%.6f" line writer in livox-motion-compensation-sim_amd/csrc/codecs.hpp
-// (the section from `struct PcdFast` to `kPcdSlowTile`, spliced in by tests/test_pcd_formatter_host.py
-// at FORMATTER_SECTION) with host stand-ins for the gfx950 intrinsics it uses.  Every line of a
+// Host build of the device "%.6f" line writer (csrc/pcd_line_core.hpp) behind the host stand-ins for the
+// gfx950 intrinsics it uses, for tests/test_pcd_formatter_host.py and tests/test_sanitizers.py.  Every line of a
 // 256-line tile is OR-ed in reverse lane order into a zeroed buffer 16 bytes in (as the kernel's
 // pcd_tile_text does), at a tile offset modulo 16, as the kernel's lanes may interleave; the text is
 // compared with the C library's correctly rounded "%.6f" (the same digits as Python's formatting) and
@@ -14,39 +13,13 @@
 #include <string>
 #include <vector>
 
-#define __device__
-#define __forceinline__ inline
-#define __noinline__
-#define __ATOMIC_RELAXED 0
-#define __HIP_MEMORY_SCOPE_WORKGROUP 0
-// ds_or_b64 (an LDS atomic OR): the host's plain read-modify-write
-template <class T>
-static inline T __hip_atomic_fetch_or(T* p, T v, int, int) {
-  T o;
-  std::memcpy(&o, p, sizeof o);
-  const T n = o | v;
-  std::memcpy(p, &n, sizeof n);
-  return o;
-}
-static inline uint32_t __umul24(uint32_t a, uint32_t b) { return (a & 0xffffffu) * (b & 0xffffffu); }
-// v_mul_i32_i24: the low 24 bits of each operand as signed integers
-static inline int __mul24(int a, int b) {
-  const int64_t x = (int64_t)(int32_t)((uint32_t)a << 8) >> 8, y = (int64_t)(int32_t)((uint32_t)b << 8) >> 8;
-  return (int)(uint32_t)(uint64_t)(x * y);
-}
-// v_perm_b32: byte i of the result = byte sel[i] of {s0:s1} (0-3 = s1, 4-7 = s0), 12 -> 0x00
-static inline uint32_t __builtin_amdgcn_perm(uint32_t s0, uint32_t s1, uint32_t sel) {
-  const uint64_t v = ((uint64_t)s0 << 32) | s1;
-  uint32_t r = 0;
-  for (int i = 0; i < 4; ++i) {
-    const uint32_t c = (sel >> (8 * i)) & 0xffu;
-    const uint32_t b = c < 8 ? (uint32_t)(v >> (8 * c)) & 0xffu : (c == 12 ? 0u : 0xffu);
-    r |= b << (8 * i);
-  }
-  return r;
-}
-// pk_tens_units (codecs.hpp, outside the spliced section): per 16-bit lane
-static inline void pk_tens_units(uint32_t v, uint32_t& t, uint32_t& u) {
+#include "device_standins.hpp"
+#include "pcd_line_core.hpp"
+
+// what the core leaves to the including unit (codecs.hpp on the device)
+namespace mc {
+// pk_tens_units (codecs.hpp): per 16-bit lane
+void pk_tens_units(uint32_t v, uint32_t& t, uint32_t& u) {
   t = u = 0;
   for (int l = 0; l < 2; ++l) {
     const uint32_t x = (v >> (16 * l)) & 0xffffu;
@@ -55,17 +28,10 @@ static inline void pk_tens_units(uint32_t v, uint32_t& t, uint32_t& u) {
     u |= ((x - q * 10u) & 0xffffu) << (16 * l);
   }
 }
-struct alignas(16) uint4 { uint32_t x, y, z, w; };   // the kernel's 16-byte text chunks
-using std::fma;
-using std::signbit;
-using std::rint;
 struct CodecFrames { const double* aos; };
-static inline void codec_point(const CodecFrames& s, int32_t, int64_t row, double c[4]) {
+void codec_point(const CodecFrames& s, int32_t, int64_t row, double c[4]) {
   for (int k = 0; k < 4; ++k) c[k] = s.aos[4 * row + k];
 }
-
-namespace mc {
-// FORMATTER_SECTION
 }  // namespace mc
 using namespace mc;
 

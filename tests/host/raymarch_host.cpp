@@ -1,6 +1,6 @@
-// The per-pair core of the ray-march scanner (csrc/raymarch.hpp, the section between its CORE
-// markers) compiled for the CPU: tests/test_raymarch_cpu.py splices that section in below, builds
-// this file with -fsanitize=address,undefined -ffp-contract=off and runs it on the golden cases.
+// The per-pair core of the ray-march scanner (csrc/raymarch_core.hpp) compiled for the CPU:
+// tests/test_raymarch_cpu.py builds this file with -fsanitize=address,undefined -ffp-contract=off and
+// runs it on the golden cases.
 //
 // Input file (little-endian): int64 F, n_rays, K, E; double step; steps[K]; dirs[n_rays][3];
 // scene xyz[E][3]; int64 object[E]; then per frame origin[3], R[9].
@@ -14,7 +14,7 @@
 #include <stdint.h>
 #include <vector>
 
-// RAYMARCH_CORE
+#include "raymarch_core.hpp"
 
 using namespace mcray;
 

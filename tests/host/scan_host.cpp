@@ -1,7 +1,6 @@
-// The decision core of the scene scanner (csrc/scan.hpp, the section between its CORE markers:
-// ScanParams .. scan_visible) compiled for the CPU: tests/test_scan_edges_cpu.py splices that section
-// in below, builds this file with -fsanitize=address,undefined -ffp-contract=off and runs it on the
-// edge scenes of tests/scanedges.py.
+// The decision core of the scene scanner (csrc/scan_core.hpp: ScanParams .. scan_visible) compiled for
+// the CPU: tests/test_scan_edges_cpu.py builds this file with -fsanitize=address,undefined
+// -ffp-contract=off and runs it on the edge scenes of tests/scanedges.py.
 //
 // Input file (little-endian doubles): the number of cases, then per case range_min, range_max,
 // fov_horizontal, fov_vertical (the config's values; prepared below as mc_scan_count prepares them);
@@ -16,17 +15,15 @@
 #include <stdint.h>
 #include <vector>
 
-#define __device__
-#define __forceinline__ inline
-#define __noinline__
-
+// the exact tier's calls, counted: defined after <math.h> and before the core, whose text they rename
 static int g_exact = 0;
 static double counted_atan2(double y, double x) { ++g_exact; return atan2(y, x); }
 static double counted_asin(double x) { ++g_exact; return asin(x); }
 #define atan2 counted_atan2
 #define asin counted_asin
 
-// SCAN_CORE
+#include "scan_core.hpp"
+using namespace mc;
 
 static std::vector<double> read_n(FILE* f, size_t n) {
   std::vector<double> v(n);

@@ -1,6 +1,5 @@
-// Host build of the scalar core of the voxel-grid filter: the section of
-// livox-motion-compensation-sim_amd/csrc/voxel_core.hpp between the VOXEL_CORE_BEGIN / VOXEL_CORE_END
-// marker comments (VOXEL_CORE), spliced in by tests/test_voxel_cpu.py.  Built with -ffp-contract=off.
+// Host build of the scalar core of the voxel-grid filter (csrc/voxel_core.hpp), for tests/test_voxel_cpu.py.
+// Built with -ffp-contract=off.
 // The harness computes; the comparison with tests/voxel.py is the test's, bit for bit.
 //   voxel_host quant <in> <out>   in: h, origin[3] (4 f64), then rows x, y, z, intensity (4 f64)
 //                                 out: per row k[3] (i32), bad (i32), Q[3], QI (i64), key (u64),
@@ -16,12 +15,7 @@
 #include <cstring>
 #include <vector>
 
-#define MC_VOXEL_FN inline
-#define MC_VOXEL_NO_CONTRACT
-
-namespace mc {
-// VOXEL_CORE
-}  // namespace mc
+#include "voxel_core.hpp"
 using namespace mc;
 
 static std::vector<uint8_t> slurp(const char* path) {

@@ -2,12 +2,11 @@
 g++ under ASan/UBSan, stand-alone: tests/host/batch_state_host.cpp drives scripted event sequences and
 checks every decision against the rules written in the header.  No GPU, no library."""
 import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
+import hostbuild
+from hostbuild import CSRC
 
 SCENARIOS = [
     "three_identical_calls",      # (prep, ordinary) / (prep, any-order, speculate) / hit: 2 preps for 3 calls
@@ -26,13 +25,8 @@ SCENARIOS = [
 
 @pytest.fixture(scope="module")
 def host_run(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("batch_state") / "batch_state_host"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-I", CSRC,
-                        os.path.join(ROOT, "tests", "host", "batch_state_host.cpp"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    exe = hostbuild.build(tmp_path_factory.mktemp("batch_state"), "batch_state_host.cpp", "-Wall", "-Werror", sanitize=True)
+    return hostbuild.run(exe, timeout=60)
 
 
 def test_every_scenario_ran_clean(host_run):

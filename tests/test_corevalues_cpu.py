@@ -1,29 +1,23 @@
 """The value classes of tests/corevalues.py through the g++ builds of the scalar cores (no GPU): the
-"%.6f" / "%.0f" formatters, the text token parser and the LAS record cores, spliced into the harnesses
-of tests/host/ as the existing host tests splice them, fed from files and compared here with
+"%.6f" / "%.0f" formatters, the text token parser and the LAS record cores, included by the harnesses
+of tests/host/ as the existing host tests build them, fed from files and compared here with
 "%.6f" % v / "%.0f" % v, float(token) and tests/las.py.  The branch predicates of corevalues.py count
 how many inputs reach each branch of each core, and the counts are asserted: a class that stops
 reaching its branch fails here, before a GPU sees the generator.  tests/test_gpu_corevalues.py sends the
 same classes through the kernels; if it fails while this passes, the device compile is at fault, not
 the algorithm."""
 import collections
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import corevalues as CV
 import csimexport as CE
+import hostbuild
 import ingest as ING
 import las as LAS
-from test_csim_text_host import section
-from test_ingest_host import token_section
-from test_las_host import DEC_OUT, ENC_OUT, core
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tests", "host")
+from test_las_host import DEC_OUT, ENC_OUT
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 
@@ -31,32 +25,17 @@ N_ROWS = 60_000      # formatter rows (x 5 columns), the rows the GPU test encod
 SEED = 20240611
 
 
-def build(tmp, name, code, *flags):
-    cpp = tmp / f"{name}.cpp"
-    cpp.write_text(code)
-    exe = tmp / name
-    r = subprocess.run(["g++", "-O2", "-std=c++17", *flags, str(cpp), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def exes(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("corevalues")
-    text = open(os.path.join(HOST, "csim_text_host.cpp")).read()
-    text = text.replace("// FMT6_SECTION", section("codecs.hpp", "struct Fmt6 {", "struct PcdArgs {"))
-    text = text.replace("// CSIM_SECTION", section("csim_codecs.hpp", "__device__ __forceinline__ int u64_digits",
-                                                   "// (end of the formatter section"))
-    tok = open(os.path.join(HOST, "ingest_host.cpp")).read().replace("// TOKEN_SECTION", token_section())
-    las = open(os.path.join(HOST, "las_host.cpp")).read().replace("// LAS_CORE\n", core())
-    return tmp, build(tmp, "csim_text", text), build(tmp, "ingest", tok), build(tmp, "las", las, "-ffp-contract=off")
+    return (tmp, hostbuild.build(tmp, "csim_text_host.cpp"), hostbuild.build(tmp, "ingest_host.cpp"),
+            hostbuild.build(tmp, "las_host.cpp", "-ffp-contract=off"))
 
 
 def run(exe, tmp, mode, data):
     src, dst = tmp / "in.bin", tmp / "out.bin"
     src.write_bytes(data)
-    r = subprocess.run([str(exe), mode, str(src), str(dst)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    hostbuild.run(exe, mode, src, dst, timeout=120)
     return dst.read_bytes()
 
 

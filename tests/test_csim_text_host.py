@@ -1,36 +1,17 @@
 """The device text formatters behind the CSIM exports (DataExporter._export_pcd / _xyz / _csv,
 CSIM:1643-1715) compiled for the host with g++ and checked against the C library's correctly rounded
-formatting: the kernel's own source — the "%.6f" formatter of codecs.hpp and the "%.0f" formatter and
-line-descriptor prepare / emit of csim_codecs.hpp — spliced into tests/host/csim_text_host.cpp and
+formatting: the kernel's own source — the "%.6f" formatter of fmt6_core.hpp and the "%.0f" formatter and
+line-descriptor prepare / emit of csim_text_core.hpp — included by tests/host/csim_text_host.cpp and
 exercised on this CPU (no GPU): random doubles over every exponent up to 2^107, the planted "%.0f" and
 "%.6f" ties, +-0, NaN / inf, and whole PCD / XYZ / CSV lines."""
-import os
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
-HARNESS = os.path.join(ROOT, "tests", "host", "csim_text_host.cpp")
-
-
-def section(name: str, start: str, end: str) -> str:
-    src = open(os.path.join(CSRC, name)).read()
-    return src[src.index(start):src.index(end)]
+import hostbuild
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_text_formatters_match_printf(tmp_path):
-    code = open(HARNESS).read()
-    code = code.replace("// FMT6_SECTION", section("codecs.hpp", "struct Fmt6 {", "struct PcdArgs {"))
-    code = code.replace("// CSIM_SECTION", section("csim_codecs.hpp", "__device__ __forceinline__ int u64_digits",
-                                                   "// (end of the formatter section"))
-    cpp = tmp_path / "csim_text.cpp"
-    cpp.write_text(code)
-    exe = tmp_path / "csim_text"
-    r = subprocess.run(["g++", "-O2", "-std=c++17", str(cpp), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([str(exe), "200000"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout[-3000:]
+    r = hostbuild.run(hostbuild.build(tmp_path, "csim_text_host.cpp"), 200000, timeout=120)
     assert "bad 0" in r.stdout

@@ -7,17 +7,14 @@ import ctypes
 import os
 import shutil
 import struct
-import subprocess
 from ctypes import c_float, c_int, c_int32, c_int64, c_uint8, c_uint64
 
 import numpy as np
 import pytest
 
+import hostbuild
 import ingest as ING
 from conftest import golden, pkg
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
 
 
 def files():
@@ -135,20 +132,14 @@ def test_index_refuses_another_format_or_frame_count():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_walker_stand_alone_under_asan_ubsan(tmp_path):
-    exe = tmp_path / "ingest_index_host"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", f"-I{CSRC}", os.path.join(ROOT, "tests", "host", "ingest_index_host.cpp"),
-                    os.path.join(CSRC, "ingest_index.cpp"), "-o", str(exe)], check=True, capture_output=True, text=True)
+    exe = hostbuild.build(tmp_path, "ingest_index_host.cpp", os.path.join(hostbuild.CSRC, "ingest_index.cpp"), sanitize=True)
     paths, want = [], []
     for i, (name, data) in enumerate(list(files().items()) + sorted(malformed().items())):
         p = tmp_path / f"case_{i:02d}.bin"
         p.write_bytes(data)
         paths.append(str(p))
         want.append(name in files())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([str(exe), *paths], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    r = hostbuild.run(exe, *paths)
     assert "contradictions 0" in r.stdout
     lines = {ln.split(" ", 1)[0]: ln.split(" ")[1] for ln in r.stdout.splitlines() if ln.startswith(str(tmp_path))}
     for p, ok in zip(paths, want):

@@ -2,13 +2,9 @@
 points_version) compiled for the host with g++ under ASan/UBSan, stand-alone:
 tests/host/keep_intensity_host.cpp drives the events of deskews and of the other writers and checks every
 answer against the rule written in the header.  No GPU, no library."""
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
+import hostbuild
 
 SCENARIOS = [
     "held_after_the_event",
@@ -24,13 +20,8 @@ SCENARIOS = [
 
 @pytest.fixture(scope="module")
 def host_run(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("keep_intensity") / "keep_intensity_host"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                        "-fno-sanitize-recover=all", "-I", CSRC,
-                        os.path.join(ROOT, "tests", "host", "keep_intensity_host.cpp"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    exe = hostbuild.build(tmp_path_factory.mktemp("keep_intensity"), "keep_intensity_host.cpp", "-Wall", "-Werror", sanitize=True)
+    return hostbuild.run(exe, timeout=60)
 
 
 def test_every_scenario_ran_clean(host_run):

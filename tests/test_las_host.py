@@ -1,57 +1,40 @@
-"""The per-record cores of the LAS kernels (csrc/las.hpp between the LAS_CORE_BEGIN / LAS_CORE_END
-marker comments: las_encode_rec, las_decode_rec, las_time_ns) compiled for the host with g++ and
-compared bit for bit with the numpy restatement of tests/las.py — the kernel's own source spliced
-into tests/host/las_host.cpp and run on this CPU (no GPU).  Encode: the rounding ties, both int32 edges
+"""The per-record cores of the LAS kernels (csrc/las_core.hpp: las_encode_rec, las_decode_rec,
+las_time_ns) compiled for the host with g++ and
+compared bit for bit with the numpy restatement of tests/las.py — the kernel's own source included
+by tests/host/las_host.cpp and run on this CPU (no GPU).  Encode: the rounding ties, both int32 edges
 +-1 ulp of the quotient, -0.0, denormals, NaN and +-inf (flagged), intensities at both ends.  Decode:
 20 000 random full-range int32 X at scale 0.001 / offset 500000.0, where a fused multiply-add changes
 the result of over 1 000 rows (counted exactly with fractions.Fraction) — and a mutant of the harness
 that fuses them must fail the comparison."""
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import las as LAS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
-HARNESS = os.path.join(ROOT, "tests", "host", "las_host.cpp")
 UNFUSED = "  return p + off;\n"
 FUSED = "  return fma((double)X, scale, off);\n"
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 
 
-def core() -> str:
-    src = open(os.path.join(CSRC, "las.hpp")).read()
-    return src[src.index("// LAS_CORE_BEGIN"):src.index("// LAS_CORE_END")]
-
-
-def build(tmp, name, section):
-    cpp = tmp / f"{name}.cpp"
-    cpp.write_text(open(HARNESS).read().replace("// LAS_CORE\n", section))
-    exe = tmp / name
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", str(cpp), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
-
-
 @pytest.fixture(scope="module")
 def exes(tmp_path_factory):
+    """The harness, and the harness as the compiler reads it with las_unscale's two roundings fused."""
     tmp = tmp_path_factory.mktemp("las_host")
-    section = core()
-    assert section.count(UNFUSED) == 1
-    return tmp, build(tmp, "las_host", section), build(tmp, "las_host_fma", section.replace(UNFUSED, FUSED))
+    text = hostbuild.preprocessed("las_host.cpp", "-ffp-contract=off")
+    assert text.count(UNFUSED) == 1
+    mutant = tmp / "las_host_fma.ii"
+    mutant.write_text(text.replace(UNFUSED, FUSED))
+    return tmp, hostbuild.build(tmp, "las_host.cpp", "-ffp-contract=off"), hostbuild.build(tmp, mutant, "-ffp-contract=off")
 
 
 def run(exe, tmp, mode, head, body):
     src, dst = tmp / "in.bin", tmp / "out.bin"
     src.write_bytes(head + body)
-    r = subprocess.run([str(exe), mode, str(src), str(dst)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    hostbuild.run(exe, mode, src, dst, timeout=120)
     return dst.read_bytes()
 
 

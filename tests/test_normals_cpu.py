@@ -1,5 +1,5 @@
-"""The surface normals of a voxel cloud without a GPU: (1) the scalar core of csrc/normals_core.hpp (the section
-between its NORMALS_CORE markers, after voxel_core.hpp's) spliced into tests/host/normals_host.cpp, built with
+"""The surface normals of a voxel cloud without a GPU: (1) the scalar core of csrc/normals_core.hpp (on top of
+voxel_core.hpp's), included by tests/host/normals_host.cpp, built with
 g++ plainly and under ASan + UBSan, and compared with the NumPy restatement of tests/normals.py on every
 builder cloud: counts, kept sets and the six covariance values bit for bit, normals and curvature by the
 eigenvector criterion; (2) what the builder clouds promise; (3) the module surface that needs no device.
@@ -10,43 +10,25 @@ and held below), so the bound is C_BOUND = 4 * 2.672 = 10.688."""
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import normals as N
 import voxel as V
 from conftest import pkg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
-HARNESS = os.path.join(ROOT, "tests", "host", "normals_host.cpp")
+ROOT = hostbuild.ROOT
 OUT = np.dtype([("n", "<i4"), ("zero", "<i4"), ("C", "<f8", (6,)), ("o", "<f8", (4,)), ("kept", "<u8", (12,))])
-SAN = ("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer")
 
 needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-
-
-def core(name, tag) -> str:
-    src = open(os.path.join(CSRC, name)).read()
-    return src[src.index(f"// {tag}_BEGIN"):src.index(f"// {tag}_END")]
 
 
 @pytest.fixture(scope="module")
 def exes(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("normals_host")
-    cpp = tmp / "normals_host.cpp"
-    cpp.write_text(open(HARNESS).read().replace("// VOXEL_CORE\n", core("voxel_core.hpp", "VOXEL_CORE"))
-                   .replace("// NORMALS_CORE\n", core("normals_core.hpp", "NORMALS_CORE")))
-    out = []
-    for name, flags in (("normals_host", ("-O2",)), ("normals_host_san", SAN)):
-        exe = tmp / name
-        r = subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", *flags, str(cpp), "-o", str(exe)],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        out.append(exe)
-    return tmp, out
+    return tmp, [hostbuild.build(tmp, "normals_host.cpp", "-ffp-contract=off", sanitize=san) for san in (False, True)]
 
 
 def run(exe, tmp, c, viewpoint=None):
@@ -60,8 +42,7 @@ def run(exe, tmp, c, viewpoint=None):
     dims = np.array([len(keys), c["est"]["R"], c["max_nn"], viewpoint is not None, log2cap], np.int64).tobytes()
     src, dst = tmp / "in.bin", tmp / "out.bin"
     src.write_bytes(head + dims + np.ascontiguousarray(keys, np.int32).tobytes() + np.ascontiguousarray(cent).tobytes())
-    r = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    hostbuild.run(exe, src, dst)
     return np.frombuffer(dst.read_bytes(), OUT)
 
 

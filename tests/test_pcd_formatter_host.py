@@ -1,34 +1,18 @@
-"""The device "%.6f" line writer (codecs.hpp: pcd_fast / pcd_fast_len / digit_groups / pcd_emit_line)
+"""The device "%.6f" line writer (pcd_line_core.hpp: pcd_fast / pcd_fast_len / digit_groups / pcd_emit_line)
 compiled for the host with g++ and checked against the C library's correctly rounded
-formatting — the kernel's own source, spliced into tests/host/pcd_formatter_host.cpp, exercised
+formatting — the kernel's own source, included by tests/host/pcd_formatter_host.cpp, exercised
 on this CPU (no GPU): float32 / float64 values, exact ties, digit carries, -0.0, values near the
 4294 cut-off, lanes of a tile written in reverse order."""
-import os
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CODECS = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc", "codecs.hpp")
-HARNESS = os.path.join(ROOT, "tests", "host", "pcd_formatter_host.cpp")
-
-
-def formatter_section() -> str:
-    src = open(CODECS).read()
-    return src[src.index("struct PcdFast {"):src.index("constexpr int32_t kPcdSlowTile")]
+import hostbuild
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_line_writer_matches_printf(tmp_path):
-    code = open(HARNESS).read().replace("// FORMATTER_SECTION", formatter_section())
-    cpp = tmp_path / "fmt.cpp"
-    cpp.write_text(code)
-    exe = tmp_path / "fmt"
-    r = subprocess.run(["g++", "-O2", "-std=c++17", str(cpp), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([str(exe), "200000"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout[-3000:]
+    r = hostbuild.run(hostbuild.build(tmp_path, "pcd_formatter_host.cpp"), 200000, timeout=120)
     assert "bad 0" in r.stdout
 
 

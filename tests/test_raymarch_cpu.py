@@ -1,21 +1,19 @@
 """The ray-march scanner's contract on the CPU (no GPU): tests/raymarch.py's numpy restatement
 against the reference's recorded runs (tests/golden/csim_raymarch.npz), the host-table rules the
 Python layer relies on, the fixtures' own conditions, and the kernel's per-pair core
-(csrc/raymarch.hpp) compiled for the host under AddressSanitizer + UndefinedBehaviorSanitizer."""
+(csrc/raymarch_core.hpp) compiled for the host under AddressSanitizer + UndefinedBehaviorSanitizer."""
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import raymarch as RM
 from conftest import golden, pkg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CORE = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc", "raymarch.hpp")
-HARNESS = os.path.join(ROOT, "tests", "host", "raymarch_host.cpp")
+ROOT = hostbuild.ROOT
 NEW_SYMBOLS = ("mc_set_ray_scene", "mc_ray_count", "mc_ray_hits", "mc_ray_emit", "mc_ray_emit_f64",
                "mc_timing_read_ray")
 
@@ -246,11 +244,6 @@ def test_arange_step_table_rule():
     assert np.count_nonzero(t != 0.05 + np.arange(len(t)) * 0.1) > 0
 
 
-def core_section() -> str:
-    src = open(CORE).read()
-    return src[src.index("// RAYMARCH_CORE_BEGIN"):src.index("// RAYMARCH_CORE_END")]
-
-
 def dump_case(path, dirs, steps, objects, poses):
     """The harness' input: the tables, the flattened scene and one (origin, R) per frame."""
     xyz, _, oid, _ = RM.flatten(objects)
@@ -266,23 +259,12 @@ def dump_case(path, dirs, steps, objects, poses):
 
 @pytest.fixture(scope="module")
 def host_core(tmp_path_factory):
-    """The CORE section in the harness, built once with g++ under ASan + UBSan; returns run(path) ->
+    """The core in the harness, built once with g++ under ASan + UBSan; returns run(path) ->
     (per-ray "step object scene_index" rows, the last line)."""
-    tmp = tmp_path_factory.mktemp("raymarch_host")
-    cpp = tmp / "raymarch_host.cpp"
-    cpp.write_text(open(HARNESS).read().replace("// RAYMARCH_CORE", core_section()))
-    exe = tmp / "raymarch_host"
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-fno-omit-frame-pointer", "-ffp-contract=off", str(cpp), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    exe = hostbuild.build(tmp_path_factory.mktemp("raymarch_host"), "raymarch_host.cpp", "-ffp-contract=off", sanitize=True)
 
     def run(path):
-        r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=300, env=env)
-        assert r.returncode == 0, (str(path), r.stdout[-2000:], r.stderr[-3000:])
-        assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
-        lines = r.stdout.strip().splitlines()
+        lines = hostbuild.run(exe, path).stdout.strip().splitlines()
         return np.array([ln.split() for ln in lines[:-1]], dtype=np.int64), lines[-1]
     return run
 

@@ -6,20 +6,16 @@ csrc/relfold.hpp compiled for the host.  No GPU.
 
 Every case prints `case: d_ref ..., folded / two-pass outside the bar` (pytest -s); DESIGN §5 records them.
 """
-import os
 import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import relative as V
 import rounding as Q
 from oracle import restatement as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
 
 
 def test_oracle_matches_scipy_across_yaw_wrap():
@@ -97,11 +93,7 @@ def test_point_at_reference_time_maps_to_itself(shifted):
 def test_fold_compiled_for_the_host(tmp_path):
     """rel_fold of csrc/relfold.hpp through g++ -ffp-contract=off equals the numpy fold bit for bit, on
     the records of a shifted table and a reference pose between two samples."""
-    exe = tmp_path / "relfold_host"
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", CSRC,
-                        os.path.join(ROOT, "tests", "host", "relfold_host.cpp"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = hostbuild.build(tmp_path, "relfold_host.cpp", "-ffp-contract=off")
     tr = dict(Q.pose_table("big"))
     tr["position_gps"] = tr["position_gps"] + V.SHIFT
     sg = Q.pose_segments(tr)
@@ -109,8 +101,7 @@ def test_fold_compiled_for_the_host(tmp_path):
     rec = np.ascontiguousarray(np.column_stack([sg["q0"], sg["v"], sg["p0"], sg["dp"]]))
     src, dst = tmp_path / "in.bin", tmp_path / "out.bin"
     src.write_bytes(struct.pack("<q", len(rec)) + np.concatenate([q_ref, pos_ref]).tobytes() + rec.tobytes())
-    r = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    hostbuild.run(exe, src, dst, timeout=120)
     got = np.frombuffer(dst.read_bytes(), np.float64).reshape(-1, 14)
     fd = V.fold_records(sg, q_ref, pos_ref)
     want = np.column_stack([fd["q0"], fd["v"], fd["p0"], fd["dp"]])

@@ -1,24 +1,21 @@
 """The scene scanner's visibility decision on the CPU (no GPU): tests/scanedges.py's fixtures
 against oracle.restatement.scan_environment and their own conditions, and scan_visible's two tiers
-(csrc/scan.hpp, the section between the CORE markers) compiled for the host under AddressSanitizer +
+(csrc/scan_core.hpp) compiled for the host under AddressSanitizer +
 UndefinedBehaviorSanitizer: equal to the reference's mask on every row of every edge scene, and no
 longer equal once any of its comparisons, margins or guards is altered."""
-import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import scanedges as S
 from oracle import restatement as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CORE = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc", "scan.hpp")
-HARNESS = os.path.join(ROOT, "tests", "host", "scan_host.cpp")
+FLAGS = ("-ffp-contract=off", "-Wno-unknown-pragmas")
 EDGE_CLASSES = ("range_max", "range_min", "az_edge", "el_edge", "corner_az_rmin", "corner_el_rmax")
 
-# (name, text of the core section, its replacement); every mutant must change a decision on some
+# (name, text of the core as the compiler reads it, its replacement); every mutant must change a decision on some
 # fixture row.  "behind shortcut dropped" cannot: without `lx < -m -> az_in = 0` the exact tier
 # decides those rows, and decides them alike; it is held to what it does change, rows behind the
 # sensor reaching atan2, and its decision-changing form (the `lx < -m` condition alone dropped, so
@@ -117,28 +114,16 @@ def test_cap_scene_counts():
     assert len(env) == 4400 and (2 * S.N_CAP - 2) // 1024 == 4
 
 
-def core_section() -> str:
-    src = open(CORE).read()
-    return src[src.index("// SCAN_CORE_BEGIN"):src.index("// SCAN_CORE_END")]
-
-
-def build_host(tmp, name, core):
-    cpp = tmp / f"{name}.cpp"
-    cpp.write_text(open(HARNESS).read().replace("// SCAN_CORE", core))
-    exe = tmp / name
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                        "-fno-omit-frame-pointer", "-ffp-contract=off", "-Wno-unknown-pragmas", str(cpp), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
+def build_mutant(tmp, name, text):
+    """The preprocessed harness with one alteration, built as the harness itself is."""
+    ii = tmp / f"{name}.ii"
+    ii.write_text(text)
+    return hostbuild.build(tmp, ii, *FLAGS, sanitize=True)
 
 
 def run_host(exe, path):
     """(visible, exact evaluations) per row of every case in ``path``, as its own process."""
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([str(exe), str(path)], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-3000:])
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-3000:]
+    r = hostbuild.run(exe, path)
     out = np.array(r.stdout.split(), dtype=np.int64).reshape(-1, 2)
     return out[:, 0].astype(bool), out[:, 1]
 
@@ -165,8 +150,8 @@ def test_host_core_equals_mask_and_mutants_do_not(tmp_path, scenes, case_file):
     with the mask on at least one row; the decision-neutral one sends rows to atan2 that the core
     decides without."""
     path, want = case_file
-    core = core_section()
-    got, exact = run_host(build_host(tmp_path, "scan_host", core), path)
+    core = hostbuild.preprocessed("scan_host.cpp", *FLAGS, sanitize=True)
+    got, exact = run_host(hostbuild.build(tmp_path, "scan_host.cpp", *FLAGS, sanitize=True), path)
     assert len(got) == len(want)
     bad = np.flatnonzero(got != want)
     assert len(bad) == 0, (len(bad), bad[:10])
@@ -178,7 +163,7 @@ def test_host_core_equals_mask_and_mutants_do_not(tmp_path, scenes, case_file):
         assert ci not in S.FAST or 0.0 < frac < 1.0, (ci, pi, frac)
     for k, (name, old, new) in enumerate(MUTANTS):
         assert core.count(old) == 1, name
-        mgot, mexact = run_host(build_host(tmp_path, f"mutant{k}", core.replace(old, new)), path)
+        mgot, mexact = run_host(build_mutant(tmp_path, f"mutant{k}", core.replace(old, new)), path)
         n = int((mgot != want).sum())
         per = [int((mgot != want)[offs[j]:offs[j + 1]].sum()) for j in range(len(scenes))]
         hit = sorted({scenes[j][0] for j in range(len(scenes)) if per[j]})

@@ -1,71 +1,15 @@
-"""The codec kernels' unit order (layout.hpp stream_unit, DESIGN §4 "Codec unit order"): the
-function's own source compiled for the host with g++, checked to be a bijection on [0, n) for every
+"""The codec kernels' unit order (unit_order.hpp stream_unit, DESIGN §4 "Codec unit order"): the
+header compiled for the host with g++ (tests/host/stream_order_host.cpp), checked to be a bijection on [0, n) for every
 order and n, and to start where the order it answers ended (reversed: the last unit first; XCD
 ranges reversed: each of xcd_unit<true>'s 8 ranges from its tail)."""
-import os
 import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LAYOUT = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc", "layout.hpp")
-
-HARNESS = r"""
-#include <cstdint>
-#include <cstdio>
-#include <vector>
-constexpr int kXcds = 8;
-template <bool ON>
-inline int64_t xcd_unit(int64_t b, int64_t n) {
-  if (!ON) return b;
-  const int64_t x = b % kXcds, i = b / kXcds, per = n / kXcds, rem = n % kXcds;
-  return x * per + (x < rem ? x : rem) + i;
-}
-// STREAM_UNIT
-int main() {
-  long bad = 0;
-  for (int64_t n = 1; n <= 3000; ++n) {
-    for (int order = 0; order < 4; ++order) {
-      std::vector<char> seen(n, 0);
-      for (int64_t b = 0; b < n; ++b) {
-        const int64_t u = stream_unit(order, b, n);
-        if (u < 0 || u >= n || seen[u]) { ++bad; break; }
-        seen[u] = 1;
-      }
-    }
-    for (int64_t b = 0; b < n; ++b) {
-      if (stream_unit(0, b, n) != b) ++bad;
-      if (stream_unit(1, b, n) != n - 1 - b) ++bad;
-      if (stream_unit(2, b, n) != xcd_unit<true>(b, n)) ++bad;
-    }
-    // order 3 runs each XCD range of order 2 backwards: the units order 2 reaches last come first
-    for (int64_t b = 0; b < n && b < kXcds; ++b) {
-      const int64_t x = b % kXcds, per = n / kXcds, rem = n % kXcds;
-      const int64_t len = per + (x < rem ? 1 : 0);
-      if (len == 0) continue;
-      if (stream_unit(3, b, n) != xcd_unit<true>(b + kXcds * (len - 1), n)) ++bad;
-    }
-  }
-  std::printf("bad %ld\n", bad);
-  return bad != 0;
-}
-"""
-
-
-def stream_unit_source() -> str:
-    src = open(LAYOUT).read()
-    a = src.index("__device__ __forceinline__ int64_t stream_unit(")
-    b = src.index("\n}\n", a) + 3
-    return src[a:b].replace("__device__ __forceinline__ ", "inline ")
+import hostbuild
 
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
 def test_stream_unit_is_a_bijection_starting_at_the_hot_end(tmp_path):
-    cpp = tmp_path / "order.cpp"
-    cpp.write_text(HARNESS.replace("// STREAM_UNIT", stream_unit_source()))
-    exe = tmp_path / "order"
-    r = subprocess.run(["g++", "-O2", "-std=c++17", str(cpp), "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "bad 0" in r.stdout, r.stdout[-2000:]
+    r = hostbuild.run(hostbuild.build(tmp_path, "stream_order_host.cpp"), timeout=120)
+    assert "bad 0" in r.stdout, r.stdout[-2000:]

@@ -3,36 +3,27 @@ NumPy restatement of tests/timerule.py.  No GPU.
 
 The rule's one arithmetic is int32 wrap-around: the predicate compares a stored time with what the
 deskew kernel generates for its index, so "evenly timed" means "generated back to the bit"."""
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbuild
 import timerule as TR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def host_results(tmp_path_factory):
     """Every host case through the compiled core, once: name -> (even, t0, dt, generated times)."""
     d = tmp_path_factory.mktemp("time_rule")
-    exe = d / "time_rule_host"
-    r = subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", CSRC,
-                        os.path.join(ROOT, "tests", "host", "time_rule_host.cpp"), "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
+    exe = hostbuild.build(d, "time_rule_host.cpp", "-Wall", "-Werror")
     cases = TR.host_cases()
     src, dst = d / "in.bin", d / "out.bin"
     blob = struct.pack("<q", len(cases))
     for t, _ in cases.values():
         blob += struct.pack("<q", len(t)) + np.ascontiguousarray(t, np.int32).tobytes()
     src.write_bytes(blob)
-    r = subprocess.run([str(exe), str(src), str(dst)], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+    hostbuild.run(exe, src, dst, timeout=60)
     out = np.frombuffer(dst.read_bytes(), np.int32)
     res, k = {}, 0
     for name, (t, _) in cases.items():

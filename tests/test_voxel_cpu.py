@@ -1,58 +1,40 @@
-"""The voxel-grid filter without a GPU: (1) the scalar core of csrc/voxel_core.hpp (the section between
-its VOXEL_CORE markers) spliced into tests/host/voxel_host.cpp, built with g++ plainly and under
+"""The voxel-grid filter without a GPU: (1) the scalar core of csrc/voxel_core.hpp, included by
+tests/host/voxel_host.cpp, built with g++ plainly and under
 ASan + UBSan, and compared bit for bit with the NumPy restatement of tests/voxel.py on the boundary and
 range values; (2) the restatement's own accuracy bounds against exact rational means; (3) the module
 surface that needs no device."""
 import os
 import re
 import shutil
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+import hostbuild
 import voxel as V
 from conftest import pkg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "livox-motion-compensation-sim_amd", "csrc")
-HARNESS = os.path.join(ROOT, "tests", "host", "voxel_host.cpp")
+ROOT = hostbuild.ROOT
 
 QUANT_OUT = np.dtype([("k", "<i4", (3,)), ("bad", "<i4"), ("Q", "<i8", (3,)), ("QI", "<i8"), ("key", "<u8"),
                       ("uk", "<i4", (3,)), ("zero", "<i4")])
 FIN_IN = np.dtype([("k", "<i4", (3,)), ("zero", "<i4"), ("S", "<i8", (3,)), ("SI", "<i8"), ("n", "<i8")])
 FIN_OUT = np.dtype([("c", "<f8", (4,)), ("f", "<f4", (4,))])
-SAN = ("-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer")
 
 needs_gxx = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
-
-
-def core() -> str:
-    src = open(os.path.join(CSRC, "voxel_core.hpp")).read()
-    return src[src.index("// VOXEL_CORE_BEGIN"):src.index("// VOXEL_CORE_END")]
 
 
 @pytest.fixture(scope="module")
 def exes(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("voxel_host")
-    cpp = tmp / "voxel_host.cpp"
-    cpp.write_text(open(HARNESS).read().replace("// VOXEL_CORE\n", core()))
-    out = []
-    for name, flags in (("voxel_host", ("-O2",)), ("voxel_host_san", SAN)):
-        exe = tmp / name
-        r = subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", *flags, str(cpp), "-o", str(exe)],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stderr[-3000:]
-        out.append(exe)
-    return tmp, out
+    return tmp, [hostbuild.build(tmp, "voxel_host.cpp", "-ffp-contract=off", sanitize=san) for san in (False, True)]
 
 
 def run(exe, tmp, mode, h, origin, body):
     src, dst = tmp / "in.bin", tmp / "out.bin"
     src.write_bytes(np.array([h, *origin], np.float64).tobytes() + body)
-    r = subprocess.run([str(exe), mode, str(src), str(dst)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    hostbuild.run(exe, mode, src, dst, timeout=120)
     return dst.read_bytes()
 
 
