@@ -516,6 +516,53 @@ int mc_voxel_normals(mc_ctx* ctx, double radius, int32_t max_nn, const double* v
  * launched only when there are some); *launches = timed regions */
 int mc_timing_read_normals(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 
+/* ---- density clustering of the voxel cloud (csrc/cluster_core.hpp, cluster.hpp) -------------------
+ * The first step of the reference's point cloud processing list, noise filtering and outlier removal
+ * (docs/Comprehensive Guide.md:488-491), and the segmentation behind the object files its viewer is run
+ * on (read_pointcloud.py:233-257, ..._nonground_train_wagon_01.pcd to _05.pcd): DBSCAN over the voxel
+ * points of the live build.  Its noise label is the radius-outlier filter, its clusters are the
+ * segments; with min_points = 1 every voxel is core and the result is Euclidean cluster extraction
+ * (connected components).  With h the build's voxel size, R = ceil(eps / h) and eps2 = eps * eps; every
+ * line ONE IEEE float64 operation, no contraction:
+ *   neighbours  of voxel i: exactly the set of the normals above without a cap, radius = eps: the occupied
+ *               cells within R of k_i on every axis (cells outside the key range do not exist) with
+ *               u = c_j - c_i     d2 = (u.x*u.x + u.y*u.y) + u.z*u.z     d2 <= eps2;  i itself included.
+ *               The relation is symmetric.
+ *   density     the number of neighbours; weighted: the sum of the neighbours' source-point counts (the
+ *               d_counts of mc_voxel_emit_f64; at most N < 2^31, an int32)
+ *   core        density >= min_points
+ *   cluster     a connected component of the core voxels under the neighbour relation
+ *   border      a voxel that is not core and has a core neighbour joins the cluster of the core neighbour
+ *               with the smallest (d2, ix), ix the place in the window walk, which ascends with the
+ *               packed key (a voxel's place in the output never breaks a tie)
+ *   noise       every other voxel that is not core: label -1
+ *   numbering   clusters are 0 .. K - 1 in ascending order of their lowest core voxel id (a voxel's id is
+ *               its place in the cloud's output), so cluster 0 is the one whose core appears first.  The
+ *               lowest core id is the union-find's root; a border voxel with a lower id than every core
+ *               voxel of its cluster does not number it
+ * The partition is a function of the voxel set, eps, min_points and weighted alone, the numbering of
+ * the cloud's order alone; neither depends on the order the device's atomics arrive in (a lock-free
+ * union-find whose roots are the lowest ids of their trees; no lane waits for another), so every run
+ * gives the same bits.
+ * d_labels (M,) int32 and d_density (M,) int32 (may be NULL), rows in the cloud's order; *n_clusters = K
+ * (may be NULL).  Any number of calls per build, with any parameters.
+ * MC_ERR_INVALID before any launch: eps not finite or <= 0, eps / h > 4 (voxelise coarser or shrink the
+ * radius), min_points < 1, weighted not 0 or 1, ctx NULL, d_labels NULL with M > 0.  No successful build:
+ * MC_ERR_STATE.  M = 0: MC_OK, K = 0, nothing written.  Device memory, with the voxel filter's: 8 B per
+ * voxel beside the normals' centroids (32 B per voxel, shared with them). */
+int mc_voxel_clusters(mc_ctx* ctx, double eps, int32_t min_points, int32_t weighted, int32_t* d_labels,
+                      int32_t* d_density, int64_t* n_clusters);
+/* per cluster of the last mc_voxel_clusters of the live build, K rows, any may be NULL: d_voxels (K,) int32
+ * voxels, d_points (K,) int64 source points, d_cell_min / d_cell_max (K, 3) int32 the bounding box of the
+ * cells kx, ky, kz (inclusive).  Integer atomic sums, minima and maxima: the same on every run.  Without such
+ * a clustering (none yet, or a later build or release): MC_ERR_STATE.  K = 0: MC_OK, nothing written. */
+int mc_voxel_cluster_stats(mc_ctx* ctx, int32_t* d_voxels, int64_t* d_points, int32_t* d_cell_min,
+                           int32_t* d_cell_max);
+/* event time (ms) of the timed phases since the last read: ms_phase[5] = density, union, label, number,
+ * stats; *launches = timed regions (the centroids, when a clustering is the first to need them, are timed
+ * with the normals') */
+int mc_timing_read_clusters(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

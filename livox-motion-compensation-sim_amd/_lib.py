@@ -137,6 +137,10 @@ _SIGS = {
     # the surface normals of the voxel cloud
     "mc_voxel_normals": (c_int, [c_void_p, c_double, c_int32, _pd, c_void_p, c_void_p, c_void_p]),
     "mc_timing_read_normals": (c_int, [c_void_p, _pd, _pi64]),
+    # the density clustering of the voxel cloud
+    "mc_voxel_clusters": (c_int, [c_void_p, c_double, c_int32, c_int32, c_void_p, c_void_p, _pi64]),
+    "mc_voxel_cluster_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mc_timing_read_clusters": (c_int, [c_void_p, _pd, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

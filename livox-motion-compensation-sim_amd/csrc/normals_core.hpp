@@ -64,25 +64,26 @@ MC_CORE_HD bool normals_find(const NormalsGrid& g, uint64_t key, uint32_t* v) {
   }
 }
 
-// fn(ix, u, d2) for every neighbour of the voxel at cell ki with centroid ci, in walk order; ix is the
+// fn(ix, v, u, d2) for every neighbour of the voxel at cell ki with centroid ci, in walk order; ix is the
 // cell's place in the window, ((dkx + R) (2R + 1) + dky + R) (2R + 1) + dkz + R, which ascends with the
-// packed key
-template <typename Fn>
-MC_CORE_HD void normals_neighbours(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
-                                    Fn&& fn) {
+// packed key; v is the neighbour's voxel id (what the clustering of cluster_core.hpp needs beside it).  The walk
+// kFromCell: the walk starts at the cell of place `first`; planes, rows and cells before it are not probed.
+template <bool kFromCell = false, typename Fn>
+MC_CORE_HD void normals_neighbours_v(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
+                                      Fn&& fn, int32_t first = 0) {
   MC_CORE_NO_CONTRACT
   const int32_t W = 2 * q.R + 1;
   int32_t ix = 0;
   for (int32_t dx = -q.R; dx <= q.R; ++dx) {
     int32_t k[3];
     k[0] = ki[0] + dx;
-    if (k[0] < kVoxelKeyMin || k[0] >= kVoxelKeyEnd) { ix += W * W; continue; }
+    if ((kFromCell && ix + W * W <= first) || k[0] < kVoxelKeyMin || k[0] >= kVoxelKeyEnd) { ix += W * W; continue; }
     for (int32_t dy = -q.R; dy <= q.R; ++dy) {
       k[1] = ki[1] + dy;
-      if (k[1] < kVoxelKeyMin || k[1] >= kVoxelKeyEnd) { ix += W; continue; }
+      if ((kFromCell && ix + W <= first) || k[1] < kVoxelKeyMin || k[1] >= kVoxelKeyEnd) { ix += W; continue; }
       for (int32_t dz = -q.R; dz <= q.R; ++dz, ++ix) {
         k[2] = ki[2] + dz;
-        if (k[2] < kVoxelKeyMin || k[2] >= kVoxelKeyEnd) continue;
+        if ((kFromCell && ix < first) || k[2] < kVoxelKeyMin || k[2] >= kVoxelKeyEnd) continue;
         uint32_t v;
         if (!normals_find(g, voxel_pack(k), &v)) continue;
         const double* cj = g.cent + (int64_t)kNormalsCent * v;
@@ -95,10 +96,17 @@ MC_CORE_HD void normals_neighbours(const NormalsGrid& g, const int32_t ki[3], co
         const double zz = u[2] * u[2];
         const double xy = xx + yy;
         const double d2 = xy + zz;
-        if (d2 <= q.r2) fn(ix, u, d2);
+        if (d2 <= q.r2) fn(ix, v, u, d2);
       }
     }
   }
+}
+
+// the same without the neighbour's id: fn(ix, u, d2)
+template <typename Fn>
+MC_CORE_HD void normals_neighbours(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
+                                    Fn&& fn) {
+  normals_neighbours_v(g, ki, ci, q, [&](int32_t ix, uint32_t, const double u[3], double d2) { fn(ix, u, d2); });
 }
 
 MC_CORE_HD void normals_clear(NormalsMoments* m) {

@@ -3,10 +3,12 @@
 // The filter's state (the key table, the per-point slots, the per-voxel sums and what the last build
 // left for its emits) is the CtxExt in the context's voxel slot (internal.hpp): the other translation
 // units see only that hook.  mc_voxel_release frees it early; mc_destroy frees what is left.  The surface
-// normals of the built cloud (mc_voxel_normals; kernels in normals.hpp) read that state and keep theirs in it.
+// normals of the built cloud (mc_voxel_normals; kernels in normals.hpp) and its density clustering
+// (mc_voxel_clusters; kernels in cluster.hpp) read that state and keep theirs in it.
 #include "../../include/mcdeskew.h"
 #include "voxel.hpp"
 #include "normals.hpp"
+#include "cluster.hpp"
 #include "internal.hpp"
 #include "hostutil.hpp"
 
@@ -19,6 +21,7 @@ namespace {
 
 enum { kInsert = 0, kRank = 1, kAccumulate = 2, kFinalise = 3, kPhases = 4 };
 enum { kNrmCentroids = 0, kNrmWindow = 1, kNrmCap = 2, kNrmPhases = 3 };
+enum { kClDensity = 0, kClUnion = 1, kClLabel = 2, kClNumber = 3, kClStats = 4 };
 
 struct VoxState : mcimpl::CtxExt {
   // table (a power of two of slots), per-point arrays (points / chunks), per-voxel records
@@ -44,11 +47,18 @@ struct VoxState : mcimpl::CtxExt {
   DevBuf<uint32_t> capped;
   DevBuf<uint32_t> n_capped;
   EventPairs nrm_ev[kNrmPhases];
+  // the last clustering of the last build: the union-find word and the label of every voxel (the cluster's
+  // number, kClusterNone for noise), the roots per workgroup, and K
+  DevBuf<uint32_t> cl_parent, cl_label, cl_chunk, cl_meta;
+  bool cl_current = false;
+  int64_t cl_K = 0;
+  EventPairs cl_ev[kClusterPhases];
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
     for (auto& v : ev) ev_destroy(v);
     for (auto& v : nrm_ev) ev_destroy(v);
+    for (auto& v : cl_ev) ev_destroy(v);
   }
 };
 
@@ -70,6 +80,7 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   VoxState* s = state_of(c, true);
   s->built = false;
   s->cent_current = false;
+  s->cl_current = false;
   s->M = 0;
   s->h = src.h;
   std::copy_n(src.o, 3, s->o);
@@ -152,6 +163,27 @@ int emit(mc_ctx* c, VoxState* s, VoxOut a, bool batch, int64_t P) {
     else hipLaunchKernelGGL(k_vox_emit_rows, grid, blk, 0, c->stream, a);
   }
   HIPCHK(hipGetLastError());
+  return MC_OK;
+}
+
+// the centroids by voxel id of the live build (M > 0), written once per build: what the window walks of the
+// normals and of the clustering read
+int centroids(mc_ctx* c, VoxState* s) {
+  const int64_t M = s->M;
+  if (int r = ctx_reserve(c, s->cent, kNormalsCent * (size_t)M)) return r;
+  if (s->cent_current) return MC_OK;
+  VoxOut o = {};
+  o.keys = s->keys; o.vslot = s->vslot; o.sums = s->sums; o.cnt = s->cnt;
+  o.M = M;
+  o.h = s->h;
+  std::copy_n(s->o, 3, o.o);
+  {
+    TimedRegion tr(c, &s->nrm_ev[kNrmCentroids], c->stream);
+    hipLaunchKernelGGL(k_nrm_centroids, dim3((uint32_t)((M + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, o,
+                       s->cent.get());
+  }
+  HIPCHK(hipGetLastError());
+  s->cent_current = true;
   return MC_OK;
 }
 
@@ -275,23 +307,10 @@ int mc_voxel_normals(mc_ctx* c, double radius, int32_t max_nn, const double* vie
   if (M == 0) return MC_OK;
   CHECK_ARG(d_normals, "d_normals is NULL");
   DeviceGuard g(c->device);
-  if (int r = ctx_reserve(c, s->cent, kNormalsCent * (size_t)M)) return r;
+  if (int r = centroids(c, s)) return r;
   if (int r = ctx_reserve(c, s->capped, (size_t)M)) return r;
   if (!s->n_capped) if (int r = s->n_capped.alloc(1)) return r;
   const dim3 blk(kVoxBlock), grid((uint32_t)((M + kVoxBlock - 1) / kVoxBlock));
-  if (!s->cent_current) {
-    VoxOut o = {};
-    o.keys = s->keys; o.vslot = s->vslot; o.sums = s->sums; o.cnt = s->cnt;
-    o.M = M;
-    o.h = s->h;
-    std::copy_n(s->o, 3, o.o);
-    {
-      TimedRegion tr(c, &s->nrm_ev[kNrmCentroids], c->stream);
-      hipLaunchKernelGGL(k_nrm_centroids, grid, blk, 0, c->stream, o, s->cent.get());
-    }
-    HIPCHK(hipGetLastError());
-    s->cent_current = true;
-  }
   NrmArgs a = {};
   a.g.keys = s->keys; a.g.vid = s->vid; a.g.cent = s->cent;
   a.g.shift = s->shift; a.g.mask = s->mask;
@@ -342,6 +361,117 @@ int mc_timing_read_normals(mc_ctx* c, double* ms_phase, int64_t* launches) {
   return MC_OK;
 }
 
+int mc_voxel_clusters(mc_ctx* c, double eps, int32_t min_points, int32_t weighted, int32_t* d_labels, int32_t* d_density,
+                      int64_t* n_clusters) {
+  if (n_clusters) *n_clusters = 0;
+  CHECK_ARG(c, "ctx is NULL");
+  CHECK_ARG(std::isfinite(eps) && eps > 0.0, "eps must be finite and > 0 (got %g)", eps);
+  CHECK_ARG(min_points >= 1, "min_points must be >= 1 (got %d)", min_points);
+  CHECK_ARG(weighted == 0 || weighted == 1, "weighted must be 0 or 1 (got %d)", weighted);
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_clusters needs a successful mc_voxel_build_* first");
+  CHECK_ARG(eps / s->h <= (double)kNormalsMaxR,
+            "eps %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius",
+            eps, eps / s->h, s->h, kNormalsMaxR);
+  const int64_t M = s->M;
+  CHECK_ARG(M == 0 || d_labels, "d_labels is NULL");
+  s->cl_current = false;   // a refused call leaves the last clustering; one that starts replaces it
+  s->cl_K = 0;
+  if (M == 0) { s->cl_current = true; return MC_OK; }
+  DeviceGuard g(c->device);
+  const uint32_t blocks = (uint32_t)((M + kVoxBlock - 1) / kVoxBlock);
+  if (int r = centroids(c, s)) return r;
+  if (int r = ctx_reserve(c, s->cl_parent, (size_t)M)) return r;
+  if (int r = ctx_reserve(c, s->cl_label, (size_t)M)) return r;
+  if (int r = ctx_reserve(c, s->cl_chunk, (size_t)blocks)) return r;
+  if (!s->cl_meta) if (int r = s->cl_meta.alloc(2)) return r;
+  ClusterArgs a = {};
+  a.g.keys = s->keys; a.g.vid = s->vid; a.g.cent = s->cent;
+  a.g.shift = s->shift; a.g.mask = s->mask;
+  a.vslot = s->vslot;
+  a.cnt = s->cnt;
+  a.M = M;
+  a.q = cluster_query(std::max(1, (int)std::ceil(eps / s->h)), eps * eps);
+  a.min_points = min_points;
+  a.weighted = weighted;
+  a.parent = s->cl_parent; a.label = s->cl_label; a.chunk = s->cl_chunk;
+  a.labels_out = d_labels; a.density_out = d_density;
+  const dim3 blk(kVoxBlock), grid(blocks);
+  {
+    TimedRegion tr(c, &s->cl_ev[kClDensity], c->stream);
+    hipLaunchKernelGGL(k_cl_density, grid, blk, 0, c->stream, a);
+  }
+  {
+    TimedRegion tr(c, &s->cl_ev[kClUnion], c->stream);
+    hipLaunchKernelGGL(k_cl_union, grid, blk, 0, c->stream, a);
+  }
+  {
+    TimedRegion tr(c, &s->cl_ev[kClLabel], c->stream);
+    hipLaunchKernelGGL(k_cl_label, grid, blk, 0, c->stream, a);
+  }
+  {
+    TimedRegion tr(c, &s->cl_ev[kClNumber], c->stream);
+    hipLaunchKernelGGL(k_cl_flag, grid, blk, 0, c->stream, a);
+    hipLaunchKernelGGL(k_vox_scan, dim3(1), blk, 0, c->stream, s->cl_chunk.get(), (int64_t)blocks, s->cl_meta.get());
+    hipLaunchKernelGGL(k_cl_rank, grid, blk, 0, c->stream, a);
+    hipLaunchKernelGGL(k_cl_number, grid, blk, 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  // the one synchronisation: K
+  uint32_t meta[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(meta, s->cl_meta, sizeof meta, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((int64_t)meta[1] > M) return fail(MC_ERR_STATE, "voxel clusters: %u clusters of %lld voxels", meta[1], (long long)M);
+  s->cl_K = (int64_t)meta[1];
+  s->cl_current = true;
+  if (n_clusters) *n_clusters = s->cl_K;
+  return MC_OK;
+}
+
+int mc_voxel_cluster_stats(mc_ctx* c, int32_t* d_voxels, int64_t* d_points, int32_t* d_cell_min, int32_t* d_cell_max) {
+  CHECK_ARG(c, "ctx is NULL");
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built || !s->cl_current)
+    return fail(MC_ERR_STATE, "mc_voxel_cluster_stats needs a successful mc_voxel_clusters of the live build first");
+  const int64_t K = s->cl_K;
+  if (K == 0 || (!d_voxels && !d_points && !d_cell_min && !d_cell_max)) return MC_OK;
+  DeviceGuard g(c->device);
+  ClusterStatsArgs a = {};
+  a.keys = s->keys; a.vslot = s->vslot; a.cnt = s->cnt; a.label = s->cl_label;
+  a.M = s->M;
+  a.voxels = d_voxels;
+  a.points = reinterpret_cast<long long*>(d_points);
+  a.cell_min = d_cell_min; a.cell_max = d_cell_max;
+  {
+    TimedRegion tr(c, &s->cl_ev[kClStats], c->stream);
+    // every cluster holds a voxel, so no start value survives: 0x7F7F7F7F is above and 0x80808080 below any key
+    if (d_voxels) HIPCHK(hipMemsetAsync(d_voxels, 0, (size_t)K * sizeof(int32_t), c->stream));
+    if (d_points) HIPCHK(hipMemsetAsync(d_points, 0, (size_t)K * sizeof(int64_t), c->stream));
+    if (d_cell_min) HIPCHK(hipMemsetAsync(d_cell_min, 0x7F, (size_t)K * 3 * sizeof(int32_t), c->stream));
+    if (d_cell_max) HIPCHK(hipMemsetAsync(d_cell_max, 0x80, (size_t)K * 3 * sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(k_cl_stats, dim3((uint32_t)((s->M + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return MC_OK;
+}
+
+int mc_timing_read_clusters(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  int64_t total = 0;
+  for (int k = 0; k < kClusterPhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
+  if (VoxState* s = state_of(c, false)) {
+    for (int k = 0; k < kClusterPhases; ++k) {
+      int64_t n = 0;
+      if (int r = sum_events(c, s->cl_ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
+      total += n;
+    }
+  }
+  if (launches) *launches = total;
+  return MC_OK;
+}
+
 int mc_voxel_release(mc_ctx* c) {
   if (!c) return MC_OK;
   VoxState* s = state_of(c, false);
@@ -350,6 +480,7 @@ int mc_voxel_release(mc_ctx* c) {
   (void)sync_all(c);
   for (auto& v : s->ev) ev_recycle(c, v);
   for (auto& v : s->nrm_ev) ev_recycle(c, v);
+  for (auto& v : s->cl_ev) ev_recycle(c, v);
   c->ext[mcimpl::kSlotVoxel].reset();
   return MC_OK;
 }

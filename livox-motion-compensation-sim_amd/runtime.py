@@ -375,6 +375,14 @@ class Context:
         check(self.lib.mc_timing_read_normals(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_normals")
         return {"centroids_ms": ms[0], "window_ms": ms[1], "cap_ms": ms[2], "regions": n.value}
 
+    def read_timing_clusters(self) -> dict:
+        """Event time (ms) of the phases of VoxelCloud.clusters since the last read (mc_timing_read_clusters)."""
+        ms = np.zeros(5, np.float64)
+        n = c_int64()
+        check(self.lib.mc_timing_read_clusters(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_clusters")
+        return {"density_ms": ms[0], "union_ms": ms[1], "label_ms": ms[2], "number_ms": ms[3], "stats_ms": ms[4],
+                "regions": n.value}
+
     def device_buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)
 

@@ -5,6 +5,7 @@ of a drive are accumulated into one cloud and most points re-observe the same su
   voxel_downsample(batch_or_rows, voxel, origin=(0, 0, 0))  -> VoxelCloud
   VoxelCloud.n_voxels, .batch(), .rows(), .point_counts(), .keys(), .close()
   VoxelCloud.normals(radius, max_nn=30, viewpoint=None, covariance=False)  -> VoxelNormals
+  VoxelCloud.clusters(eps, min_points=10, weighted=False)  -> VoxelClusters
 
 One output point per occupied voxel: the mean of the voxel's points and of their intensities.  The
 per-voxel sums are integers (the coordinate inside its voxel in 2^-32 voxel units, the intensity in
@@ -33,6 +34,17 @@ in ascending key order, the covariance C = E[u u^T] - E[u] E[u]^T; the normal is
 for its smallest eigenvalue, the curvature its Rayleigh quotient over the trace.  Refused with ValueError:
 a radius that is not finite and > 0 or exceeds 4 h, max_nn not 0 and not in 3..64, a viewpoint that is not
 three finite numbers.
+
+Density clustering (csrc/cluster_core.hpp, csrc/cluster.hpp; ``mc_voxel_clusters``): DBSCAN over the live
+build, the noise filtering and outlier removal of the reference's processing list (docs/Comprehensive
+Guide.md:488-491) and the segmentation behind the object files its viewer opens (read_pointcloud.py:233-257).
+The neighbours of a voxel are the normals' set without a cap at radius = eps; a voxel is core when it has
+min_points of them (weighted: when their source points add up to min_points); a cluster is a connected
+component of core voxels; a voxel that is not core joins the cluster of its core neighbour of smallest
+(d2, packed key), or is noise (label -1).  Clusters are numbered 0 .. K - 1 by their lowest core voxel id, so the
+partition is a function of the voxel set and the numbering of the cloud's order: the same bits on every run.
+min_points = 1 is Euclidean cluster extraction (connected components).  Refused with ValueError: an eps that
+is not finite and > 0 or exceeds 4 h, min_points not an integer >= 1, weighted not a bool.
 """
 from __future__ import annotations
 
@@ -97,6 +109,35 @@ def _normals_args(radius, max_nn, viewpoint, h):
         if vp.shape != (3,) or not np.isfinite(vp).all():
             raise ValueError(f"viewpoint must be three finite numbers, got {viewpoint!r}")
     return r, int(max_nn), vp
+
+
+class VoxelClusters(NamedTuple):
+    """What :meth:`VoxelCloud.clusters` returns: per voxel in the cloud's order, then per cluster."""
+    labels: np.ndarray      # (M,) int32 the voxel's cluster 0 .. K - 1, -1 for noise
+    density: np.ndarray     # (M,) int32 neighbours within eps, the voxel included (weighted: their source points)
+    n_clusters: int         # K
+    voxels: np.ndarray      # (K,) int32 voxels of each cluster
+    points: np.ndarray      # (K,) int64 source points of each cluster
+    cell_min: np.ndarray    # (K, 3) int32 the lowest kx, ky, kz of each cluster
+    cell_max: np.ndarray    # (K, 3) int32 the highest
+
+
+def _clusters_args(eps, min_points, weighted, h):
+    """(eps, min_points, weighted as 0 / 1), checked before a device is touched."""
+    try:
+        e = float(eps)
+    except (TypeError, ValueError):
+        raise ValueError(f"eps must be a number > 0, got {eps!r}") from None
+    if not (math.isfinite(e) and e > 0.0):
+        raise ValueError(f"eps must be finite and > 0, got {eps!r}")
+    if h is not None and e / h > MAX_RADIUS_VOXELS:
+        raise ValueError(f"eps {e!r} is {e / h:.3g} voxels of {h!r} and the search window takes at most "
+                         f"{MAX_RADIUS_VOXELS}: voxelise coarser or shrink the radius")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= min_points <= MAX_POINTS:
+        raise ValueError(f"min_points must be an integer >= 1, got {min_points!r}")
+    if not isinstance(weighted, (bool, np.bool_)):
+        raise ValueError(f"weighted must be True or False, got {weighted!r}")
+    return e, int(min_points), int(bool(weighted))
 
 
 class VoxelCloud:
@@ -172,6 +213,42 @@ class VoxelCloud:
                 if b is not None:
                     b.close()
         return VoxelNormals(np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]), counts, cov)
+
+    def clusters(self, eps, min_points: int = 10, weighted: bool = False) -> "VoxelClusters":
+        """DBSCAN over the voxel points (module docstring; include/mcdeskew.h ``mc_voxel_clusters``): labels
+        and densities in the cloud's order, as :meth:`rows` / :meth:`keys`, and per cluster its voxels, source
+        points and cell bounding box.  Noise is label -1: ``labels >= 0`` is the radius-outlier filter, and
+        ``cloud.rows()[labels == k]`` is segment k.  ``weighted``: the density of a voxel is the number of
+        source points of its neighbours, not the number of neighbours.  Any number of calls, with any
+        parameters, on one live cloud."""
+        e, mp, w = _clusters_args(eps, min_points, weighted, self._h)
+        self._live()
+        M = self.n_voxels
+        if M == 0:
+            return VoxelClusters(np.zeros(0, np.int32), np.zeros(0, np.int32), 0, np.zeros(0, np.int32), np.zeros(0, np.int64),
+                                 np.zeros((0, 3), np.int32), np.zeros((0, 3), np.int32))
+        ctx = self.ctx
+        bufs = [ctx.device_buffer(M * 4), ctx.device_buffer(M * 4)]
+        try:
+            k = c_int64(0)
+            check(ctx.lib.mc_voxel_clusters(ctx.handle, e, mp, w, bufs[0].ptr, bufs[1].ptr, ctypes.byref(k)), "clusters")
+            K = k.value
+            labels = bufs[0].to_host(np.int32, count=M)
+            density = bufs[1].to_host(np.int32, count=M)
+            if K == 0:
+                return VoxelClusters(labels, density, 0, np.zeros(0, np.int32), np.zeros(0, np.int64),
+                                     np.zeros((0, 3), np.int32), np.zeros((0, 3), np.int32))
+            # one buffer, the int64 array first: voxels (K,), points (K,), cell_min (K, 3), cell_max (K, 3)
+            bufs.append(ctx.device_buffer(K * 36))
+            base = bufs[2].ptr.value
+            check(ctx.lib.mc_voxel_cluster_stats(ctx.handle, base + 8 * K, base, base + 12 * K, base + 24 * K), "clusters")
+            raw = bufs[2].to_host(np.int32, count=9 * K)
+        finally:
+            for b in bufs:
+                b.close()
+        return VoxelClusters(labels, density, K, np.ascontiguousarray(raw[2 * K:3 * K]),
+                             np.ascontiguousarray(raw[:2 * K]).view(np.int64), np.ascontiguousarray(raw[3 * K:6 * K]).reshape(K, 3),
+                             np.ascontiguousarray(raw[6 * K:]).reshape(K, 3))
 
     def close(self):
         """Give the filter's device scratch back (a later call allocates it again)."""
