@@ -563,6 +563,63 @@ int mc_voxel_cluster_stats(mc_ctx* ctx, int32_t* d_voxels, int64_t* d_points, in
  * with the normals') */
 int mc_timing_read_clusters(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 
+/* ---- plane segmentation of the voxel cloud and selection into a batch (csrc/plane_core.hpp, plane.hpp) ----
+ * The ground filter of the reference's processing chain (read_pointcloud.py:244-257: downsampled -> aligned ->
+ * ground_filtered (..._nonground) -> side_filtered -> segmented) and the step that writes a segment out: RANSAC
+ * plane segmentation of the live build, the counterpart of open3d's segment_plane, and a stable compaction of
+ * the cloud by a mask into a one-frame batch.  Defined op for op, integer where it can be: the same bits on every
+ * run.  c_v: the build's centroids by voxel id (float64).  t = distance, K = num_iterations.  ids: the candidate
+ * voxel ids, ascending (d_among NULL: all M; else the voxels whose byte is non-zero), n their number.  Every
+ * float64 line ONE IEEE operation, no contraction:
+ *   sampler     GOLDEN = 0x9E3779B97F4A7C15;  mix(z): z = (z ^ z>>30) * 0xBF58476D1CE4E5B9,
+ *               z = (z ^ z>>27) * 0x94D049BB133111EB, z ^ z>>31  (uint64, wrapping)
+ *               hypothesis k, draw j = 0, 1, 2:  r_j = mix(seed + GOLDEN * (3k + j + 1))
+ *               a = mulhi64(r0, n)     b = mulhi64(r1, n - 1), b++ if b >= a
+ *               c = mulhi64(r2, n - 2), c++ if c >= min(a, b), then c++ if c >= max(a, b)
+ *               the samples are p0, p1, p2 = c of ids[a], ids[b], ids[c]: distinct, no rejection loop, no state
+ *   hypothesis  e1 = p1 - p0   e2 = p2 - p0   n = e1 x e2, each component (u*v) - (w*x)
+ *               l2 = (nx*nx + ny*ny) + nz*nz     d = -((nx*p0x + ny*p0y) + nz*p0z)     tau = (t*t) * l2
+ *               valid iff l2 > 0 and l2, d, tau finite; an invalid hypothesis scores 0
+ *   score       candidate v is an inlier iff s*s <= tau, s = ((nx*cx + ny*cy) + nz*cz) + d; the score is the
+ *               number of inliers
+ *   winner      the highest score of at least 3, ties to the lowest k; none: iteration -1, an all-zero mask,
+ *               the zero model, MC_OK
+ *   model       refine 0:  l = sqrt(l2)   n^ = n / l   d^ = -((n^x*p0x + n^y*p0y) + n^z*p0z); the inliers are
+ *               the hypothesis's own
+ *   refit       refine 1: over voxel ids 0 .. M-1 the leaves u = c_v - p0 and ux*ux, ux*uy, ux*uz, uy*uy, uy*uz,
+ *               uz*uz for an inlier of the winner, +0.0 otherwise; each of the nine sums is the balanced
+ *               adjacent-pair tree over the leaves padded with +0.0 to the power of two >= max(M, 256) (a
+ *               function of the cloud, not of workgroups or atomics).  m = s / n_in, E = P / n_in,
+ *               C = E - m m^T and the unit eigenvector of C's smallest eigenvalue as the normals compute them;
+ *               q = p0 + m;  d^ = -((n^x*qx + n^y*qy) + n^z*qz); the inliers are the candidates with
+ *               fabs(((n^x*cx + n^y*cy) + n^z*cz) + d^) <= t
+ *   sign        the whole model is negated when the component of n^ of largest magnitude is negative (the lowest
+ *               axis wins a tie), as the normals' rule; in the refit before d^ is computed
+ * The sampler draws voxel ids: the result is a function of the cloud in its order and of the seed, not of the
+ * voxel set alone.
+ * d_among (M,) uint8 or NULL; d_inliers (M,) uint8 0 / 1 or NULL; host outputs: model[4] = n^x, n^y, n^z, d^;
+ * cov[6] = C (xx, xy, xz, yy, yz, zz; zeros when not refined; may be NULL); samples[3] voxel ids (-1 without a
+ * winner); stats[4] = iteration, score (the RANSAC score, also after a refit), n_inliers, refined.
+ * MC_ERR_INVALID before any launch: a NULL ctx, model, samples or stats, distance not finite or <= 0,
+ * num_iterations outside 1 .. 2^20, refine not 0 or 1, fewer than three voxels (M = 0 among them); after the
+ * mask's scan: fewer than three candidates.  No successful build: MC_ERR_STATE.  Device memory, with the voxel
+ * filter's: 5 B per voxel (9 with d_among), 80 B per hypothesis, and 72 B per 256 voxels of the padded tree,
+ * beside the normals' centroids. */
+int mc_voxel_plane(mc_ctx* ctx, double distance, int32_t num_iterations, uint64_t seed, int32_t refine,
+                   const uint8_t* d_among, uint8_t* d_inliers, double* model, double* cov, int32_t* samples,
+                   int64_t* stats);
+/* the hypotheses one launch of the score phase takes (its workgroup counters); more run in further launches */
+int mc_voxel_plane_chunk(void);
+/* The voxels of the live build whose byte of d_mask (M,) uint8 is non-zero, in the cloud's order, into the
+ * one-frame batch out: each voxel's four float32 values are what mc_voxel_emit_batch writes for it, the padding
+ * of the last 256-point block as there.  out->N must equal the number of set bytes (the mask's scan counts
+ * them): otherwise MC_ERR_INVALID, and out is not marked written.  No successful build: MC_ERR_STATE. */
+int mc_voxel_emit_selected(mc_ctx* ctx, const uint8_t* d_mask, mc_batch* out);
+/* event time (ms) of the timed phases since the last read: ms_phase[6] = compact (the candidates of a call with
+ * d_among), sample, score (ceil(num_iterations / mc_voxel_plane_chunk()) launches), mask, moments, select (the
+ * mask's compaction and the emit of mc_voxel_emit_selected); *launches = timed regions */
+int mc_timing_read_plane(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

@@ -27,7 +27,10 @@ Drop-in surface (reference file:line in each docstring):
                          VoxelCloud.normals(radius, max_nn=30, viewpoint, covariance) -> VoxelNormals, the viewer's
                          estimate_normals (read_pointcloud.py:81-84) from the live build, a function of the voxel set;
                          VoxelCloud.clusters(eps, min_points=10, weighted) -> VoxelClusters, DBSCAN over the live build:
-                         noise removal and segmentation (docs/Comprehensive Guide.md:488-491), the same on every run
+                         noise removal and segmentation (docs/Comprehensive Guide.md:488-491), the same on every run;
+                         VoxelCloud.segment_plane(distance_threshold, num_iterations=1000, seed=0, refine, among)
+                         -> VoxelPlane, RANSAC plane segmentation (the ground filter of read_pointcloud.py:244-257), and
+                         VoxelCloud.select(mask) -> Batch, the cloud cut by a mask on the device
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
 from . import _lib, codecs, config, coords, csim_export, dist, ingest, las, raymarch, runtime, trajectory, voxel  # noqa: F401
@@ -42,6 +45,6 @@ from .config import default_config, validate_config  # noqa: F401
 from .raymarch import LiDARSimulator  # noqa: F401
 from .runtime import Batch, Context, default_context  # noqa: F401
 from .simulator import LiDARMotionSimulator  # noqa: F401
-from .voxel import VoxelCloud, VoxelClusters, VoxelNormals, voxel_downsample  # noqa: F401
+from .voxel import VoxelCloud, VoxelClusters, VoxelNormals, VoxelPlane, voxel_downsample  # noqa: F401
 
 __version__ = "0.1.0"

@@ -141,6 +141,11 @@ _SIGS = {
     "mc_voxel_clusters": (c_int, [c_void_p, c_double, c_int32, c_int32, c_void_p, c_void_p, _pi64]),
     "mc_voxel_cluster_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mc_timing_read_clusters": (c_int, [c_void_p, _pd, _pi64]),
+    # the plane segmentation of the voxel cloud and the selection of a subset into a batch
+    "mc_voxel_plane": (c_int, [c_void_p, c_double, c_int32, c_uint64, c_int32, c_void_p, c_void_p, _pd, _pd, _pi32, _pi64]),
+    "mc_voxel_plane_chunk": (c_int, []),
+    "mc_voxel_emit_selected": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mc_timing_read_plane": (c_int, [c_void_p, _pd, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

@@ -4,16 +4,19 @@
 // left for its emits) is the CtxExt in the context's voxel slot (internal.hpp): the other translation
 // units see only that hook.  mc_voxel_release frees it early; mc_destroy frees what is left.  The surface
 // normals of the built cloud (mc_voxel_normals; kernels in normals.hpp) and its density clustering
-// (mc_voxel_clusters; kernels in cluster.hpp) read that state and keep theirs in it.
+// (mc_voxel_clusters; kernels in cluster.hpp) read that state and keep theirs in it; so do its plane segmentation
+// and the selection of a subset into a batch (mc_voxel_plane, mc_voxel_emit_selected; kernels in plane.hpp).
 #include "../../include/mcdeskew.h"
 #include "voxel.hpp"
 #include "normals.hpp"
 #include "cluster.hpp"
+#include "plane.hpp"
 #include "internal.hpp"
 #include "hostutil.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <vector>
 
 using namespace mc;
 
@@ -22,6 +25,7 @@ namespace {
 enum { kInsert = 0, kRank = 1, kAccumulate = 2, kFinalise = 3, kPhases = 4 };
 enum { kNrmCentroids = 0, kNrmWindow = 1, kNrmCap = 2, kNrmPhases = 3 };
 enum { kClDensity = 0, kClUnion = 1, kClLabel = 2, kClNumber = 3, kClStats = 4 };
+enum { kPlCompact = 0, kPlSample = 1, kPlScore = 2, kPlMask = 3, kPlMoments = 4, kPlSelect = 5, kPlanePhases = 6 };
 
 struct VoxState : mcimpl::CtxExt {
   // table (a power of two of slots), per-point arrays (points / chunks), per-voxel records
@@ -53,12 +57,20 @@ struct VoxState : mcimpl::CtxExt {
   bool cl_current = false;
   int64_t cl_K = 0;
   EventPairs cl_ev[kClusterPhases];
+  // the plane segmentation and the selection: the ascending voxel ids of a mask and their scan, the hypothesis
+  // table, the scores, the inlier byte of every voxel under the last model, and the levels of the refit's tree
+  DevBuf<uint32_t> pl_ids, pl_chunk, pl_meta, pl_score, pl_count;
+  DevBuf<double> pl_hyp, pl_tree;
+  DevBuf<int32_t> pl_samples;
+  DevBuf<uint8_t> pl_mask;
+  EventPairs pl_ev[kPlanePhases];
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
     for (auto& v : ev) ev_destroy(v);
     for (auto& v : nrm_ev) ev_destroy(v);
     for (auto& v : cl_ev) ev_destroy(v);
+    for (auto& v : pl_ev) ev_destroy(v);
   }
 };
 
@@ -184,6 +196,83 @@ int centroids(mc_ctx* c, VoxState* s) {
   }
   HIPCHK(hipGetLastError());
   s->cent_current = true;
+  return MC_OK;
+}
+
+// the ascending voxel ids of the set bytes of d_mask (M > 0) into pl_ids, and their number (one synchronisation)
+int compact(mc_ctx* c, VoxState* s, const uint8_t* d_mask, int phase, int64_t* n) {
+  const int64_t M = s->M;
+  const uint32_t blocks = (uint32_t)((M + kVoxBlock - 1) / kVoxBlock);
+  if (int r = ctx_reserve(c, s->pl_ids, (size_t)M)) return r;
+  if (int r = ctx_reserve(c, s->pl_chunk, (size_t)blocks)) return r;
+  if (!s->pl_meta) if (int r = s->pl_meta.alloc(2)) return r;
+  {
+    TimedRegion tr(c, &s->pl_ev[phase], c->stream);
+    hipLaunchKernelGGL(k_pl_flag, dim3(blocks), dim3(kVoxBlock), 0, c->stream, d_mask, M, s->pl_chunk.get());
+    hipLaunchKernelGGL(k_vox_scan, dim3(1), dim3(kVoxBlock), 0, c->stream, s->pl_chunk.get(), (int64_t)blocks, s->pl_meta.get());
+    hipLaunchKernelGGL(k_pl_scatter, dim3(blocks), dim3(kVoxBlock), 0, c->stream, d_mask, M, (const uint32_t*)s->pl_chunk.get(),
+                       s->pl_ids.get());
+  }
+  HIPCHK(hipGetLastError());
+  uint32_t meta[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(meta, s->pl_meta, sizeof meta, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((int64_t)meta[1] > M) return fail(MC_ERR_STATE, "voxel mask: %u set bytes of %lld voxels", meta[1], (long long)M);
+  *n = (int64_t)meta[1];
+  return MC_OK;
+}
+
+// pl_mask = the candidates inside (n, d) and their number (one synchronisation)
+int plane_mask(mc_ctx* c, VoxState* s, const uint8_t* d_among, const double model[4], double bound, bool refined,
+               int64_t* n_inliers) {
+  PlaneMaskArgs a = {};
+  a.cent = s->cent; a.among = d_among; a.M = s->M;
+  std::copy_n(model, 3, a.n);
+  a.d = model[3];
+  a.bound = bound;
+  a.refined = refined ? 1 : 0;
+  a.mask = s->pl_mask; a.count = s->pl_count;
+  {
+    TimedRegion tr(c, &s->pl_ev[kPlMask], c->stream);
+    HIPCHK(hipMemsetAsync(s->pl_count, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_pl_mask, dim3((uint32_t)((s->M + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  uint32_t count = 0;
+  HIPCHK(hipMemcpyAsync(&count, s->pl_count, sizeof count, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  *n_inliers = (int64_t)count;
+  return MC_OK;
+}
+
+// the nine tree sums of pl_mask's voxels about p0 (one synchronisation)
+int plane_moments(mc_ctx* c, VoxState* s, const double p0[3], double sums[kPlaneSums]) {
+  const int64_t L = plane_leaves(s->M);
+  size_t words = 0;
+  for (int64_t cnt = L / kVoxBlock;; cnt /= kVoxBlock) {
+    words += (size_t)kPlaneSums * cnt;
+    if (cnt < kVoxBlock) break;
+  }
+  if (int r = ctx_reserve(c, s->pl_tree, words)) return r;
+  int64_t cnt = L / kVoxBlock;
+  double* cur = s->pl_tree;
+  {
+    TimedRegion tr(c, &s->pl_ev[kPlMoments], c->stream);
+    hipLaunchKernelGGL(k_pl_moments, dim3((uint32_t)cnt), dim3(kVoxBlock), 0, c->stream, (const double*)s->cent.get(),
+                       (const uint8_t*)s->pl_mask.get(), s->M, p0[0], p0[1], p0[2], cur);
+    while (cnt >= kVoxBlock) {
+      double* next = cur + kPlaneSums * cnt;
+      hipLaunchKernelGGL(k_pl_tree, dim3((uint32_t)(cnt / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, (const double*)cur, cnt, next);
+      cur = next;
+      cnt /= kVoxBlock;
+    }
+  }
+  HIPCHK(hipGetLastError());
+  // fewer than 256 partials per sum are left: the last levels of the same tree, here
+  std::vector<double> top((size_t)kPlaneSums * cnt);
+  HIPCHK(hipMemcpyAsync(top.data(), cur, top.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < kPlaneSums; ++k) sums[k] = plane_tree(top.data() + (size_t)k * cnt, cnt, 1);
   return MC_OK;
 }
 
@@ -472,6 +561,141 @@ int mc_timing_read_clusters(mc_ctx* c, double* ms_phase, int64_t* launches) {
   return MC_OK;
 }
 
+int mc_voxel_plane_chunk(void) { return kPlaneChunk; }
+
+int mc_voxel_plane(mc_ctx* c, double distance, int32_t num_iterations, uint64_t seed, int32_t refine, const uint8_t* d_among,
+                   uint8_t* d_inliers, double* model, double* cov, int32_t* samples, int64_t* stats) {
+  if (model) std::fill_n(model, 4, 0.0);
+  if (cov) std::fill_n(cov, 6, 0.0);
+  if (samples) std::fill_n(samples, 3, -1);
+  if (stats) { stats[0] = -1; stats[1] = stats[2] = stats[3] = 0; }
+  CHECK_ARG(c && model && samples && stats, "NULL argument");
+  CHECK_ARG(std::isfinite(distance) && distance > 0.0, "distance must be finite and > 0 (got %g)", distance);
+  CHECK_ARG(num_iterations >= 1 && num_iterations <= kPlaneMaxIterations, "num_iterations must be in 1..%d (got %d)",
+            kPlaneMaxIterations, num_iterations);
+  CHECK_ARG(refine == 0 || refine == 1, "refine must be 0 or 1 (got %d)", refine);
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_plane needs a successful mc_voxel_build_* first");
+  const int64_t M = s->M;
+  CHECK_ARG(M >= 3, "a plane needs three candidate voxels (the cloud has %lld)", (long long)M);
+  DeviceGuard g(c->device);
+  const int32_t K = num_iterations;
+  if (int r = centroids(c, s)) return r;
+  int64_t n = M;
+  if (d_among) {
+    if (int r = compact(c, s, d_among, kPlCompact, &n)) return r;
+    CHECK_ARG(n >= 3, "a plane needs three candidate voxels (the mask has %lld)", (long long)n);
+  }
+  if (int r = ctx_reserve(c, s->pl_hyp, (size_t)kPlaneHyp * K)) return r;
+  if (int r = ctx_reserve(c, s->pl_samples, (size_t)3 * K)) return r;
+  if (int r = ctx_reserve(c, s->pl_score, (size_t)K)) return r;
+  if (int r = ctx_reserve(c, s->pl_mask, (size_t)M)) return r;
+  if (!s->pl_count) if (int r = s->pl_count.alloc(1)) return r;
+  {
+    PlaneSampleArgs a = {};
+    a.cent = s->cent;
+    a.ids = d_among ? s->pl_ids.get() : nullptr;
+    a.n = n;
+    a.seed = seed;
+    a.K = K;
+    a.tt = distance * distance;
+    a.hyp = s->pl_hyp; a.samples = s->pl_samples;
+    TimedRegion tr(c, &s->pl_ev[kPlSample], c->stream);
+    hipLaunchKernelGGL(k_pl_sample, dim3((uint32_t)((K + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, a);
+  }
+  {
+    const int64_t tiles = (M + kPlaneTile - 1) / kPlaneTile;
+    const dim3 grid((uint32_t)std::min<int64_t>(tiles, kPlaneScoreGrid));
+    TimedRegion tr(c, &s->pl_ev[kPlScore], c->stream);
+    HIPCHK(hipMemsetAsync(s->pl_score, 0, (size_t)K * sizeof(uint32_t), c->stream));
+    for (int32_t k0 = 0; k0 < K; k0 += kPlaneChunk)
+      hipLaunchKernelGGL(k_pl_score, grid, dim3(kVoxBlock), 0, c->stream, (const double*)s->cent.get(), d_among, M,
+                         (const double*)s->pl_hyp.get(), k0, std::min<int32_t>(kPlaneChunk, K - k0), s->pl_score.get());
+  }
+  HIPCHK(hipGetLastError());
+  // pick, on the host: the scores come back with the call's first synchronisation
+  std::vector<uint32_t> score((size_t)K);
+  HIPCHK(hipMemcpyAsync(score.data(), s->pl_score, score.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const int32_t k = plane_pick(score.data(), K);
+  if (k < 0) {   // no valid hypothesis with three inliers: an all-false mask and the zero model
+    HIPCHK(hipMemsetAsync(s->pl_mask, 0, (size_t)M, c->stream));
+    if (d_inliers) HIPCHK(hipMemsetAsync(d_inliers, 0, (size_t)M, c->stream));
+    return MC_OK;
+  }
+  PlaneHyp h;
+  static_assert(sizeof(PlaneHyp) == kPlaneHyp * sizeof(double), "the hypothesis record");
+  HIPCHK(hipMemcpyAsync(&h, s->pl_hyp + (size_t)kPlaneHyp * k, sizeof h, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(samples, s->pl_samples + (size_t)3 * k, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const double raw[4] = {h.n[0], h.n[1], h.n[2], h.d};
+  int64_t n_in = 0;
+  if (int r = plane_mask(c, s, d_among, raw, h.tau, false, &n_in)) return r;
+  if (n_in != (int64_t)score[k])
+    return fail(MC_ERR_STATE, "voxel plane: hypothesis %d scored %u and holds %lld voxels", k, score[k], (long long)n_in);
+  stats[0] = k;
+  stats[1] = (int64_t)score[k];
+  if (refine) {
+    double sums[kPlaneSums], C[6];
+    if (int r = plane_moments(c, s, h.p0, sums)) return r;
+    plane_refit(sums, (int32_t)n_in, h.p0, model, C);
+    if (cov) std::copy_n(C, 6, cov);
+    if (int r = plane_mask(c, s, d_among, model, distance, true, &n_in)) return r;
+    stats[3] = 1;
+  } else {
+    plane_model(h, model);
+  }
+  stats[2] = n_in;
+  if (d_inliers) HIPCHK(hipMemcpyAsync(d_inliers, s->pl_mask, (size_t)M, hipMemcpyDeviceToDevice, c->stream));
+  return MC_OK;
+}
+
+int mc_voxel_emit_selected(mc_ctx* c, const uint8_t* d_mask, mc_batch* out) {
+  CHECK_ARG(c && out, "NULL argument");
+  CHECK_ARG(out->ctx == c, "batch belongs to another context");
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_emit_selected needs a successful mc_voxel_build_* first");
+  CHECK_ARG(s->M == 0 || d_mask, "d_mask is NULL");
+  DeviceGuard g(c->device);
+  int64_t n = 0;
+  if (s->M > 0) if (int r = compact(c, s, d_mask, kPlSelect, &n)) return r;
+  CHECK_ARG(out->F == 1 && out->N == n, "the out batch must be one frame of exactly %lld points (it has %d frames, %lld points)",
+            (long long)n, out->F, (long long)out->N);
+  if (out->P > 0) {
+    VoxOut a = {};
+    a.keys = s->keys; a.vslot = s->vslot; a.sums = s->sums; a.cnt = s->cnt;
+    a.M = s->M;
+    a.h = s->h;
+    std::copy_n(s->o, 3, a.o);
+    a.cols = out->d_cols;
+    a.C = out->C;
+    {
+      TimedRegion tr(c, &s->pl_ev[kPlSelect], c->stream);
+      hipLaunchKernelGGL(k_pl_emit_selected, dim3((uint32_t)((out->P / 4 + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0,
+                         c->stream, a, out->P, (const uint32_t*)s->pl_ids.get(), n);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  return mcimpl::batch_columns_written(out, mcimpl::kWroteAllQueued);
+}
+
+int mc_timing_read_plane(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  int64_t total = 0;
+  for (int k = 0; k < kPlanePhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
+  if (VoxState* s = state_of(c, false)) {
+    for (int k = 0; k < kPlanePhases; ++k) {
+      int64_t n = 0;
+      if (int r = sum_events(c, s->pl_ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
+      total += n;
+    }
+  }
+  if (launches) *launches = total;
+  return MC_OK;
+}
+
 int mc_voxel_release(mc_ctx* c) {
   if (!c) return MC_OK;
   VoxState* s = state_of(c, false);
@@ -481,6 +705,7 @@ int mc_voxel_release(mc_ctx* c) {
   for (auto& v : s->ev) ev_recycle(c, v);
   for (auto& v : s->nrm_ev) ev_recycle(c, v);
   for (auto& v : s->cl_ev) ev_recycle(c, v);
+  for (auto& v : s->pl_ev) ev_recycle(c, v);
   c->ext[mcimpl::kSlotVoxel].reset();
   return MC_OK;
 }

@@ -254,18 +254,18 @@ __global__ __launch_bounds__(kVoxBlock) void k_vox_emit_rows(VoxOut a) {
   }
 }
 
-// four voxels per lane: one float4 per column of the out batch's single frame (padding slots get 0)
-__global__ __launch_bounds__(kVoxBlock) void k_vox_emit_batch(VoxOut a, int64_t P) {
-  const int64_t p0 = ((int64_t)blockIdx.x * kVoxBlock + threadIdx.x) * 4;
-  if (p0 >= P) return;
+// four points per lane: one float4 per column of the out batch's single frame; point p < n is voxel voxel_of(p),
+// the padding slots from n on get 0
+template <typename VoxelOf>
+__device__ __forceinline__ void vox_emit_four(const VoxOut& a, int64_t p0, int64_t n, VoxelOf&& voxel_of) {
   vox_f4 col[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    if (p0 + j < a.M) {
+    if (p0 + j < n) {
       int32_t k[3];
       double out[4];
-      int64_t n;
-      vox_finalise_one(a, p0 + j, k, out, &n);
+      int64_t cnt;
+      vox_finalise_one(a, voxel_of(p0 + j), k, out, &cnt);
 #pragma unroll
       for (int c = 0; c < 4; ++c) col[c][j] = (float)out[c];
     }
@@ -273,6 +273,13 @@ __global__ __launch_bounds__(kVoxBlock) void k_vox_emit_batch(VoxOut a, int64_t 
   float* b = a.cols + bidx(a.C, 0, p0);
 #pragma unroll
   for (int c = 0; c < 4; ++c) *reinterpret_cast<vox_f4*>(b + c * kBlkPts) = col[c];
+}
+
+// the whole cloud: point p is voxel p
+__global__ __launch_bounds__(kVoxBlock) void k_vox_emit_batch(VoxOut a, int64_t P) {
+  const int64_t p0 = ((int64_t)blockIdx.x * kVoxBlock + threadIdx.x) * 4;
+  if (p0 >= P) return;
+  vox_emit_four(a, p0, a.M, [](int64_t p) { return p; });
 }
 
 }  // namespace mc

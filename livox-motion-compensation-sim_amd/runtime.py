@@ -383,6 +383,15 @@ class Context:
         return {"density_ms": ms[0], "union_ms": ms[1], "label_ms": ms[2], "number_ms": ms[3], "stats_ms": ms[4],
                 "regions": n.value}
 
+    def read_timing_plane(self) -> dict:
+        """Event time (ms) of the phases of VoxelCloud.segment_plane and VoxelCloud.select since the last read
+        (mc_timing_read_plane)."""
+        ms = np.zeros(6, np.float64)
+        n = c_int64()
+        check(self.lib.mc_timing_read_plane(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_plane")
+        return {"compact_ms": ms[0], "sample_ms": ms[1], "score_ms": ms[2], "mask_ms": ms[3], "moments_ms": ms[4],
+                "select_ms": ms[5], "regions": n.value}
+
     def device_buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)
 

@@ -6,6 +6,8 @@ of a drive are accumulated into one cloud and most points re-observe the same su
   VoxelCloud.n_voxels, .batch(), .rows(), .point_counts(), .keys(), .close()
   VoxelCloud.normals(radius, max_nn=30, viewpoint=None, covariance=False)  -> VoxelNormals
   VoxelCloud.clusters(eps, min_points=10, weighted=False)  -> VoxelClusters
+  VoxelCloud.segment_plane(distance_threshold, num_iterations=1000, seed=0, refine=True, among=None)  -> VoxelPlane
+  VoxelCloud.select(mask, with_pcd_len=False)  -> Batch
 
 One output point per occupied voxel: the mean of the voxel's points and of their intensities.  The
 per-voxel sums are integers (the coordinate inside its voxel in 2^-32 voxel units, the intensity in
@@ -45,6 +47,40 @@ component of core voxels; a voxel that is not core joins the cluster of its core
 partition is a function of the voxel set and the numbering of the cloud's order: the same bits on every run.
 min_points = 1 is Euclidean cluster extraction (connected components).  Refused with ValueError: an eps that
 is not finite and > 0 or exceeds 4 h, min_points not an integer >= 1, weighted not a bool.
+
+Plane segmentation (csrc/plane_core.hpp, csrc/plane.hpp; ``mc_voxel_plane``): the ground filter of the reference's
+processing chain (read_pointcloud.py:244-257), RANSAC as open3d's segment_plane, here defined op for op and integer
+where it can be, so a VoxelPlane is the same bits on every run and equal to the NumPy restatement of
+tests/planes.py.  c_v: the live build's centroids by voxel id; t the threshold; K = num_iterations; ids the
+candidate voxel ids ascending (``among``: the voxels of a mask; None: all), n their number (n < 3: ValueError).
+Every float64 line is one IEEE operation:
+
+  sampler     GOLDEN = 0x9E3779B97F4A7C15;  mix(z): z = (z ^ z>>30) * 0xBF58476D1CE4E5B9;
+              z = (z ^ z>>27) * 0x94D049BB133111EB; return z ^ z>>31   (uint64, wrapping)
+              hypothesis k, draw j in {0, 1, 2}: r_j = mix(seed + GOLDEN * (3k + j + 1))
+              a = mulhi64(r0, n);  b = mulhi64(r1, n-1), b++ if b >= a;
+              c = mulhi64(r2, n-2), c++ if c >= min(a, b), then c++ if c >= max(a, b)
+              p0, p1, p2 = the centroids of ids[a], ids[b], ids[c]: distinct by construction, no state
+  hypothesis  e1 = p1 - p0;  e2 = p2 - p0;  n = e1 x e2, each component (u*v) - (w*x)
+              l2 = (nx*nx + ny*ny) + nz*nz;  d = -((nx*p0x + ny*p0y) + nz*p0z);  tau = (t*t) * l2
+              valid iff l2 > 0 and l2, d, tau are finite; an invalid hypothesis scores 0
+  score       a candidate is an inlier iff s*s <= tau, s = ((nx*cx + ny*cy) + nz*cz) + d; the score is their number
+  winner      the highest score of at least 3, ties to the lowest k; none: iteration -1, an all-False mask, a zero model
+  refine=False  l = sqrt(l2);  n^ = n / l;  d^ = -((n^x*p0x + n^y*p0y) + n^z*p0z); the hypothesis's own inliers
+  refine=True   over the voxel ids 0 .. M-1: u = c_v - p0 and ux*ux, ux*uy, ux*uz, uy*uy, uy*uz, uz*uz for an inlier,
+              +0.0 otherwise; each of the nine sums is the balanced adjacent-pair tree over the leaves padded with
+              +0.0 to the power of two >= max(M, 256) (``while len(a) > 1: a = a[0::2] + a[1::2]``); m = s / n_in,
+              E = P / n_in, C = E - m m^T and its eigenvector as the normals compute them; q = p0 + m;
+              d^ = -((n^x*qx + n^y*qy) + n^z*qz); inliers: fabs(((n^x*cx + n^y*cy) + n^z*cz) + d^) <= t; the score stays
+  sign        the model is negated when the component of n^ of largest magnitude is negative (lowest axis on a tie)
+
+The sampler draws voxel ids, so the result is a function of the cloud in its order and the seed.  Refused with
+ValueError: a threshold that is not finite and > 0, num_iterations not an integer in 1..2^20, a seed not an integer
+in 0..2^64-1, refine not a bool, a mask that is not (M,) bool, fewer than three candidates.
+
+Selection (``mc_voxel_emit_selected``): ``select(mask)`` is the stable compaction of the cloud by a (M,) bool mask
+into a one-frame Batch on the device, every value bit-equal to ``batch()``'s for that voxel: ``select(~plane.inliers)``
+is the non-ground cloud, ``select(labels == k)`` a segment, ``select(labels >= 0)`` the outlier filter.
 """
 from __future__ import annotations
 
@@ -55,7 +91,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from ._lib import check, ptr
+from ._lib import check, load, ptr
 from .runtime import Batch, Context, default_context
 
 MAX_POINTS = 2 ** 31 - 1
@@ -138,6 +174,52 @@ def _clusters_args(eps, min_points, weighted, h):
     if not isinstance(weighted, (bool, np.bool_)):
         raise ValueError(f"weighted must be True or False, got {weighted!r}")
     return e, int(min_points), int(bool(weighted))
+
+
+MAX_ITERATIONS = 2 ** 20
+
+
+class VoxelPlane(NamedTuple):
+    """What :meth:`VoxelCloud.segment_plane` returns."""
+    model: np.ndarray               # (4,) float64 n^x, n^y, n^z, d^: n^ . c + d^ = 0
+    inliers: np.ndarray             # (M,) bool in the cloud's order
+    n_inliers: int
+    score: int                      # the winning hypothesis's RANSAC score, also after a refit
+    iteration: int                  # the winning hypothesis k; -1: no valid hypothesis
+    samples: np.ndarray             # (3,) int32 voxel ids of the winner's samples (-1 without a winner)
+    covariance: np.ndarray | None   # (6,) float64 xx, xy, xz, yy, yz, zz of the refit; None when not refined
+    refined: bool
+
+
+def _mask_arg(mask, M, name):
+    """A (M,) bool mask as contiguous bytes, checked before a device is touched."""
+    if not isinstance(mask, np.ndarray) or mask.dtype != np.bool_ or mask.shape != (M,):
+        raise ValueError(f"{name} must be a bool array of shape ({M},), got "
+                         f"{getattr(mask, 'dtype', type(mask).__name__)} {getattr(mask, 'shape', '')}")
+    return np.ascontiguousarray(mask).view(np.uint8)
+
+
+def _plane_args(distance_threshold, num_iterations, seed, refine, among, M):
+    """(t, K, seed, refine as 0 / 1, among as bytes or None), checked before a device is touched."""
+    try:
+        t = float(distance_threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"distance_threshold must be a number > 0, got {distance_threshold!r}") from None
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"distance_threshold must be finite and > 0, got {distance_threshold!r}")
+    if (isinstance(num_iterations, bool) or not isinstance(num_iterations, (int, np.integer))
+            or not 1 <= num_iterations <= MAX_ITERATIONS):
+        raise ValueError(f"num_iterations must be an integer in 1..{MAX_ITERATIONS}, got {num_iterations!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be an integer in 0..2^64-1, got {seed!r}")
+    if not isinstance(refine, (bool, np.bool_)):
+        raise ValueError(f"refine must be True or False, got {refine!r}")
+    return t, int(num_iterations), int(seed), int(bool(refine)), None if among is None else _mask_arg(among, M, "among")
+
+
+def plane_score_chunk() -> int:
+    """The hypotheses one launch of the score phase takes (``mc_voxel_plane_chunk``); needs no device."""
+    return int(load().mc_voxel_plane_chunk())
 
 
 class VoxelCloud:
@@ -249,6 +331,52 @@ class VoxelCloud:
         return VoxelClusters(labels, density, K, np.ascontiguousarray(raw[2 * K:3 * K]),
                              np.ascontiguousarray(raw[:2 * K]).view(np.int64), np.ascontiguousarray(raw[3 * K:6 * K]).reshape(K, 3),
                              np.ascontiguousarray(raw[6 * K:]).reshape(K, 3))
+
+    def segment_plane(self, distance_threshold, num_iterations: int = 1000, seed: int = 0, refine: bool = True,
+                      among=None) -> "VoxelPlane":
+        """RANSAC plane segmentation of the voxel points, open3d's ``segment_plane(distance_threshold, 3,
+        num_iterations)`` as a function of the cloud in its order and the seed (module docstring; include/mcdeskew.h
+        ``mc_voxel_plane``).  ``refine``: the model is refitted on the winner's inliers and the inliers are taken
+        again.  ``among``: a (M,) bool mask of the candidates — ``among=~ground.inliers`` finds the next plane.  Any
+        number of calls on one live cloud."""
+        M = self.n_voxels
+        t, K, sd, rf, cand = _plane_args(distance_threshold, num_iterations, seed, refine, among, M)
+        self._live()
+        if (M if cand is None else int(np.count_nonzero(cand))) < 3:
+            raise ValueError("a plane needs three candidate voxels")
+        ctx = self.ctx
+        bufs = [ctx.device_buffer(M), ctx.device_buffer(M) if cand is not None else None]
+        try:
+            if cand is not None:
+                bufs[1].from_host(cand)
+            model, cov = np.zeros(4), np.zeros(6)
+            samples, stats = np.zeros(3, np.int32), np.zeros(4, np.int64)
+            check(ctx.lib.mc_voxel_plane(ctx.handle, t, K, sd, rf, bufs[1].ptr if cand is not None else None, bufs[0].ptr,
+                                         ptr(model, c_double), ptr(cov, c_double), ptr(samples, c_int32), ptr(stats, c_int64)),
+                  "segment_plane")
+            inliers = bufs[0].to_host(np.uint8, count=M).view(np.bool_)
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.close()
+        refined = bool(stats[3])
+        return VoxelPlane(model, inliers, int(stats[2]), int(stats[1]), int(stats[0]), samples, cov if refined else None, refined)
+
+    def select(self, mask, with_pcd_len: bool = False) -> Batch:
+        """The voxel points whose ``mask`` entry is True, in the cloud's order, as a one-frame float32 Batch like
+        :meth:`batch`'s (every value bit-equal to it), compacted on the device (``mc_voxel_emit_selected``)."""
+        m = _mask_arg(mask, self.n_voxels, "mask")
+        self._live()
+        ctx = self.ctx
+        out = Batch(ctx, [int(np.count_nonzero(m))], with_pcd_len=with_pcd_len)
+        buf = ctx.device_buffer(max(len(m), 1))
+        try:
+            if len(m):
+                buf.from_host(m)
+            check(ctx.lib.mc_voxel_emit_selected(ctx.handle, buf.ptr, out.handle), "select")
+        finally:
+            buf.close()
+        return out
 
     def close(self):
         """Give the filter's device scratch back (a later call allocates it again)."""
