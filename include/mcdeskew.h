@@ -620,6 +620,74 @@ int mc_voxel_emit_selected(mc_ctx* ctx, const uint8_t* d_mask, mc_batch* out);
  * mask's compaction and the emit of mc_voxel_emit_selected); *launches = timed regions */
 int mc_timing_read_plane(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 
+/* ---- registration against the voxel cloud (csrc/register_core.hpp, register.hpp) --------------------------------
+ * How well a scan sits on the map, and the small pose correction that makes it sit better: the nearest centroid of
+ * the live build for points that are not its voxels, and point-to-plane ICP on it.  The source is a batch (its
+ * float32 x, y, z read as float64; frame -1: all frames as one rigid body, else that frame alone) or device float64
+ * rows (x, y, z first, ld >= 3); a point's index is its place in the source.  With h and the origin the build's,
+ * (R, t) the pose (4 x 4 row-major, last row 0, 0, 0, 1); every line ONE IEEE float64 operation, no contraction:
+ *   move      q = R p + t, each component ((R0*x + R1*y) + R2*z) + t
+ *   cell      the voxel filter's k of q (a = q - o, g = a / h, k = floor(g)); a q that is not finite or whose cell is
+ *             outside [-2^20, 2^20) on an axis has no nearest voxel (id -1, d2 inf) and is not an error
+ *   nearest   W = ceil(max_distance / h), r2 = max_distance * max_distance; the occupied cells within W of q's cell
+ *             on every axis, walked dkx, dky, dkz ascending = ascending packed key (cells outside the key range do
+ *             not exist): u = c_j - q, d2 = (u.x*u.x + u.y*u.y) + u.z*u.z; a candidate when d2 <= r2; the winner is
+ *             the smallest d2, ties to the cell walked first (the lower packed key).  The implementation leaves out
+ *             cells whose box is farther from q than the smallest d2 it knows (they can neither win nor tie): no
+ *             output differs from the plain walk's
+ *   pair      the winner v, when the normal of v was estimated from three neighbours or more (the normals above with
+ *             normals_radius, max_nn and no viewpoint, computed once per call); otherwise the point has no pair (the
+ *             next-nearest voxel is not tried)
+ *   leaves    d = q - c_v;  r = (nx*dx + ny*dy) + nz*dz;  a = q x n, each component (u*v) - (w*x);  J = (a, n);
+ *             the 21 products J_i*J_j (i <= j, row-major), the 6 products J_i*r, and r*r; +0.0 each without a pair
+ *   sums      each of the 28 by the balanced adjacent-pair tree of the plane refit over the source point index, the
+ *             leaves padded with +0.0 to the power of two >= max(N, 256); pairs: an integer sum
+ *   step      fewer than 6 pairs: status too_few_pairs.  A x = -b by Cholesky: A = L L^T row by row (i, then j <= i),
+ *             acc = A_ij, acc = acc - L_ik*L_jk for k ascending, L_ii = sqrt(acc), L_ij = acc / L_jj; a diagonal acc
+ *             that is not finite or not > 0: status singular.  y_i = (-b_i - sum_k<i L_ik*y_k) / L_ii for i ascending;
+ *             x_i = (y_i - sum_k>i L_ki*x_k) / L_ii for i descending, k ascending.  x = (w, v)
+ *   update    hx = 0.5*w.x ..;  n = sqrt(1 + ((hx*hx + hy*hy) + hz*hz));  the quaternion (1/n, hx/n, hy/n, hz/n) as a
+ *             rotation dR (diagonal 1 - 2*(yy + zz) .., off-diagonal 2*(xy - wz) ..);  R <- dR R, t <- dR t + v, each
+ *             entry (a0 + a1) + a2
+ *   stop      after the update: converged when (w.x*w.x + w.y*w.y) + w.z*w.z <= tol_rotation^2 and the same of v
+ *             <= tol_translation^2; max_iterations when the last allowed iteration did not converge.  too_few_pairs
+ *             and singular return the pose before the failed step
+ * mc_voxel_nearest_*: d_ids (N,) int32 the nearest voxel's id (its row in the cloud's order) or -1, d_dist2 (N,)
+ * float64 d2 or inf; transform NULL: the identity.  mc_voxel_register_*: transformation[16]; history
+ * (max_iterations, 8), row i = pairs, sum r*r, w, v of iteration i (a failed step: zeros), `iterations` rows written;
+ * stats[4] = pairs (of the last iteration), iterations, status (0 converged, 1 max_iterations, 2 too_few_pairs,
+ * 3 singular), N.  Neither call changes the build; any number of calls per build.  One synchronisation and one copy
+ * of fewer than 256 x 28 partials and the pair count per iteration; the scratch is the voxel state's (4 B per
+ * source point, 36 B per voxel, 224 B per 256 source points of the padded tree) and is not reallocated by an
+ * iteration.  The result is the same bits on every run.
+ * MC_ERR_INVALID before any launch: a NULL ctx or output, a batch of another context, a frame outside the batch, an
+ * empty source (N = 0), max_distance not finite or <= 0 or max_distance / h > 4 (voxelise coarser or shrink the
+ * radius), a pose whose last row is not 0, 0, 0, 1, that is not finite or with |R^T R - I| > 1e-6 in an entry,
+ * max_iterations outside 1 .. 2^16, a negative or non-finite tolerance, and the normals' own refusals.  No successful
+ * build: MC_ERR_STATE.  An empty cloud (M = 0): every id is -1, and a registration ends with too_few_pairs. */
+typedef struct mc_register_params {
+  double max_distance;
+  double normals_radius;
+  double tol_rotation, tol_translation;
+  double init[16];          /* the starting pose, row-major */
+  int32_t max_nn;           /* of the normals: 0 or 3..64 */
+  int32_t max_iterations;
+} mc_register_params;
+int mc_voxel_nearest_batch(mc_ctx* ctx, const mc_batch* src, int32_t frame, double max_distance,
+                           const double* transform, int32_t* d_ids, double* d_dist2);
+int mc_voxel_nearest_f64(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t n, double max_distance,
+                         const double* transform, int32_t* d_ids, double* d_dist2);
+int mc_voxel_register_batch(mc_ctx* ctx, const mc_batch* src, int32_t frame, const mc_register_params* params,
+                            double* transformation, double* history, int64_t* stats);
+int mc_voxel_register_f64(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t n,
+                          const mc_register_params* params, double* transformation, double* history,
+                          int64_t* stats);
+/* time (ms) of the phases since the last read: ms_phase[5] = normals (the call's window and cap launches),
+ * correspond, leaves (with the first tree level), tree (the further levels; none below 65 536 source points), solve
+ * (the host's last levels, Cholesky and update, by the host's clock, counted while timing is enabled);
+ * *launches = timed regions */
+int mc_timing_read_register(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

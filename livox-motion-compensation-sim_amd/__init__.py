@@ -30,7 +30,10 @@ Drop-in surface (reference file:line in each docstring):
                          noise removal and segmentation (docs/Comprehensive Guide.md:488-491), the same on every run;
                          VoxelCloud.segment_plane(distance_threshold, num_iterations=1000, seed=0, refine, among)
                          -> VoxelPlane, RANSAC plane segmentation (the ground filter of read_pointcloud.py:244-257), and
-                         VoxelCloud.select(mask) -> Batch, the cloud cut by a mask on the device
+                         VoxelCloud.select(mask) -> Batch, the cloud cut by a mask on the device;
+                         VoxelCloud.nearest(src, max_distance, transform, frame) -> VoxelNearest and
+                         VoxelCloud.register(src, max_distance, init, ...) -> VoxelRegistration, a scan registered
+                         against the cloud by point-to-plane ICP, the whole iteration history the same on every run
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
 from . import _lib, codecs, config, coords, csim_export, dist, ingest, las, raymarch, runtime, trajectory, voxel  # noqa: F401
@@ -45,6 +48,7 @@ from .config import default_config, validate_config  # noqa: F401
 from .raymarch import LiDARSimulator  # noqa: F401
 from .runtime import Batch, Context, default_context  # noqa: F401
 from .simulator import LiDARMotionSimulator  # noqa: F401
-from .voxel import VoxelCloud, VoxelClusters, VoxelNormals, VoxelPlane, voxel_downsample  # noqa: F401
+from .voxel import (VoxelCloud, VoxelClusters, VoxelNearest, VoxelNormals, VoxelPlane, VoxelRegistration,  # noqa: F401
+                    voxel_downsample)  # noqa: F401
 
 __version__ = "0.1.0"

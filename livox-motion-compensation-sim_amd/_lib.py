@@ -46,6 +46,13 @@ _pi64 = POINTER(c_int64)
 _pi32 = POINTER(c_int32)
 _pf = POINTER(ctypes.c_float)
 
+
+class RegisterParams(ctypes.Structure):
+    """mc_register_params of include/mcdeskew.h."""
+    _fields_ = [("max_distance", c_double), ("normals_radius", c_double), ("tol_rotation", c_double),
+                ("tol_translation", c_double), ("init", c_double * 16), ("max_nn", c_int32), ("max_iterations", c_int32)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "mc_abi_version": (c_int, []),
@@ -146,6 +153,12 @@ _SIGS = {
     "mc_voxel_plane_chunk": (c_int, []),
     "mc_voxel_emit_selected": (c_int, [c_void_p, c_void_p, c_void_p]),
     "mc_timing_read_plane": (c_int, [c_void_p, _pd, _pi64]),
+    # the registration of a source against the voxel cloud (params: a pointer to RegisterParams)
+    "mc_voxel_nearest_batch": (c_int, [c_void_p, c_void_p, c_int32, c_double, _pd, c_void_p, c_void_p]),
+    "mc_voxel_nearest_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_double, _pd, c_void_p, c_void_p]),
+    "mc_voxel_register_batch": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, _pd, _pd, _pi64]),
+    "mc_voxel_register_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, _pd, _pd, _pi64]),
+    "mc_timing_read_register": (c_int, [c_void_p, _pd, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

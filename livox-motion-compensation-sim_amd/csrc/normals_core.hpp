@@ -68,22 +68,30 @@ MC_CORE_HD bool normals_find(const NormalsGrid& g, uint64_t key, uint32_t* v) {
 // cell's place in the window, ((dkx + R) (2R + 1) + dky + R) (2R + 1) + dkz + R, which ascends with the
 // packed key; v is the neighbour's voxel id (what the clustering of cluster_core.hpp needs beside it).  The walk
 // kFromCell: the walk starts at the cell of place `first`; planes, rows and cells before it are not probed.
-template <bool kFromCell = false, typename Fn>
+// skip: a walker may leave out a plane (its kx), a row (kx, ky) or a cell (kx, ky, kz) that cannot matter to it
+// (register_core.hpp's nearest-centroid search); NormalsNoSkip leaves nothing out.
+struct NormalsNoSkip {
+  MC_CORE_HD bool plane(int32_t) const { return false; }
+  MC_CORE_HD bool row(int32_t, int32_t) const { return false; }
+  MC_CORE_HD bool cell(const int32_t*) const { return false; }
+};
+
+template <bool kFromCell = false, typename Fn, typename Skip = NormalsNoSkip>
 MC_CORE_HD void normals_neighbours_v(const NormalsGrid& g, const int32_t ki[3], const double ci[3], const NormalsQuery& q,
-                                      Fn&& fn, int32_t first = 0) {
+                                      Fn&& fn, int32_t first = 0, const Skip& skip = Skip()) {
   MC_CORE_NO_CONTRACT
   const int32_t W = 2 * q.R + 1;
   int32_t ix = 0;
   for (int32_t dx = -q.R; dx <= q.R; ++dx) {
     int32_t k[3];
     k[0] = ki[0] + dx;
-    if ((kFromCell && ix + W * W <= first) || k[0] < kVoxelKeyMin || k[0] >= kVoxelKeyEnd) { ix += W * W; continue; }
+    if ((kFromCell && ix + W * W <= first) || k[0] < kVoxelKeyMin || k[0] >= kVoxelKeyEnd || skip.plane(k[0])) { ix += W * W; continue; }
     for (int32_t dy = -q.R; dy <= q.R; ++dy) {
       k[1] = ki[1] + dy;
-      if ((kFromCell && ix + W <= first) || k[1] < kVoxelKeyMin || k[1] >= kVoxelKeyEnd) { ix += W; continue; }
+      if ((kFromCell && ix + W <= first) || k[1] < kVoxelKeyMin || k[1] >= kVoxelKeyEnd || skip.row(k[0], k[1])) { ix += W; continue; }
       for (int32_t dz = -q.R; dz <= q.R; ++dz, ++ix) {
         k[2] = ki[2] + dz;
-        if ((kFromCell && ix < first) || k[2] < kVoxelKeyMin || k[2] >= kVoxelKeyEnd) continue;
+        if ((kFromCell && ix < first) || k[2] < kVoxelKeyMin || k[2] >= kVoxelKeyEnd || skip.cell(k)) continue;
         uint32_t v;
         if (!normals_find(g, voxel_pack(k), &v)) continue;
         const double* cj = g.cent + (int64_t)kNormalsCent * v;

@@ -152,21 +152,23 @@ __global__ __launch_bounds__(kVoxBlock) void k_pl_mask(PlaneMaskArgs a) {
   if ((threadIdx.x & 63) == 0 && wave) atomicAdd(a.count, wave);
 }
 
-// the sum of the workgroup's 256 values as the adjacent-pair tree gives it (every thread takes part); in thread 0
-__device__ __forceinline__ void plane_block_tree(double x[kPlaneSums], double* out, int64_t out_stride) {
-  __shared__ double part[kVoxBlock / 64][kPlaneSums];
+// the sums of the workgroup's 256 leaves of kW values each as the adjacent-pair tree gives them (every thread takes
+// part); thread c < kW stores sum c.  kW = kPlaneSums: the refit's; kRegSums: the registration's (register.hpp)
+template <int kW>
+__device__ __forceinline__ void plane_block_tree(double x[kW], double* out, int64_t out_stride) {
+  __shared__ double part[kVoxBlock / 64][kW];
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
 #pragma unroll
-    for (int c = 0; c < kPlaneSums; ++c) x[c] = x[c] + __shfl_xor(x[c], d, 64);
+    for (int c = 0; c < kW; ++c) x[c] = x[c] + __shfl_xor(x[c], d, 64);
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) {
 #pragma unroll
-    for (int c = 0; c < kPlaneSums; ++c) part[wave][c] = x[c];
+    for (int c = 0; c < kW; ++c) part[wave][c] = x[c];
   }
   __syncthreads();
-  if (threadIdx.x < kPlaneSums) {
+  if (threadIdx.x < kW) {
     const int c = threadIdx.x;
     const double lo = part[0][c] + part[1][c];
     const double hi = part[2][c] + part[3][c];
@@ -183,16 +185,17 @@ __global__ __launch_bounds__(kVoxBlock) void k_pl_moments(const double* cent, co
   const double* cv = cent + kNormalsCent * (v < M ? v : 0);
   const double c[3] = {cv[0], cv[1], cv[2]}, p0[3] = {p0x, p0y, p0z};
   plane_leaf(in, c, p0, x);
-  plane_block_tree(x, out + blockIdx.x, gridDim.x);
+  plane_block_tree<kPlaneSums>(x, out + blockIdx.x, gridDim.x);
 }
 
-// a further level: in[c * count + i], count = 256 gridDim.x -> out[c * gridDim.x + b]
+// a further level of a tree of kW sums: in[c * count + i], count = 256 gridDim.x -> out[c * gridDim.x + b]
+template <int kW>
 __global__ __launch_bounds__(kVoxBlock) void k_pl_tree(const double* in, int64_t count, double* out) {
   const int64_t i = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
-  double x[kPlaneSums];
+  double x[kW];
 #pragma unroll
-  for (int c = 0; c < kPlaneSums; ++c) x[c] = in[c * count + i];
-  plane_block_tree(x, out + blockIdx.x, gridDim.x);
+  for (int c = 0; c < kW; ++c) x[c] = in[c * count + i];
+  plane_block_tree<kW>(x, out + blockIdx.x, gridDim.x);
 }
 
 // k_vox_emit_batch over the voxels ids[0 .. n): point p is voxel ids[p]

@@ -5,16 +5,19 @@
 // units see only that hook.  mc_voxel_release frees it early; mc_destroy frees what is left.  The surface
 // normals of the built cloud (mc_voxel_normals; kernels in normals.hpp) and its density clustering
 // (mc_voxel_clusters; kernels in cluster.hpp) read that state and keep theirs in it; so do its plane segmentation
-// and the selection of a subset into a batch (mc_voxel_plane, mc_voxel_emit_selected; kernels in plane.hpp).
+// and the selection of a subset into a batch (mc_voxel_plane, mc_voxel_emit_selected; kernels in plane.hpp), and the
+// registration of a source against the cloud (mc_voxel_nearest_*, mc_voxel_register_*; kernels in register.hpp).
 #include "../../include/mcdeskew.h"
 #include "voxel.hpp"
 #include "normals.hpp"
 #include "cluster.hpp"
 #include "plane.hpp"
+#include "register.hpp"
 #include "internal.hpp"
 #include "hostutil.hpp"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <vector>
 
@@ -26,6 +29,7 @@ enum { kInsert = 0, kRank = 1, kAccumulate = 2, kFinalise = 3, kPhases = 4 };
 enum { kNrmCentroids = 0, kNrmWindow = 1, kNrmCap = 2, kNrmPhases = 3 };
 enum { kClDensity = 0, kClUnion = 1, kClLabel = 2, kClNumber = 3, kClStats = 4 };
 enum { kPlCompact = 0, kPlSample = 1, kPlScore = 2, kPlMask = 3, kPlMoments = 4, kPlSelect = 5, kPlanePhases = 6 };
+enum { kRgNormals = 0, kRgCorrespond = 1, kRgLeaves = 2, kRgTree = 3, kRgSolve = 4, kRegPhases = 5 };
 
 struct VoxState : mcimpl::CtxExt {
   // table (a power of two of slots), per-point arrays (points / chunks), per-voxel records
@@ -64,6 +68,14 @@ struct VoxState : mcimpl::CtxExt {
   DevBuf<int32_t> pl_samples;
   DevBuf<uint8_t> pl_mask;
   EventPairs pl_ev[kPlanePhases];
+  // the registration of a source against the cloud: the nearest voxel of every source point, the normals and
+  // their neighbour counts by voxel id, and the levels of the 28-wide tree with the pair counter behind the last;
+  // the solve is the host's, timed by its clock
+  DevBuf<int32_t> rg_ids, rg_counts;
+  DevBuf<double> rg_normals, rg_tree;
+  EventPairs rg_ev[kRegPhases];
+  double rg_solve_ms = 0.0;
+  int64_t rg_solve_n = 0;
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
@@ -71,6 +83,7 @@ struct VoxState : mcimpl::CtxExt {
     for (auto& v : nrm_ev) ev_destroy(v);
     for (auto& v : cl_ev) ev_destroy(v);
     for (auto& v : pl_ev) ev_destroy(v);
+    for (auto& v : rg_ev) ev_destroy(v);
   }
 };
 
@@ -245,34 +258,287 @@ int plane_mask(mc_ctx* c, VoxState* s, const uint8_t* d_among, const double mode
   return MC_OK;
 }
 
+// A tree of `width` sums over L leaves (a power of two >= 256): its levels lie back to back, the first of L / 256
+// partials per sum, each next of a 256th, down to the first of fewer than 256: -> the words of all of them
+size_t tree_words(int width, int64_t L) {
+  size_t words = 0;
+  for (int64_t cnt = L / kVoxBlock;; cnt /= kVoxBlock) {
+    words += (size_t)width * cnt;
+    if (cnt < kVoxBlock) break;
+  }
+  return words;
+}
+
+// the levels after the first (*cnt partials per sum at cur), queued: -> the last level, *cnt its partials per sum
+template <int kW>
+double* tree_levels(mc_ctx* c, double* cur, int64_t* cnt) {
+  while (*cnt >= kVoxBlock) {
+    double* next = cur + kW * *cnt;
+    hipLaunchKernelGGL(k_pl_tree<kW>, dim3((uint32_t)(*cnt / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, (const double*)cur, *cnt, next);
+    cur = next;
+    *cnt /= kVoxBlock;
+  }
+  return cur;
+}
+
+// fewer than 256 partials per sum are left (top[k * cnt + i], on the host): the last levels of the same tree, in place
+void tree_top(double* top, int64_t cnt, int width, double* sums) {
+  for (int k = 0; k < width; ++k) sums[k] = plane_tree(top + (size_t)k * cnt, cnt, 1);
+}
+
 // the nine tree sums of pl_mask's voxels about p0 (one synchronisation)
 int plane_moments(mc_ctx* c, VoxState* s, const double p0[3], double sums[kPlaneSums]) {
   const int64_t L = plane_leaves(s->M);
-  size_t words = 0;
-  for (int64_t cnt = L / kVoxBlock;; cnt /= kVoxBlock) {
-    words += (size_t)kPlaneSums * cnt;
-    if (cnt < kVoxBlock) break;
-  }
-  if (int r = ctx_reserve(c, s->pl_tree, words)) return r;
+  if (int r = ctx_reserve(c, s->pl_tree, tree_words(kPlaneSums, L))) return r;
   int64_t cnt = L / kVoxBlock;
   double* cur = s->pl_tree;
   {
     TimedRegion tr(c, &s->pl_ev[kPlMoments], c->stream);
     hipLaunchKernelGGL(k_pl_moments, dim3((uint32_t)cnt), dim3(kVoxBlock), 0, c->stream, (const double*)s->cent.get(),
                        (const uint8_t*)s->pl_mask.get(), s->M, p0[0], p0[1], p0[2], cur);
-    while (cnt >= kVoxBlock) {
-      double* next = cur + kPlaneSums * cnt;
-      hipLaunchKernelGGL(k_pl_tree, dim3((uint32_t)(cnt / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, (const double*)cur, cnt, next);
-      cur = next;
-      cnt /= kVoxBlock;
-    }
+    cur = tree_levels<kPlaneSums>(c, cur, &cnt);
   }
   HIPCHK(hipGetLastError());
-  // fewer than 256 partials per sum are left: the last levels of the same tree, here
   std::vector<double> top((size_t)kPlaneSums * cnt);
   HIPCHK(hipMemcpyAsync(top.data(), cur, top.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  for (int k = 0; k < kPlaneSums; ++k) sums[k] = plane_tree(top.data() + (size_t)k * cnt, cnt, 1);
+  tree_top(top.data(), cnt, kPlaneSums, sums);
+  return MC_OK;
+}
+
+// The normals of the live build (include/mcdeskew.h mc_voxel_normals) for `who`; for_register: the window and cap
+// phases are timed as the registration's normals phase, not as the normals' own
+int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoint, double* d_normals, int32_t* d_counts,
+                double* d_cov, const char* who, bool for_register) {
+  CHECK_ARG(std::isfinite(radius) && radius > 0.0, "radius must be finite and > 0 (got %g)", radius);
+  CHECK_ARG(max_nn == 0 || (max_nn >= kNormalsMinNN && max_nn <= kNormalsMaxNN),
+            "max_nn must be 0 (no cap) or in %d..%d (got %d)", kNormalsMinNN, kNormalsMaxNN, max_nn);
+  if (viewpoint)
+    for (int k = 0; k < 3; ++k)
+      CHECK_ARG(std::isfinite(viewpoint[k]), "viewpoint must be finite (axis %d: %g)", k, viewpoint[k]);
+  CHECK_ARG(((uintptr_t)d_normals & 15) == 0 && ((uintptr_t)d_cov & 15) == 0, "d_normals and d_cov must be 16-byte aligned");
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "%s needs a successful mc_voxel_build_* first", who);
+  CHECK_ARG(radius / s->h <= (double)kNormalsMaxR,
+            "radius %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius",
+            radius, radius / s->h, s->h, kNormalsMaxR);
+  const int64_t M = s->M;
+  if (M == 0) return MC_OK;
+  CHECK_ARG(d_normals, "d_normals is NULL");
+  DeviceGuard g(c->device);
+  if (int r = centroids(c, s)) return r;
+  if (int r = ctx_reserve(c, s->capped, (size_t)M)) return r;
+  if (!s->n_capped) if (int r = s->n_capped.alloc(1)) return r;
+  const dim3 blk(kVoxBlock), grid((uint32_t)((M + kVoxBlock - 1) / kVoxBlock));
+  EventPairs* window = for_register ? &s->rg_ev[kRgNormals] : &s->nrm_ev[kNrmWindow];
+  EventPairs* cap = for_register ? &s->rg_ev[kRgNormals] : &s->nrm_ev[kNrmCap];
+  NrmArgs a = {};
+  a.g.keys = s->keys; a.g.vid = s->vid; a.g.cent = s->cent;
+  a.g.shift = s->shift; a.g.mask = s->mask;
+  a.vslot = s->vslot;
+  a.M = M;
+  a.q.R = std::max(1, (int)std::ceil(radius / s->h));
+  a.q.max_nn = max_nn;
+  a.q.r2 = radius * radius;
+  a.has_viewpoint = viewpoint ? 1 : 0;
+  if (viewpoint) std::copy_n(viewpoint, 3, a.viewpoint);
+  a.normals = d_normals; a.counts = d_counts; a.cov = d_cov;
+  a.capped = s->capped; a.n_capped = s->n_capped;
+  {
+    TimedRegion tr(c, window, c->stream);
+    HIPCHK(hipMemsetAsync(s->n_capped, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_nrm_window, grid, blk, 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  // the one synchronisation: how many voxels the cap applies to (none: no third launch)
+  uint32_t n_capped = 0;
+  HIPCHK(hipMemcpyAsync(&n_capped, s->n_capped, sizeof n_capped, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((int64_t)n_capped > M) return fail(MC_ERR_STATE, "voxel normals: %u capped voxels of %lld", n_capped, (long long)M);
+  if (n_capped) {
+    {
+      TimedRegion tr(c, cap, c->stream);
+      hipLaunchKernelGGL(k_nrm_cap, dim3((n_capped + kNrmCapBlock - 1) / kNrmCapBlock), dim3(kNrmCapBlock), 0, c->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  return MC_OK;
+}
+
+// ---- the registration of a source against the cloud ------------------------------------------------------------------
+// a 4 x 4 row-major pose argument (null: the identity) -> *T
+int reg_pose(const double* m, const char* name, RegPose* T) {
+  if (!m) {
+    for (int i = 0; i < 9; ++i) T->R[i] = i % 4 == 0 ? 1.0 : 0.0;
+    T->t[0] = T->t[1] = T->t[2] = 0.0;
+    return MC_OK;
+  }
+  CHECK_ARG(m[12] == 0.0 && m[13] == 0.0 && m[14] == 0.0 && m[15] == 1.0, "%s: the last row must be 0, 0, 0, 1", name);
+  for (int r = 0; r < 3; ++r) {
+    for (int k = 0; k < 3; ++k) T->R[3 * r + k] = m[4 * r + k];
+    T->t[r] = m[4 * r + 3];
+  }
+  CHECK_ARG(register_pose_ok(*T), "%s: the entries must be finite and the rotation orthonormal (|R^T R - I| <= 1e-6)", name);
+  return MC_OK;
+}
+
+int reg_distance(const VoxState* s, double max_distance) {
+  CHECK_ARG(std::isfinite(max_distance) && max_distance > 0.0, "max_distance must be finite and > 0 (got %g)", max_distance);
+  CHECK_ARG(max_distance / s->h <= (double)kNormalsMaxR,
+            "max_distance %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius",
+            max_distance, max_distance / s->h, s->h, kNormalsMaxR);
+  return MC_OK;
+}
+
+// the points of a batch (frame < 0: all of them, as one body) or of device rows as a source
+int reg_source_batch(mc_ctx* c, const mc_batch* in, int32_t frame, RegSrc* src) {
+  CHECK_ARG(in, "the source batch is NULL");
+  CHECK_ARG(in->ctx == c, "batch belongs to another context");
+  CHECK_ARG(frame >= -1 && frame < in->F, "frame %d of a batch of %d frames", frame, in->F);
+  *src = {};
+  src->cols = in->d_cols; src->C = in->C; src->F = in->F;
+  src->poff = in->d_poff; src->doff = in->d_doff;
+  src->first = frame < 0 ? 0 : in->doff[frame];
+  src->n = frame < 0 ? in->N : in->counts[frame];
+  CHECK_ARG(src->n >= 1, "the source is empty");
+  CHECK_ARG(src->n < ((int64_t)1 << 31), "%lld points: a source takes fewer than 2^31", (long long)src->n);
+  return MC_OK;
+}
+
+int reg_source_rows(const double* d_rows, int64_t ld, int64_t n, RegSrc* src) {
+  CHECK_ARG(ld >= 3, "source rows are x, y, z: ld >= 3; got %lld", (long long)ld);
+  CHECK_ARG(n >= 1, "the source is empty");
+  CHECK_ARG(n < ((int64_t)1 << 31), "%lld points: a source takes fewer than 2^31", (long long)n);
+  CHECK_ARG(d_rows, "d_rows is NULL");
+  *src = {};
+  src->rows = d_rows; src->ld = ld; src->n = n;
+  return MC_OK;
+}
+
+// what both kernels read of the live build (its centroids written), for a window of max_distance
+int reg_args(mc_ctx* c, VoxState* s, const RegSrc& src, double max_distance, RegArgs* a) {
+  *a = {};
+  a->src = src;
+  a->M = s->M;
+  a->h = s->h;
+  std::copy_n(s->o, 3, a->o);
+  a->w.R = std::max(1, (int)std::ceil(max_distance / s->h));
+  a->w.max_nn = 0;
+  a->w.r2 = max_distance * max_distance;
+  if (s->M == 0) return MC_OK;   // no table and no centroids: every point is without a pair
+  if (int r = centroids(c, s)) return r;
+  a->g.keys = s->keys; a->g.vid = s->vid; a->g.cent = s->cent;
+  a->g.shift = s->shift; a->g.mask = s->mask;
+  return MC_OK;
+}
+
+template <bool BATCH>
+int reg_correspond(mc_ctx* c, VoxState* s, const RegArgs& a) {
+  {
+    TimedRegion tr(c, &s->rg_ev[kRgCorrespond], c->stream);
+    hipLaunchKernelGGL(k_rg_correspond<BATCH>, dim3((uint32_t)((a.src.n + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0,
+                       c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  return MC_OK;
+}
+
+template <bool BATCH>
+int nearest_run(mc_ctx* c, const RegSrc& src, double max_distance, const double* transform, int32_t* d_ids, double* d_dist2,
+                const char* who) {
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "%s needs a successful mc_voxel_build_* first", who);
+  if (int r = reg_distance(s, max_distance)) return r;
+  RegPose T;
+  if (int r = reg_pose(transform, "transform", &T)) return r;
+  CHECK_ARG(d_ids && d_dist2, "d_ids or d_dist2 is NULL");
+  DeviceGuard g(c->device);
+  RegArgs a;
+  if (int r = reg_args(c, s, src, max_distance, &a)) return r;
+  a.T = T;
+  a.ids = d_ids;
+  a.d2 = d_dist2;
+  return reg_correspond<BATCH>(c, s, a);
+}
+
+template <bool BATCH>
+int register_run(mc_ctx* c, const RegSrc& src, const mc_register_params* p, double* transformation, double* history,
+                 int64_t* stats, const char* who) {
+  VoxState* s = state_of(c, false);
+  if (!s || !s->built) return fail(MC_ERR_STATE, "%s needs a successful mc_voxel_build_* first", who);
+  if (int r = reg_distance(s, p->max_distance)) return r;
+  CHECK_ARG(p->max_iterations >= 1 && p->max_iterations <= kRegMaxIterations, "max_iterations must be in 1..%d (got %d)",
+            kRegMaxIterations, p->max_iterations);
+  CHECK_ARG(std::isfinite(p->tol_rotation) && p->tol_rotation >= 0.0 && std::isfinite(p->tol_translation) &&
+                p->tol_translation >= 0.0,
+            "tol_rotation and tol_translation must be finite and >= 0 (got %g, %g)", p->tol_rotation, p->tol_translation);
+  RegPose T;
+  if (int r = reg_pose(p->init, "init", &T)) return r;
+  const int64_t N = src.n, M = s->M;
+  stats[3] = N;
+  DeviceGuard g(c->device);
+  // the normals of the call, into the state's scratch (their own checks of the radius and of max_nn)
+  if (int r = ctx_reserve(c, s->rg_normals, 4 * (size_t)std::max<int64_t>(M, 1))) return r;
+  if (int r = ctx_reserve(c, s->rg_counts, (size_t)std::max<int64_t>(M, 1))) return r;
+  if (int r = normals_run(c, p->normals_radius, p->max_nn, nullptr, s->rg_normals, s->rg_counts, nullptr, who, true)) return r;
+  const int64_t L = plane_leaves(N);
+  const size_t words = tree_words(kRegSums, L);
+  if (int r = ctx_reserve(c, s->rg_ids, (size_t)N)) return r;
+  if (int r = ctx_reserve(c, s->rg_tree, words + 1)) return r;   // the pair counter behind the last level
+  RegArgs a;
+  if (int r = reg_args(c, s, src, p->max_distance, &a)) return r;
+  a.T = T;
+  a.ids = s->rg_ids;
+  a.normals = s->rg_normals; a.counts = s->rg_counts;
+  a.out = s->rg_tree;
+  a.pairs = reinterpret_cast<unsigned long long*>(s->rg_tree.get() + words);
+  int64_t last = L / kVoxBlock;
+  while (last >= kVoxBlock) last /= kVoxBlock;
+  std::vector<double> top((size_t)kRegSums * last + 1);
+  int status = kRegGoOn;
+  int32_t it = 0;
+  int64_t pairs = 0;
+  while (status == kRegGoOn && it < p->max_iterations) {
+    if (int r = reg_correspond<BATCH>(c, s, a)) return r;
+    int64_t cnt = L / kVoxBlock;
+    double* cur = s->rg_tree;
+    {
+      TimedRegion tr(c, &s->rg_ev[kRgLeaves], c->stream);
+      HIPCHK(hipMemsetAsync(a.pairs, 0, sizeof(unsigned long long), c->stream));
+      hipLaunchKernelGGL(k_rg_leaves<BATCH>, dim3((uint32_t)cnt), dim3(kVoxBlock), 0, c->stream, a);
+    }
+    if (cnt >= kVoxBlock) {
+      TimedRegion tr(c, &s->rg_ev[kRgTree], c->stream);
+      cur = tree_levels<kRegSums>(c, cur, &cnt);
+    }
+    HIPCHK(hipGetLastError());
+    // the iteration's one copy: the last level's partials and the pair counter behind them
+    HIPCHK(hipMemcpyAsync(top.data(), cur, top.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long long found = 0;
+    std::memcpy(&found, &top[(size_t)kRegSums * cnt], sizeof found);
+    if ((int64_t)found > N) return fail(MC_ERR_STATE, "voxel register: %llu pairs of %lld points", found, (long long)N);
+    pairs = (int64_t)found;
+    double sums[kRegSums];
+    tree_top(top.data(), cnt, kRegSums, sums);
+    status = register_step(sums, pairs, p->tol_rotation, p->tol_translation, &a.T, history + (size_t)kRegHistory * it);
+    ++it;
+    if (c->timing) {
+      s->rg_solve_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      ++s->rg_solve_n;
+    }
+  }
+  if (status == kRegGoOn) status = kRegMaxIter;
+  for (int r = 0; r < 3; ++r) {
+    for (int k = 0; k < 3; ++k) transformation[4 * r + k] = a.T.R[3 * r + k];
+    transformation[4 * r + 3] = a.T.t[r];
+  }
+  transformation[12] = transformation[13] = transformation[14] = 0.0;
+  transformation[15] = 1.0;
+  stats[0] = pairs;
+  stats[1] = it;
+  stats[2] = status;
   return MC_OK;
 }
 
@@ -380,57 +646,7 @@ int mc_timing_read_voxel(mc_ctx* c, double* ms_phase, int64_t* launches) {
 int mc_voxel_normals(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoint, double* d_normals,
                      int32_t* d_counts, double* d_cov) {
   CHECK_ARG(c, "ctx is NULL");
-  CHECK_ARG(std::isfinite(radius) && radius > 0.0, "radius must be finite and > 0 (got %g)", radius);
-  CHECK_ARG(max_nn == 0 || (max_nn >= kNormalsMinNN && max_nn <= kNormalsMaxNN),
-            "max_nn must be 0 (no cap) or in %d..%d (got %d)", kNormalsMinNN, kNormalsMaxNN, max_nn);
-  if (viewpoint)
-    for (int k = 0; k < 3; ++k)
-      CHECK_ARG(std::isfinite(viewpoint[k]), "viewpoint must be finite (axis %d: %g)", k, viewpoint[k]);
-  CHECK_ARG(((uintptr_t)d_normals & 15) == 0 && ((uintptr_t)d_cov & 15) == 0, "d_normals and d_cov must be 16-byte aligned");
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_normals needs a successful mc_voxel_build_* first");
-  CHECK_ARG(radius / s->h <= (double)kNormalsMaxR,
-            "radius %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius",
-            radius, radius / s->h, s->h, kNormalsMaxR);
-  const int64_t M = s->M;
-  if (M == 0) return MC_OK;
-  CHECK_ARG(d_normals, "d_normals is NULL");
-  DeviceGuard g(c->device);
-  if (int r = centroids(c, s)) return r;
-  if (int r = ctx_reserve(c, s->capped, (size_t)M)) return r;
-  if (!s->n_capped) if (int r = s->n_capped.alloc(1)) return r;
-  const dim3 blk(kVoxBlock), grid((uint32_t)((M + kVoxBlock - 1) / kVoxBlock));
-  NrmArgs a = {};
-  a.g.keys = s->keys; a.g.vid = s->vid; a.g.cent = s->cent;
-  a.g.shift = s->shift; a.g.mask = s->mask;
-  a.vslot = s->vslot;
-  a.M = M;
-  a.q.R = std::max(1, (int)std::ceil(radius / s->h));
-  a.q.max_nn = max_nn;
-  a.q.r2 = radius * radius;
-  a.has_viewpoint = viewpoint ? 1 : 0;
-  if (viewpoint) std::copy_n(viewpoint, 3, a.viewpoint);
-  a.normals = d_normals; a.counts = d_counts; a.cov = d_cov;
-  a.capped = s->capped; a.n_capped = s->n_capped;
-  {
-    TimedRegion tr(c, &s->nrm_ev[kNrmWindow], c->stream);
-    HIPCHK(hipMemsetAsync(s->n_capped, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_nrm_window, grid, blk, 0, c->stream, a);
-  }
-  HIPCHK(hipGetLastError());
-  // the one synchronisation: how many voxels the cap applies to (none: no third launch)
-  uint32_t n_capped = 0;
-  HIPCHK(hipMemcpyAsync(&n_capped, s->n_capped, sizeof n_capped, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  if ((int64_t)n_capped > M) return fail(MC_ERR_STATE, "voxel normals: %u capped voxels of %lld", n_capped, (long long)M);
-  if (n_capped) {
-    {
-      TimedRegion tr(c, &s->nrm_ev[kNrmCap], c->stream);
-      hipLaunchKernelGGL(k_nrm_cap, dim3((n_capped + kNrmCapBlock - 1) / kNrmCapBlock), dim3(kNrmCapBlock), 0, c->stream, a);
-    }
-    HIPCHK(hipGetLastError());
-  }
-  return MC_OK;
+  return normals_run(c, radius, max_nn, viewpoint, d_normals, d_counts, d_cov, "mc_voxel_normals", false);
 }
 
 int mc_timing_read_normals(mc_ctx* c, double* ms_phase, int64_t* launches) {
@@ -696,6 +912,66 @@ int mc_timing_read_plane(mc_ctx* c, double* ms_phase, int64_t* launches) {
   return MC_OK;
 }
 
+int mc_voxel_nearest_batch(mc_ctx* c, const mc_batch* src, int32_t frame, double max_distance, const double* transform,
+                           int32_t* d_ids, double* d_dist2) {
+  CHECK_ARG(c, "ctx is NULL");
+  RegSrc s;
+  if (int r = reg_source_batch(c, src, frame, &s)) return r;
+  return nearest_run<true>(c, s, max_distance, transform, d_ids, d_dist2, "mc_voxel_nearest_batch");
+}
+
+int mc_voxel_nearest_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n, double max_distance, const double* transform,
+                         int32_t* d_ids, double* d_dist2) {
+  CHECK_ARG(c, "ctx is NULL");
+  RegSrc s;
+  if (int r = reg_source_rows(d_rows, ld, n, &s)) return r;
+  return nearest_run<false>(c, s, max_distance, transform, d_ids, d_dist2, "mc_voxel_nearest_f64");
+}
+
+static void register_clear(double* transformation, int64_t* stats) {
+  if (transformation) std::fill_n(transformation, 16, 0.0);
+  if (stats) { stats[0] = stats[1] = stats[3] = 0; stats[2] = -1; }
+}
+
+int mc_voxel_register_batch(mc_ctx* c, const mc_batch* src, int32_t frame, const mc_register_params* p, double* transformation,
+                            double* history, int64_t* stats) {
+  register_clear(transformation, stats);
+  CHECK_ARG(c && p && transformation && history && stats, "NULL argument");
+  RegSrc s;
+  if (int r = reg_source_batch(c, src, frame, &s)) return r;
+  return register_run<true>(c, s, p, transformation, history, stats, "mc_voxel_register_batch");
+}
+
+int mc_voxel_register_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n, const mc_register_params* p,
+                          double* transformation, double* history, int64_t* stats) {
+  register_clear(transformation, stats);
+  CHECK_ARG(c && p && transformation && history && stats, "NULL argument");
+  RegSrc s;
+  if (int r = reg_source_rows(d_rows, ld, n, &s)) return r;
+  return register_run<false>(c, s, p, transformation, history, stats, "mc_voxel_register_f64");
+}
+
+int mc_timing_read_register(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  int64_t total = 0;
+  for (int k = 0; k < kRegPhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
+  if (VoxState* s = state_of(c, false)) {
+    for (int k = 0; k < kRgSolve; ++k) {
+      int64_t n = 0;
+      if (int r = sum_events(c, s->rg_ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
+      total += n;
+    }
+    if (ms_phase) ms_phase[kRgSolve] = s->rg_solve_ms;
+    total += s->rg_solve_n;
+    s->rg_solve_ms = 0.0;
+    s->rg_solve_n = 0;
+  }
+  if (launches) *launches = total;
+  return MC_OK;
+}
+
 int mc_voxel_release(mc_ctx* c) {
   if (!c) return MC_OK;
   VoxState* s = state_of(c, false);
@@ -706,6 +982,7 @@ int mc_voxel_release(mc_ctx* c) {
   for (auto& v : s->nrm_ev) ev_recycle(c, v);
   for (auto& v : s->cl_ev) ev_recycle(c, v);
   for (auto& v : s->pl_ev) ev_recycle(c, v);
+  for (auto& v : s->rg_ev) ev_recycle(c, v);
   c->ext[mcimpl::kSlotVoxel].reset();
   return MC_OK;
 }

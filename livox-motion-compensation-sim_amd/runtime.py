@@ -392,6 +392,15 @@ class Context:
         return {"compact_ms": ms[0], "sample_ms": ms[1], "score_ms": ms[2], "mask_ms": ms[3], "moments_ms": ms[4],
                 "select_ms": ms[5], "regions": n.value}
 
+    def read_timing_register(self) -> dict:
+        """Time (ms) of the phases of VoxelCloud.register and VoxelCloud.nearest since the last read
+        (mc_timing_read_register); the solve is the host's, by its clock."""
+        ms = np.zeros(5, np.float64)
+        n = c_int64()
+        check(self.lib.mc_timing_read_register(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_register")
+        return {"normals_ms": ms[0], "correspond_ms": ms[1], "leaves_ms": ms[2], "tree_ms": ms[3], "solve_ms": ms[4],
+                "regions": n.value}
+
     def device_buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)
 

@@ -8,6 +8,9 @@ of a drive are accumulated into one cloud and most points re-observe the same su
   VoxelCloud.clusters(eps, min_points=10, weighted=False)  -> VoxelClusters
   VoxelCloud.segment_plane(distance_threshold, num_iterations=1000, seed=0, refine=True, among=None)  -> VoxelPlane
   VoxelCloud.select(mask, with_pcd_len=False)  -> Batch
+  VoxelCloud.nearest(src, max_distance, transform=None, frame=None)  -> VoxelNearest
+  VoxelCloud.register(src, max_distance, init=None, max_iterations=30, normals_radius=None, max_nn=30,
+                      tol_rotation=1e-6, tol_translation=1e-6, frame=None)  -> VoxelRegistration
 
 One output point per occupied voxel: the mean of the voxel's points and of their intensities.  The
 per-voxel sums are integers (the coordinate inside its voxel in 2^-32 voxel units, the intensity in
@@ -81,6 +84,35 @@ in 0..2^64-1, refine not a bool, a mask that is not (M,) bool, fewer than three 
 Selection (``mc_voxel_emit_selected``): ``select(mask)`` is the stable compaction of the cloud by a (M,) bool mask
 into a one-frame Batch on the device, every value bit-equal to ``batch()``'s for that voxel: ``select(~plane.inliers)``
 is the non-ground cloud, ``select(labels == k)`` a segment, ``select(labels >= 0)`` the outlier filter.
+
+Registration (csrc/register_core.hpp, csrc/register.hpp; ``mc_voxel_nearest_*``, ``mc_voxel_register_*``): how well a
+scan sits on the map and the small pose correction that makes it sit better, the step after motion compensation when
+the IMU and GPS poses are noisy.  ``nearest`` is the nearest centroid of the live build for points that are not its
+voxels; ``register`` is point-to-plane ICP on it, a VoxelRegistration equal bit for bit to the NumPy restatement of
+tests/registration.py and the same on every run, the whole iteration history included.  The source is a device Batch
+(its float32 x, y, z read as float64; ``frame=f``: that frame alone; None: all frames as one rigid body) or host
+float64 rows (N, >= 3).  (R, t): the pose, source to cloud.  Every float64 line is one IEEE operation:
+
+  move      q = R p + t, each component ((R0*x + R1*y) + R2*z) + t
+  cell      the filter's k of q with the build's h and origin; a q that is not finite, or outside the key range, has
+            no nearest voxel (id -1, dist2 inf): not an error
+  nearest   W = ceil(max_distance / h); the occupied cells within W of q's cell on every axis in ascending key order;
+            u = c_j - q, d2 = (ux*ux + uy*uy) + uz*uz; inside when d2 <= max_distance^2; the smallest d2 wins, ties to
+            the lower cell key (cells whose box is farther than the smallest d2 known are left out: no output changes)
+  pair      the winner v when ``normals(normals_radius, max_nn).counts[v] >= 3``, else none (no second choice)
+  leaves    d = q - c_v;  r = (nx*dx + ny*dy) + nz*dz;  a = q x n;  J = (a, n); the upper triangle of J J^T row-major
+            (21), J r (6), r r (1); +0.0 without a pair
+  sums      each of the 28 by the refit's balanced adjacent-pair tree over the source point index
+  step      fewer than 6 pairs: "too_few_pairs".  A x = -b by Cholesky, rows in order, inner sums ascending; a pivot
+            that is not finite or not > 0: "singular".  x = (w, v).  Both return the pose before the failed step
+  update    dR = the rotation of the unit quaternion (1, w/2) / |(1, w/2)| (one sqrt);  R <- dR R;  t <- dR t + v
+  stop      "converged" when w.w <= tol_rotation^2 and v.v <= tol_translation^2 after the update, else
+            "max_iterations" after the last one
+
+Refused with ValueError: max_distance not finite and > 0 or beyond 4 h, a pose that is not a 4 x 4 of finite entries
+with last row (0, 0, 0, 1) and |R^T R - I| <= 1e-6 in every entry, an empty source, a batch of another context, a
+frame outside the batch, max_iterations not an integer in 1..2^16, a tolerance that is not finite and >= 0, and what
+``normals`` refuses of normals_radius (None: 2 h) and max_nn.
 """
 from __future__ import annotations
 
@@ -91,7 +123,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from ._lib import check, load, ptr
+from ._lib import RegisterParams, check, load, ptr
 from .runtime import Batch, Context, default_context
 
 MAX_POINTS = 2 ** 31 - 1
@@ -215,6 +247,102 @@ def _plane_args(distance_threshold, num_iterations, seed, refine, among, M):
     if not isinstance(refine, (bool, np.bool_)):
         raise ValueError(f"refine must be True or False, got {refine!r}")
     return t, int(num_iterations), int(seed), int(bool(refine)), None if among is None else _mask_arg(among, M, "among")
+
+
+class VoxelNearest(NamedTuple):
+    """What :meth:`VoxelCloud.nearest` returns, rows in the source's point order."""
+    ids: np.ndarray                 # (N,) int32 the voxel id of the nearest centroid, -1: none within max_distance
+    dist2: np.ndarray               # (N,) float64 the squared distance, inf where ids is -1
+
+
+class VoxelRegistration(NamedTuple):
+    """What :meth:`VoxelCloud.register` returns."""
+    transformation: np.ndarray      # (4, 4) float64, source to cloud
+    fitness: float                  # pairs / N of the last evaluated iteration
+    inlier_rmse: float              # sqrt(sum r^2 / pairs), the point-to-plane residual, of the same iteration
+    pairs: int
+    iterations: int                 # iterations evaluated = rows of history
+    status: str                     # "converged", "max_iterations", "too_few_pairs" or "singular"
+    history: np.ndarray             # (iterations, 8) float64: pairs, sum r^2, w (3), v (3); a failed step: zeros
+
+
+REGISTER_STATUS = ("converged", "max_iterations", "too_few_pairs", "singular")
+MAX_REGISTER_ITERATIONS = 2 ** 16
+
+
+def _distance_arg(max_distance, h):
+    try:
+        d = float(max_distance)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_distance must be a number > 0, got {max_distance!r}") from None
+    if not (math.isfinite(d) and d > 0.0):
+        raise ValueError(f"max_distance must be finite and > 0, got {max_distance!r}")
+    if h is not None and d / h > MAX_RADIUS_VOXELS:
+        raise ValueError(f"max_distance {d!r} is {d / h:.3g} voxels of {h!r} and the search window takes at most "
+                         f"{MAX_RADIUS_VOXELS}: voxelise coarser or shrink the radius")
+    return d
+
+
+def _pose_arg(pose, name):
+    """A 4 x 4 pose as contiguous float64 (None: the identity), checked before a device is touched."""
+    if pose is None:
+        return np.eye(4)
+    try:
+        T = np.ascontiguousarray(pose, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a 4 x 4 matrix, got {pose!r}") from None
+    if T.shape != (4, 4) or not np.isfinite(T).all():
+        raise ValueError(f"{name} must be a 4 x 4 matrix of finite entries, got shape {T.shape}")
+    if T[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
+        raise ValueError(f"{name}: the last row must be (0, 0, 0, 1), got {T[3].tolist()}")
+    R = T[:3, :3]
+    if not (np.abs(R.T @ R - np.eye(3)) <= 1e-6).all():
+        raise ValueError(f"{name}: the rotation must be orthonormal (|R^T R - I| <= 1e-6 in every entry)")
+    return T
+
+
+def _source_arg(ctx, src, frame):
+    """(batch, frame or -1, None) or (None, -1, rows (N, >= 3) float64), checked before a device is touched."""
+    if isinstance(src, Batch):
+        if src.ctx is not ctx:
+            raise ValueError("the batch belongs to another context")
+        f = -1
+        if frame is not None:
+            if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < src.n_frames:
+                raise ValueError(f"frame must be an integer in 0..{src.n_frames - 1}, got {frame!r}")
+            f = int(frame)
+        n = src.n_points if f < 0 else int(src.counts[f])
+        if n == 0:
+            raise ValueError("the source is empty")
+        if n > MAX_POINTS:
+            raise ValueError(f"{n} points: a source takes fewer than 2^31")
+        return src, f, None, n
+    if frame is not None:
+        raise ValueError("frame names a frame of a Batch; the source is rows")
+    a = np.asarray(src)
+    if a.ndim != 2 or a.shape[1] < 3:
+        raise ValueError(f"rows must be (N, >= 3) = x, y, z; got shape {a.shape}")
+    if a.shape[0] == 0:
+        raise ValueError("the source is empty")
+    if a.shape[0] > MAX_POINTS:
+        raise ValueError(f"{a.shape[0]} points: a source takes fewer than 2^31")
+    return None, -1, np.ascontiguousarray(a, dtype=np.float64), a.shape[0]
+
+
+def _register_args(max_iterations, tol_rotation, tol_translation):
+    if (isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer))
+            or not 1 <= max_iterations <= MAX_REGISTER_ITERATIONS):
+        raise ValueError(f"max_iterations must be an integer in 1..{MAX_REGISTER_ITERATIONS}, got {max_iterations!r}")
+    tol = []
+    for name, v in (("tol_rotation", tol_rotation), ("tol_translation", tol_translation)):
+        try:
+            t = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a number >= 0, got {v!r}") from None
+        if not (math.isfinite(t) and t >= 0.0):
+            raise ValueError(f"{name} must be finite and >= 0, got {v!r}")
+        tol.append(t)
+    return int(max_iterations), tol[0], tol[1]
 
 
 def plane_score_chunk() -> int:
@@ -377,6 +505,72 @@ class VoxelCloud:
         finally:
             buf.close()
         return out
+
+    def nearest(self, src, max_distance, transform=None, frame=None) -> "VoxelNearest":
+        """The nearest centroid of the cloud to every point of ``src`` moved by ``transform`` (4 x 4, source to
+        cloud; None: the identity), within ``max_distance`` <= 4 h (module docstring; include/mcdeskew.h
+        ``mc_voxel_nearest_*``).  ``src``: a device Batch (``frame=f``: that frame alone) or host float64 rows
+        (N, >= 3).  Rows in the source's point order; the cloud is not changed."""
+        d = _distance_arg(max_distance, self._h)
+        T = _pose_arg(transform, "transform")
+        batch, f, rows, n = _source_arg(self.ctx, src, frame)
+        self._live()
+        ctx = self.ctx
+        bufs = [ctx.device_buffer(4 * n), ctx.device_buffer(8 * n), None]
+        try:
+            if batch is not None:
+                rc = ctx.lib.mc_voxel_nearest_batch(ctx.handle, batch.handle, f, d, ptr(T, c_double), bufs[0].ptr, bufs[1].ptr)
+            else:
+                bufs[2] = ctx.device_buffer(rows.nbytes)
+                bufs[2].from_host(rows)
+                rc = ctx.lib.mc_voxel_nearest_f64(ctx.handle, bufs[2].ptr, rows.shape[1], n, d, ptr(T, c_double), bufs[0].ptr,
+                                                  bufs[1].ptr)
+            check(rc, "nearest")
+            out = VoxelNearest(bufs[0].to_host(np.int32, count=n), bufs[1].to_host(np.float64, count=n))
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.close()
+        return out
+
+    def register(self, src, max_distance, init=None, max_iterations: int = 30, normals_radius=None, max_nn: int = 30,
+                 tol_rotation: float = 1e-6, tol_translation: float = 1e-6, frame=None) -> "VoxelRegistration":
+        """Point-to-plane ICP of ``src`` against the cloud from the pose ``init`` (4 x 4, source to cloud; None: the
+        identity): per iteration the nearest centroid within ``max_distance`` <= 4 h of every moved point, the
+        cloud's normals (``normals(normals_radius, max_nn)``, computed once per call on the device;
+        ``normals_radius`` None: 2 h), the 6 x 6 normal equations summed by a tree over the point index, and a
+        Cholesky step (module docstring; include/mcdeskew.h ``mc_voxel_register_*``).  A Batch moves as one rigid
+        body (``frame=f``: that frame alone).  The cloud is not changed; any number of calls on one live cloud."""
+        d = _distance_arg(max_distance, self._h)
+        T = _pose_arg(init, "init")
+        iters, tol_r, tol_t = _register_args(max_iterations, tol_rotation, tol_translation)
+        if normals_radius is None:
+            if self._h is None:
+                raise ValueError("normals_radius=None means twice the voxel size, which this cloud does not know")
+            normals_radius = 2 * self._h
+        radius, nn, _ = _normals_args(normals_radius, max_nn, None, self._h)
+        batch, f, rows, n = _source_arg(self.ctx, src, frame)
+        self._live()
+        ctx = self.ctx
+        par = RegisterParams(d, radius, tol_r, tol_t, (c_double * 16)(*T.reshape(-1).tolist()), nn, iters)
+        out, history, stats = np.zeros((4, 4)), np.zeros((iters, 8)), np.zeros(4, np.int64)
+        tail = (ctypes.byref(par), ptr(out, c_double), ptr(history, c_double), ptr(stats, c_int64))
+        buf = None
+        try:
+            if batch is not None:
+                rc = ctx.lib.mc_voxel_register_batch(ctx.handle, batch.handle, f, *tail)
+            else:
+                buf = ctx.device_buffer(rows.nbytes)
+                buf.from_host(rows)
+                rc = ctx.lib.mc_voxel_register_f64(ctx.handle, buf.ptr, rows.shape[1], n, *tail)
+            check(rc, "register")
+        finally:
+            if buf is not None:
+                buf.close()
+        pairs, done = int(stats[0]), int(stats[1])
+        history = np.ascontiguousarray(history[:done])
+        rmse = math.sqrt(float(history[-1, 1]) / pairs) if pairs else 0.0
+        return VoxelRegistration(out, pairs / n, rmse, pairs, done, REGISTER_STATUS[int(stats[2])], history)
 
     def close(self):
         """Give the filter's device scratch back (a later call allocates it again)."""
