@@ -180,25 +180,48 @@ CASES = {
 _cache = {}
 
 
-def case(name):
-    """-> dict(rows, h, eps, runs, vox = V.downsample(rows, h), est = N.estimate(..., max_nn=0)); computed once per
-    session and shared (nobody writes into it)."""
-    if name not in _cache:
+def _built(rows, h, eps, runs, origin):
+    d = V.downsample(rows, h, origin)
+    return dict(rows=rows, h=h, origin=origin, eps=eps, runs=runs, vox=d, est=N.estimate(d["keys"], d["rows"][:, :3], h, eps, 0))
+
+
+def case(name, origin=V.ZERO):
+    """-> dict(rows, h, origin, eps, runs, vox = V.downsample(rows, h, origin), est = N.estimate(..., max_nn=0));
+    computed once per session and shared (nobody writes into it)."""
+    origin = tuple(float(v) for v in origin)
+    key = name if origin == V.ZERO else ("case", name, origin)
+    if key not in _cache:
         builder, runs = CASES[name]
         rows, h, eps = builder()
-        d = V.downsample(rows, h)
-        _cache[name] = dict(rows=rows, h=h, eps=eps, runs=runs, vox=d, est=N.estimate(d["keys"], d["rows"][:, :3], h, eps, 0))
-    return _cache[name]
+        _cache[key] = _built(rows, h, eps, runs, origin)
+    return _cache[key]
 
 
-def expect(name, min_points, weighted=False):
-    """The restatement's result for a case at (min_points, weighted), computed once."""
+GRID_RUNS = ((1, False), (4, False), (10, True))
+
+
+def grid_case(grid, float32=False):
+    """case()'s dict for N.grid_rows(grid) on the grid's h and origin (V.ORIGIN_GRIDS), eps = 2 h, runs GRID_RUNS."""
+    key = ("grid", grid, float32)
+    if key not in _cache:
+        g = V.ORIGIN_GRIDS[grid]
+        _cache[key] = _built(N.grid_rows(grid, float32), g["h"], 2 * g["h"], GRID_RUNS, g["origin"])
+    return _cache[key]
+
+
+def expect(name, min_points, weighted=False, c=None):
+    """The restatement's result for a case at (min_points, weighted), computed once; c: a grid_case's dict, with
+    `name` the key it is kept under."""
     key = (name, min_points, weighted)
     if key not in _cache:
-        c = case(name)
+        c = case(name) if c is None else c
         d = c["vox"]
         _cache[key] = dbscan(d["keys"], d["rows"][:, :3], d["counts"], c["h"], c["eps"], min_points, weighted, c["est"])
     return _cache[key]
+
+
+def grid_expect(grid, min_points, weighted, float32=False):
+    return expect(("grid", grid, float32), min_points, weighted, grid_case(grid, float32))
 
 
 def all_runs():

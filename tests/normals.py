@@ -242,13 +242,34 @@ CASES = {
 _cache = {}
 
 
-def case(name):
-    """-> dict(rows, h, radius, max_nn, vox = V.downsample(rows, h), est = estimate(...))"""
-    if name not in _cache:
+def case(name, origin=V.ZERO):
+    """-> dict(rows, h, origin, radius, max_nn, vox = V.downsample(rows, h, origin), est = estimate(...))"""
+    origin = tuple(float(v) for v in origin)
+    key = name if origin == V.ZERO else (name, origin)
+    if key not in _cache:
         builder, args, rel, max_nn = CASES[name]
         rows, h, radius = builder(*args)[:3]
         if rel is not None:
             radius = rel * h
-        d, est = of_rows(rows, h, radius, max_nn)
-        _cache[name] = dict(rows=rows, h=h, radius=radius, max_nn=max_nn, vox=d, est=est)
-    return _cache[name]
+        d, est = of_rows(rows, h, radius, max_nn, origin)
+        _cache[key] = dict(rows=rows, h=h, origin=origin, radius=radius, max_nn=max_nn, vox=d, est=est)
+    return _cache[key]
+
+
+def grid_rows(grid, float32=False):
+    """The cloud of every analysis' grid cases: slab(257, 257, h) with the h of V.ORIGIN_GRIDS[grid], where that grid
+    has its cloud; float32: the values a batch can hold.  Off the default origin two of its points may share a cell:
+    237 to 257 voxels."""
+    rows = V.on_grid(slab(257, 257, V.ORIGIN_GRIDS[grid]["h"])[0], grid)
+    return V.as_float32(rows) if float32 else rows
+
+
+def grid_case(grid, rel=2.0, max_nn=30, float32=False):
+    """case()'s dict for grid_rows(grid) on the grid's h and origin, at radius = rel h."""
+    key = ("grid", grid, rel, max_nn, float32)
+    if key not in _cache:
+        g = V.ORIGIN_GRIDS[grid]
+        rows, h, origin = grid_rows(grid, float32), g["h"], g["origin"]
+        d, est = of_rows(rows, h, rel * h, max_nn, origin)
+        _cache[key] = dict(rows=rows, h=h, origin=origin, radius=rel * h, max_nn=max_nn, vox=d, est=est)
+    return _cache[key]

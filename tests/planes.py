@@ -4,7 +4,15 @@ scores, winner, samples, masks, tree sums, the unrefined model and the refit's c
 normal by the eigenvector criterion of tests/normals.py — and the clouds the tests run it on.
 
 Every line of float64 arithmetic is one IEEE operation on arrays; the sampler is uint64 arithmetic that wraps, its
-mulhi64 goes through Python ints; the refit's normal is np.linalg.eigh's."""
+mulhi64 goes through Python ints; the refit's normal is np.linalg.eigh's.
+
+The clouds.  CASES: small clouds for the definition's decisions.  LARGE: slabs at the sizes where the code changes
+shape — 32 769 voxels, the smallest cloud whose 65 536 leaves give the refit a second tree level on the device (one
+workgroup, half the first level padding); 65 537, whose 131 072 leaves give two second-level workgroups and two
+partials for the host, and the first size at which compact()'s scan of the workgroup counts has a 257th count;
+2048 * 1024 + 1025 = 2 098 177, where the score kernel's 2 048 workgroups walk 2 050 tiles, one a full second tile and
+one a ragged tile of one voxel (K = 8: the restatement is the slow side, and its winner leads by more than a tile).
+grid_case: slab(257) on the grids of tests/voxel.py ORIGIN_GRIDS, off the default origin."""
 import math
 
 import numpy as np
@@ -192,14 +200,15 @@ def cells(rng, count, side):
     return np.stack([c // side - side // 2, c % side - side // 2], axis=1)
 
 
-def slab(M, seed=None, h=0.25):
+def slab(M, seed=None, h=0.25, extent=64.0):
     """M voxels of one point each: ceil(0.7 M) on the tilted plane z = 0.3 x - 0.2 y + 1 with a residual of at most
     0.55 t along z (less across the plane), the others 3 t to 10 t above or below it along z (at least 2.8 t across);
-    every point in a cell (ix, iy) of its own, so in a voxel of its own: -> rows, h, t = h."""
+    every point in a cell (ix, iy) of its own, so in a voxel of its own on the default grid: -> rows, h, t = h.  The
+    cloud is at most `extent` metres wide (what tests/test_planes_cpu.py's bounds on the SLABS assume is 64)."""
     rng = np.random.default_rng(M if seed is None else seed)
     t = h
     side = max(4, int(math.ceil(math.sqrt(2.0 * M))))
-    assert side * h <= 64.0
+    assert side * h <= extent
     n_in = int(math.ceil(0.7 * M))
     xy = (cells(rng, M, side) + rng.uniform(0.2, 0.8, (M, 2))) * h
     off = np.concatenate([rng.uniform(-0.55, 0.55, n_in) * t,
@@ -277,18 +286,65 @@ CASES = {
     "ground + wall": (ground_wall, (), 300, 11),
 }
 SLABS = tuple(name for name in CASES if name.startswith("slab"))
+
+# The sizes at which the kernels and their host side change shape (module docstring), on h = 2^-6 so that the slab
+# stays within its 64 metres.  Kept apart from CASES: the tests over CASES run several thresholds and hold the SLABS
+# to margins that were worked out for h = 0.25.
+TILE = 1024                         # csrc/plane.hpp kPlaneTile: voxels per workgroup and turn of the score kernel
+SCORE_GRID = 2048                   # kPlaneScoreGrid: its workgroups at the most
+TWO_TURNS = SCORE_GRID * TILE + TILE + 1          # 2 098 177: 2 050 tiles, the last of one voxel
+LARGE = {
+    "slab 32769": (slab, (32769, None, 2.0 ** -6), 64, 32769),
+    "slab 65537": (slab, (65537, None, 2.0 ** -6), 64, 65537),
+    f"slab {TWO_TURNS}": (slab, (TWO_TURNS, None, 2.0 ** -6), 8, 3),
+}
 _cache = {}
 
 
-def case(name):
-    """-> dict(rows, h, t, K, seed, vox = V.downsample(rows, h), cent (M, 3)); nobody writes into it"""
-    if name not in _cache:
-        builder, args, K, seed = CASES[name]
+def _built(rows, h, t, K, seed, origin, one_each):
+    d = V.downsample(rows, h, origin)
+    assert not one_each or len(d["keys"]) == len(rows)             # one point per voxel
+    return dict(rows=rows, h=h, origin=origin, t=t, K=K, seed=seed, vox=d, cent=np.ascontiguousarray(d["rows"][:, :3]))
+
+
+def case(name, origin=V.ZERO):
+    """-> dict(rows, h, origin, t, K, seed, vox = V.downsample(rows, h, origin), cent (M, 3)); nobody writes into it"""
+    origin = tuple(float(v) for v in origin)
+    key = name if origin == V.ZERO else ("case", name, origin)
+    if key not in _cache:
+        builder, args, K, seed = (CASES.get(name) or LARGE[name])
         rows, h, t = builder(*args)
-        d = V.downsample(rows, h)
-        assert len(d["keys"]) == len(rows), name                   # one point per voxel
-        _cache[name] = dict(rows=rows, h=h, t=t, K=K, seed=seed, vox=d, cent=np.ascontiguousarray(d["rows"][:, :3]))
-    return _cache[name]
+        _cache[key] = _built(rows, h, t, K, seed, origin, origin == V.ZERO)
+    return _cache[key]
+
+
+def among_of(M):
+    """The candidates the large cases run among: two voxels of every three."""
+    return np.arange(M) % 3 != 0
+
+
+def grid_case(grid, float32=False):
+    """case()'s dict for slab(257) built with the h of V.ORIGIN_GRIDS[grid] (as many cells wide as at h = 0.25), where
+    that grid has its cloud, on the grid's h and origin; K = 64, seed 257.  Off the default origin two points may
+    share a voxel.  float32: the values a batch can hold."""
+    key = ("grid", grid, float32)
+    if key not in _cache:
+        g = V.ORIGIN_GRIDS[grid]
+        rows, h, t = slab(257, h=g["h"], extent=256 * g["h"])
+        rows = V.on_grid(rows, grid)
+        _cache[key] = _built(V.as_float32(rows) if float32 else rows, h, t, 64, 257, g["origin"], False)
+    return _cache[key]
+
+
+def grid_expect(grid, refine, float32=False):
+    """The restatement of a grid case (shared: nobody writes into it)."""
+    k = ("grid expect", grid, bool(refine), float32)
+    if k not in _cache:
+        c = grid_case(grid, float32)
+        e = ransac(c["cent"], c["t"], c["K"], c["seed"], refine)
+        e["cent"] = c["cent"]
+        _cache[k] = e
+    return _cache[k]
 
 
 def thresholds(name):

@@ -6,7 +6,18 @@ point, the 28 tree sums, every iteration's step, the final pose and the status â
 Every line of float64 arithmetic is one IEEE operation, on arrays where it is per point and on Python floats (IEEE
 float64, math.sqrt correctly rounded) in the 6 x 6 solve and the pose update.  The cloud's normals and their
 neighbour counts are an input: the bits of VoxelCloud.normals(normals_radius, max_nn), or of the host core in the
-CPU tests (tests/normals.py holds those to its criterion)."""
+CPU tests (tests/normals.py holds those to its criterion).
+
+The cases.  CASES: all on the default origin, where the o terms of RegSkip's cell faces o + k h are zero.  grid_case:
+tests/normals.py's 257-point slab and 1281 scattered source points on the grids of tests/voxel.py ORIGIN_GRIDS â€” utm
+(the cloud and the source at a UTM-scale origin: o dominates o + k h and the skip's slack is at its largest),
+fractional (no axis of o is a multiple of h: the cell faces are not the default grid's), far keys (the cloud near zero,
+the origin far: keys near (825 000, -500 000, 250 000) and o + k h cancelling) and the same on h = 7.3 â€” at W = 1, 2
+and 4, from the identity and from NEARBY.  nearest() here walks every cell; the core leaves cells out, so these cases
+are the check that the skip changes no output.  At utm the step itself is ill-conditioned (the normal equations are
+taken about the world's origin, cond(A) about 1e26): the first step throws the source off the cloud and the second
+iteration ends with too_few_pairs; every bit of that is still the definition's.  radius_edges: on each grid 64 queries
+at the smallest max_distance that reaches their nearest centroid, and at the float64 below."""
 import math
 
 import numpy as np
@@ -278,14 +289,15 @@ def slab_source(n, seed, h=0.2):
 _cache = {}
 
 
-def corner():
-    """-> dict(rows, h, origin, vox = V.downsample(rows, h), keys, cent); nobody writes into it"""
-    if "corner" not in _cache:
+def corner(origin=V.ZERO):
+    """-> dict(rows, h, origin, vox = V.downsample(rows, h, origin), keys, cent); nobody writes into it"""
+    origin = tuple(float(v) for v in origin)
+    key = ("corner", origin)
+    if key not in _cache:
         rows = corner_rows()
-        d = V.downsample(rows, H)
-        _cache["corner"] = dict(rows=rows, h=H, origin=(0.0, 0.0, 0.0), vox=d, keys=d["keys"],
-                                cent=np.ascontiguousarray(d["rows"][:, :3]))
-    return _cache["corner"]
+        d = V.downsample(rows, H, origin)
+        _cache[key] = dict(rows=rows, h=H, origin=origin, vox=d, keys=d["keys"], cent=np.ascontiguousarray(d["rows"][:, :3]))
+    return _cache[key]
 
 
 def with_normals(cloud, normals, counts):
@@ -404,21 +416,96 @@ CASES = {
 }
 
 
-def case(name):
-    """-> the case's dict with vox = V.downsample(rows, h), keys and cent; nobody writes into it"""
-    k = ("case", name)
+def _voxelised(c, origin):
+    d = V.downsample(c["rows"], c["h"], origin)
+    c.update(vox=d, keys=d["keys"], cent=np.ascontiguousarray(d["rows"][:, :3]), origin=origin)
+    return c
+
+
+def case(name, origin=V.ZERO):
+    """-> the case's dict with vox = V.downsample(rows, h, origin), keys and cent; nobody writes into it"""
+    origin = tuple(float(v) for v in origin)
+    k = ("case", name) if origin == V.ZERO else ("case", name, origin)
     if k not in _cache:
         builder, args = CASES[name]
-        c = builder(*args)
-        d = V.downsample(c["rows"], c["h"])
-        c.update(vox=d, keys=d["keys"], cent=np.ascontiguousarray(d["rows"][:, :3]), origin=(0.0, 0.0, 0.0))
-        _cache[k] = c
+        _cache[k] = _voxelised(builder(*args), origin)
     return _cache[k]
 
 
-def expect_case(name, normals, counts):
-    """The restatement of a case on the normals a build returned (cached per case and normals)."""
-    c = case(name)
+def expect_case(name, normals, counts, c=None):
+    """The restatement of a case on the normals a build returned (cached per case and normals); c: a grid case's
+    dict, with `name` the key it is kept under."""
+    c = case(name) if c is None else c
     given = (np.ascontiguousarray(normals, np.float64)[:, :3].tobytes(), np.ascontiguousarray(counts, np.int32).tobytes())
     return expect(("expect", name, hash(given)), with_normals(c, normals, counts), c["src"], c["max_distance"], init=c["init"],
                   max_iterations=c["max_iterations"])
+
+
+# ---- the grids off the default origin (V.ORIGIN_GRIDS) ----------------------------------------------------------
+GRID_RUNS = tuple((rel, init) for rel in (0.9, 2.0, 4.0) for init in ("identity", "nearby"))       # W = 1, 2, 4
+
+
+def grid_case(grid, rel=2.0, init="identity", float32=False):
+    """N.grid_rows(grid) on the grid's h and origin, and slab_source(1281, 1281, h) where that grid has its cloud, at
+    max_distance = rel h for three iterations.  init "nearby": from the pose NEARBY; where the grid moves its cloud
+    the source is moved back by NEARBY first (a rotation of coordinates of millions of metres would carry it
+    kilometres off the cloud), so that NEARBY brings it onto the cloud again.  float32: cloud and source hold the
+    values a batch can hold."""
+    k = ("grid", grid, rel, init, float32)
+    if k not in _cache:
+        g = V.ORIGIN_GRIDS[grid]
+        src = V.on_grid(slab_source(1281, 1281, g["h"]), grid)
+        if init == "nearby" and g["moved"]:
+            src = moved_back(src, NEARBY)
+        if float32:
+            src = V.as_float32(src)
+        c = _case(N.grid_rows(grid, float32), g["h"], src, rel * g["h"], init=NEARBY if init == "nearby" else None)
+        _cache[k] = _voxelised(c, g["origin"])
+    return _cache[k]
+
+
+def grid_expect(grid, rel, init, normals, counts, float32=False):
+    return expect_case(("grid", grid, rel, init, float32), normals, counts, grid_case(grid, rel, init, float32))
+
+
+def d2_of(cent, q):
+    """|c - q|^2 of every centroid in the definition's op order: (xx + yy) + zz of u = c - q."""
+    u = cent - q
+    return (u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1]) + u[:, 2] * u[:, 2]
+
+
+def reach(d2):
+    """The smallest float64 md with md * md >= d2."""
+    d2 = np.float64(d2)
+    md = np.sqrt(d2)
+    while md * md >= d2:
+        md = np.nextafter(md, 0.0)
+    while md * md < d2:
+        md = np.nextafter(md, np.inf)
+    return float(md)
+
+
+EDGE_QUERIES = 64
+
+
+def radius_edges(grid):
+    """The radius edge on a grid's cloud: EDGE_QUERIES seeded queries, each in a random direction at 0.3 h to 3.5 h from
+    a randomly chosen centroid (so the nearest centroid is at most 3.5 h away and the window at most four cells).  For
+    each the brute-force nearest centroid's d2 in the definition's op order, `at` = the smallest float64 whose square
+    reaches it, `under` = the float64 below, and the restatement's nearest at both: -> list of dict(q (1, 3), at,
+    under, want_at = (ids, d2), want_under).  At `at` the brute-force nearest is within reach; at `under` it is not."""
+    k = ("edges", grid)
+    if k not in _cache:
+        c = grid_case(grid)
+        h, cent = c["h"], c["cent"]
+        rng = np.random.default_rng(64)
+        out = []
+        for _ in range(EDGE_QUERIES):
+            d = rng.normal(size=3)
+            q = (cent[rng.integers(len(cent))] + d / np.linalg.norm(d) * rng.uniform(0.3, 3.5) * h)[None, :]
+            at = reach(d2_of(cent, q[0]).min())
+            under = float(np.nextafter(at, 0.0))
+            out.append(dict(q=q, at=at, under=under, want_at=nearest(c["keys"], cent, h, c["origin"], q, at),
+                            want_under=nearest(c["keys"], cent, h, c["origin"], q, under)))
+        _cache[k] = out
+    return _cache[k]

@@ -19,6 +19,7 @@ from scipy.spatial import cKDTree
 import clusters as C
 import hostbuild
 import normals as N
+import voxel as V
 from conftest import pkg
 
 ROOT = hostbuild.ROOT
@@ -79,6 +80,29 @@ def test_core_equals_the_restatement_in_every_order(exes, name):
                 seen.append(raw)
                 assert C.equal(read_output(raw, M), want), (name, min_points, weighted, order)
         assert all(raw == seen[0] for raw in seen), (name, min_points, weighted)
+
+
+@needs_gxx
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_core_on_grids_off_the_default_origin(exes, grid):
+    """The core takes keys, centroids and counts: those of V.downsample(rows, h, origin) on every grid of
+    V.ORIGIN_GRIDS, at eps = 2 h, in every order."""
+    tmp, builds = exes
+    c = C.grid_case(grid)
+    M = len(c["vox"]["keys"])
+    assert 237 <= M <= 257
+    src, dst = tmp / "in.bin", tmp / "out.bin"
+    for min_points, weighted in c["runs"]:
+        want = C.grid_expect(grid, min_points, weighted)
+        assert C.canonical(want["labels"], want["core"])
+        seen = []
+        for exe in builds:
+            for order in ORDERS.values():
+                write_input(src, c, min_points, weighted, order, seed=20261020)
+                hostbuild.run(exe, src, dst)
+                seen.append(dst.read_bytes())
+                assert C.equal(read_output(seen[-1], M), want), (grid, min_points, weighted, order)
+        assert all(raw == seen[0] for raw in seen), (grid, min_points, weighted)
 
 
 # ---- (2) find / unite on eight threads under ThreadSanitizer -------------------------------------------------------

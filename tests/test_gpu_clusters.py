@@ -48,6 +48,39 @@ def test_every_cloud_equals_the_restatement_twice(gpu_ctx, name):
         assert raw(cloud.clusters(c["eps"], min_points, weighted)) == raw(got), (name, min_points, weighted)
 
 
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_grids_off_the_default_origin(gpu_ctx, grid):
+    """The 257-point slab on every grid of V.ORIGIN_GRIDS (a UTM-scale origin with the cloud there; an origin that is
+    no multiple of h; far keys whose o + k h cancels; the same on h = 7.3) at eps = 2 h: the build is the
+    restatement's and every run of C.GRID_RUNS equals it, twice.  Where float32 can hold the case, the Batch build
+    and the rows build of the same float32 values give the same bytes."""
+    m = pkg()
+    ctx = gpu_ctx
+    for float32 in ((False, True) if V.ORIGIN_GRIDS[grid]["batch"] else (False,)):
+        c = C.grid_case(grid, float32)
+        sources = [c["rows"]]
+        if float32:
+            b = ctx.batch([100, 0, len(c["rows"]) - 100])
+            b.upload_columns(*[c["rows"][:, k].astype(np.float32) for k in range(4)])
+            sources.append(b)
+        seen = []
+        for src in sources:
+            cloud = m.voxel_downsample(src, c["h"], c["origin"], context=ctx)
+            assert np.array_equal(cloud.keys(), c["vox"]["keys"]) and np.array_equal(cloud.point_counts(), c["vox"]["counts"])
+            assert np.array_equal(cloud.rows().view(np.uint64), c["vox"]["rows"].view(np.uint64))
+            for min_points, weighted in c["runs"]:
+                want = C.grid_expect(grid, min_points, weighted, float32)
+                got = cloud.clusters(c["eps"], min_points, weighted)
+                print(f"{grid}: float32 {float32} min_points {min_points} weighted {weighted}: K {got.n_clusters} "
+                      f"(restatement {want['K']}), labels differing {int((got.labels != want['labels']).sum())}")
+                assert shapes_hold(got, cloud.n_voxels)
+                assert C.equal(got, want), (grid, min_points, weighted)
+                assert raw(cloud.clusters(c["eps"], min_points, weighted)) == raw(got), (grid, min_points, weighted)
+                seen.append(raw(got))
+        assert len(sources) == 1 or seen[:3] == seen[3:]
+        assert C.grid_expect(grid, 4, False, float32)["K"] >= 2              # clusters, noise and borders to tell apart
+
+
 def by_key(cloud, got):
     """Per packed key, ascending: the key, the density, and the lowest packed key of the voxel's cluster (-1: noise)."""
     packed = V.pack(cloud.keys())

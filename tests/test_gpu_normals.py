@@ -134,6 +134,38 @@ def test_window_ends(gpu_ctx, name):
     run_case(gpu_ctx, name)
 
 
+def grid_run(ctx, c, src=None):
+    """run_case for a grid case: built on its own h and origin (src: a Batch of the same values)."""
+    m = pkg()
+    cloud = m.voxel_downsample(c["rows"] if src is None else src, c["h"], c["origin"], context=ctx)
+    assert np.array_equal(cloud.keys(), c["vox"]["keys"]) and np.array_equal(bits(cloud.rows()), bits(c["vox"]["rows"]))
+    got = cloud.normals(c["radius"], c["max_nn"], covariance=True)
+    k = N.check_against(c["est"], got.normals, got.curvature, got.counts, got.covariance, None, c["vox"]["rows"][:, :3])
+    assert same(got, cloud.normals(c["radius"], c["max_nn"], covariance=True))
+    return got, k
+
+
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_grids_off_the_default_origin(gpu_ctx, grid):
+    """The 257-point slab on every grid of V.ORIGIN_GRIDS (a UTM-scale origin with the cloud there; an origin that is
+    no multiple of h; far keys whose o + k h cancels; the same on h = 7.3), at radius 2 h and 4 h: the build is the
+    restatement's, counts and covariance equal bit for bit, the normals hold the criterion, twice.  Where float32
+    can hold the case, the Batch build and the rows build of the same float32 values give the same bytes."""
+    for rel in (2.0, 4.0):
+        c = N.grid_case(grid, rel)
+        got, k = grid_run(gpu_ctx, c)
+        assert (got.counts >= 3).sum() >= 200              # the slab is a quarter occupied: nearly every voxel has neighbours
+        print(f"{grid}: radius {rel} h: {len(got.counts)} voxels, unit {k['unit'].max():.2f}  rayleigh {k['rayleigh'].max():.3f}  "
+              f"curvature {k['curv'].max():.3f} (bounds 8, {N.C_BOUND}, {N.C_BOUND})")
+    if V.ORIGIN_GRIDS[grid]["batch"]:
+        c = N.grid_case(grid, float32=True)
+        b = gpu_ctx.batch([100, 0, len(c["rows"]) - 100])
+        b.upload_columns(*[c["rows"][:, k].astype(np.float32) for k in range(4)])
+        from_rows, _ = grid_run(gpu_ctx, c)
+        from_batch, _ = grid_run(gpu_ctx, c, b)
+        assert same(from_rows, from_batch)
+
+
 def test_a_radius_beyond_four_voxels_is_refused(gpu_ctx):
     m = pkg()
     c = N.case("257 voxels")

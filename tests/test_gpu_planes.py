@@ -147,6 +147,117 @@ def test_select(gpu_ctx):
     assert empty.select(np.zeros(0, bool)).n_points == 0
 
 
+def large_runs():
+    """(case, with among) of P.LARGE: the smallest size has no 257th workgroup count, so no candidates run."""
+    return [(name, among) for name in P.LARGE for among in (False, True) if among is False or name != "slab 32769"]
+
+
+@pytest.mark.parametrize("name,with_among", large_runs())
+def test_sizes_where_the_code_changes_shape(gpu_ctx, name, with_among):
+    """M = 32 769: the smallest cloud whose refit has a second tree level (65 536 leaves, one k_pl_tree<9> workgroup,
+    half the first level padding).  M = 65 537: 131 072 leaves, two second-level workgroups and two partials for the
+    host; and the first M with a 257th workgroup count in compact()'s scan, which the run among two voxels of every
+    three takes.  M = 2048 * 1024 + 1025: 2 050 tiles on the score kernel's 2 048 workgroups, so workgroup 0 walks a
+    full second tile and workgroup 1 a ragged one of one voxel, with and without candidates (K = 8: the restatement
+    is the slow side).  Without a refit the score (the tiled kernel's) is the mask kernel's count, which has no tile
+    loop; at the largest size the restatement's winner leads by more than a tile, so a wrong tile cannot hide
+    behind a tie.  A third tree level on the device needs more than 8 388 608 voxels: left out, the restatement of
+    such a cloud takes minutes."""
+    m = pkg()
+    c, cloud = cloud_of(m, gpu_ctx, name)
+    M = cloud.n_voxels
+    assert M == len(c["rows"]) == int(name.split()[1])
+    among = P.among_of(M) if with_among else None
+    key = "among" if with_among else None
+    # with candidates the largest size runs once, refined: compact, the tiled score and the tree in one call
+    for refine in ((True,) if with_among and M == P.TWO_TURNS else (False, True)):
+        want = P.expect(name, refine, among=among, key=key)
+        got = cloud.segment_plane(c["t"], c["K"], c["seed"], refine, among=among)
+        top = np.sort(want["scores"])[-2:]
+        print(f"{name}: among {with_among} refine {refine}: iteration {got.iteration} ({want['iteration']}), score {got.score} "
+              f"({want['score']}), inliers {got.n_inliers} ({want['n_inliers']}), masks differing "
+              f"{int((got.inliers != want['inliers']).sum())}; restatement scores {want['scores'].tolist()}")
+        if M == P.TWO_TURNS:
+            assert top[1] - top[0] > P.TILE, top
+        assert shapes_hold(got, M)
+        assert P.equal(got, want, refine), (name, with_among, refine)
+        assert got.n_inliers == int(got.inliers.sum())
+        if not refine:
+            assert got.score == got.n_inliers == int(got.inliers.sum())
+        assert raw(cloud.segment_plane(c["t"], c["K"], c["seed"], refine, among=among)) == raw(got), (name, with_among, refine)
+
+
+def test_select_past_256_workgroup_counts(gpu_ctx):
+    """65 537 voxels: compact()'s scan takes a second pass for the 257th count, and the emit kernel runs past 65 536
+    points.  Everything; every other voxel; the 257th workgroup's one voxel alone; all but one, seeded."""
+    m = pkg()
+    c, cloud = cloud_of(m, gpu_ctx, "slab 65537")
+    M = cloud.n_voxels
+    assert M == 65537
+    whole = columns(cloud.batch())
+    assert np.array_equal(whole.view(np.uint32), c["vox"]["f32"].view(np.uint32))
+    most = np.ones(M, bool)
+    most[np.random.default_rng(65537).integers(M)] = False
+    for mask in (np.ones(M, bool), np.arange(M) % 2 == 1, np.arange(M) >= 256 * 256, most):
+        got = cloud.select(mask)
+        assert got.n_points == int(mask.sum()) and got.n_frames == 1
+        assert columns(got).tobytes() == whole[mask].tobytes(), int(mask.sum())
+        assert columns(cloud.select(mask)).tobytes() == columns(got).tobytes()
+
+
+def grid_cloud(m, ctx, c, src=None):
+    """The build of a grid case on its own h and origin (src: a Batch of the same values) and its precondition: the
+    keys and the bits of the rows are the restatement's."""
+    cloud = m.voxel_downsample(c["rows"] if src is None else src, c["h"], c["origin"], context=ctx)
+    assert np.array_equal(cloud.keys(), c["vox"]["keys"])
+    assert np.array_equal(cloud.rows().view(np.uint64), c["vox"]["rows"].view(np.uint64))
+    return cloud
+
+
+def batch_of(ctx, rows):
+    """The rows as a Batch of three frames, the middle one empty."""
+    b = ctx.batch([100, 0, len(rows) - 100])
+    b.upload_columns(*[rows[:, k].astype(np.float32) for k in range(4)])
+    return b
+
+
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_grids_off_the_default_origin(gpu_ctx, grid):
+    """P.slab(257) on every grid of V.ORIGIN_GRIDS (a UTM-scale origin with the cloud there; an origin that is no
+    multiple of h; far keys whose o + k h cancels; the same on h = 7.3): the build, the plane both ways and the
+    selection of its inliers against the restatement, twice; and where float32 can hold the case, the Batch build
+    and the rows build of the same float32 values give the same bytes."""
+    m = pkg()
+    ctx = gpu_ctx
+    c = P.grid_case(grid)
+    cloud = grid_cloud(m, ctx, c)
+    whole = columns(cloud.batch())
+    assert np.array_equal(whole.view(np.uint32), c["vox"]["f32"].view(np.uint32))
+    for refine in (False, True):
+        want = P.grid_expect(grid, refine)
+        got = cloud.segment_plane(c["t"], c["K"], c["seed"], refine)
+        print(f"{grid}: refine {refine}: iteration {got.iteration} ({want['iteration']}), score {got.score} ({want['score']}), "
+              f"inliers {got.n_inliers} ({want['n_inliers']}), model {got.model.tolist()} ({want['model'].tolist()})")
+        assert shapes_hold(got, cloud.n_voxels)
+        assert P.equal(got, want, refine), (grid, refine)
+        assert raw(cloud.segment_plane(c["t"], c["K"], c["seed"], refine)) == raw(got), (grid, refine)
+        assert want["score"] >= 0.6 * cloud.n_voxels                      # the slab's plane, not a chance hit
+        sel = columns(cloud.select(got.inliers))
+        assert sel.tobytes() == whole[want["inliers"]].tobytes() == columns(cloud.select(got.inliers)).tobytes()
+    if not V.ORIGIN_GRIDS[grid]["batch"]:
+        return
+    c = P.grid_case(grid, float32=True)
+    seen = []
+    for src in (None, batch_of(ctx, c["rows"])):
+        cloud = grid_cloud(m, ctx, c, src)
+        for refine in (False, True):
+            got = cloud.segment_plane(c["t"], c["K"], c["seed"], refine)
+            assert P.equal(got, P.grid_expect(grid, refine, float32=True), refine), (grid, refine, src is None)
+            seen.append(raw(got))
+        seen.append(columns(cloud.select(got.inliers)).tobytes())
+    assert seen[:3] == seen[3:]
+
+
 def test_peel_ground_then_wall_then_clusters(gpu_ctx):
     """Segment, segment again among what is left, cluster the rest: every step against its restatement."""
     m = pkg()

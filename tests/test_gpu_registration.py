@@ -9,7 +9,10 @@ import ctypes
 import numpy as np
 import pytest
 
+import clusters as C
+import normals as N
 import registration as G
+import voxel as V
 from conftest import pkg
 
 pytestmark = pytest.mark.gpu
@@ -130,6 +133,124 @@ def test_batch_and_rows_and_one_frame(gpu_ctx):
     with pytest.raises(ValueError, match="another context"):
         cloud.nearest(other.batch([4]), c["max_distance"])
     assert ctx.lib.mc_voxel_nearest_batch(ctx.handle, other.batch([4]).handle, -1, c["max_distance"], None, None, None) == m._lib.MC_ERR_INVALID
+
+
+def grid_cloud(m, ctx, c, src=None):
+    """The build of a grid case on its own h and origin (src: a Batch of the same values) and its precondition: the
+    keys and the bits of the rows are the restatement's."""
+    cloud = m.voxel_downsample(c["rows"] if src is None else src, c["h"], c["origin"], context=ctx)
+    assert np.array_equal(cloud.keys(), c["keys"])
+    assert np.array_equal(cloud.rows().view(np.uint64), c["vox"]["rows"].view(np.uint64))
+    return cloud
+
+
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_grids_off_the_default_origin(gpu_ctx, grid):
+    """The 257-point slab and 1281 scattered source points on every grid of V.ORIGIN_GRIDS (a UTM-scale origin with
+    cloud and source there; an origin that is no multiple of h; far keys whose o + k h cancels; the same on
+    h = 7.3), at W = 1, 2 and 4, from the identity and from G.NEARBY, for three iterations.  The restatement's
+    nearest walks every cell of the window; the device leaves out what RegSkip says cannot win, from cell faces
+    o + k h: here the o terms are not zero."""
+    m = pkg()
+    cloud = None
+    for rel, init in G.GRID_RUNS:
+        c = G.grid_case(grid, rel, init)
+        cloud = grid_cloud(m, gpu_ctx, c) if cloud is None else cloud
+        nrm = cloud.normals(c["radius"], c["max_nn"])
+        want = G.grid_expect(grid, rel, init, nrm.normals, nrm.counts)
+        got, near = check(cloud, c, want, c["src"], what=f"{grid}, {rel} h, {init}")
+        assert (near.ids >= 0).sum() >= 200 and want["history"][0, 0] >= G.MIN_PAIRS          # the source is on the cloud
+
+
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_the_radius_edge_on_every_grid(gpu_ctx, grid):
+    """G.radius_edges: 64 queries whose nearest centroid is 0.3 h to 3.5 h away; max_distance the smallest float64
+    whose square reaches that centroid's d2, where the restatement and the device must both take it, and the float64
+    below, where neither may.  None is left out."""
+    m = pkg()
+    c = G.grid_case(grid)
+    cloud = grid_cloud(m, gpu_ctx, c)
+    edges = G.radius_edges(grid)
+    assert len(edges) == G.EDGE_QUERIES == 64
+    for i, e in enumerate(edges):
+        assert e["at"] / c["h"] <= 3.5 < 4
+        assert e["want_at"][0][0] >= 0, (grid, i)
+        for md, (ids, d2) in ((e["at"], e["want_at"]), (e["under"], e["want_under"])):
+            near = cloud.nearest(e["q"], md)
+            assert np.array_equal(near.ids, ids), (grid, i, md, near.ids, ids)
+            assert np.array_equal(G.bits(near.dist2), G.bits(d2)), (grid, i, md, near.dist2, d2)
+            again = cloud.nearest(e["q"], md)
+            assert again.ids.tobytes() == near.ids.tobytes() and again.dist2.tobytes() == near.dist2.tobytes()
+        assert cloud.nearest(e["q"], e["at"]).ids[0] >= 0
+
+
+@pytest.mark.parametrize("grid", [g for g in V.ORIGIN_GRIDS if V.ORIGIN_GRIDS[g]["batch"]])
+def test_batch_and_rows_on_a_grid(gpu_ctx, grid):
+    """Where float32 can hold the case: the cloud from a Batch and from float64 rows of the same float32 values, the
+    source as a Batch of frames of 400, 0 and 881 points and as rows: the restatement's result and the same bytes in
+    all four."""
+    m = pkg()
+    ctx = gpu_ctx
+    c = G.grid_case(grid, 2.0, "nearby", float32=True)
+    cb = ctx.batch([100, 0, len(c["rows"]) - 100])
+    cb.upload_columns(*[c["rows"][:, k].astype(np.float32) for k in range(4)])
+    sb = ctx.batch([400, 0, 881])
+    sb.upload_columns(*[c["src"][:, k].astype(np.float32) for k in range(3)], np.zeros(len(c["src"]), np.float32))
+    seen = []
+    for cloud_src in (None, cb):
+        cloud = grid_cloud(m, ctx, c, cloud_src)
+        nrm = cloud.normals(c["radius"], c["max_nn"])
+        want = G.grid_expect(grid, 2.0, "nearby", nrm.normals, nrm.counts, float32=True)
+        for src in (c["src"], sb):
+            got, near = check(cloud, c, want, src, what=f"{grid}: cloud {'batch' if cloud_src else 'rows'}, source "
+                                                        f"{'rows' if src is c['src'] else 'batch'}")
+            seen.append(raw(got) + near.ids.tobytes() + near.dist2.tobytes())
+    assert len(set(seen)) == 1
+
+
+def exact_rows(n, seed):
+    """N.slab's layer of h = 0.5 with every coordinate rounded to a multiple of 2^-8 (the points keep 0.05 h from
+    their cells' faces, the rounding moves them by 2^-9): one point per voxel, every centroid its point exactly."""
+    rows = N.slab(n, seed, 0.5)[0]
+    rows[:, :3] = np.rint(rows[:, :3] * 256.0) / 256.0
+    return rows
+
+
+def test_two_exact_builds_agree_across_origins(gpu_ctx):
+    """Without a restatement: h = 0.5 and coordinates that are multiples of 2^-8, once on the default grid and once
+    moved by (64, -32, 8) onto a grid of that origin.  v - o, the fixed-point fractions, o + (k + s) h, every
+    difference of two centroids and every product of two differences are exact in both, so the two builds must agree
+    on the keys, the cluster labels and densities, the normals' counts and covariances, the unrefined plane's score,
+    iteration, samples and inlier mask (its offsets s = n . c + d are exact, so s * s rounds alike), the refit's
+    covariance, and the nearest ids and the bits of d2 of sources moved alike."""
+    m = pkg()
+    ctx = gpu_ctx
+    h, shift = 0.5, np.array([64.0, -32.0, 8.0])
+    rows = exact_rows(257, 257)
+    src = np.rint(G.slab_source(1281, 1281, h) * 256.0) / 256.0
+    seen = []
+    for o in (np.zeros(3), shift):
+        moved = rows.copy()
+        moved[:, :3] += o
+        cloud = m.voxel_downsample(moved, h, tuple(o), context=ctx)
+        assert cloud.n_voxels == 257 and np.array_equal(cloud.rows()[:, :3], moved[:, :3])
+        nrm = cloud.normals(2 * h, covariance=True)
+        parts = [cloud.keys(), nrm.counts, nrm.covariance]
+        for min_points, weighted in C.GRID_RUNS:
+            cl = cloud.clusters(2 * h, min_points, weighted)
+            parts += [cl.labels, cl.density]
+        plain = cloud.segment_plane(h, 64, 257, False)
+        refit = cloud.segment_plane(h, 64, 257, True)
+        assert plain.score >= 3
+        parts += [np.int64([plain.score, plain.iteration, plain.n_inliers]), plain.samples, plain.inliers,
+                  np.int64([refit.score, refit.iteration]), refit.samples, refit.covariance]
+        for rel in (0.9, 2.0, 4.0):
+            near = cloud.nearest(src + o, rel * h)
+            assert (near.ids >= 0).sum() >= 200
+            parts += [near.ids, near.dist2]
+        seen.append([np.ascontiguousarray(a).tobytes() for a in parts])
+    differing = [i for i, (a, b) in enumerate(zip(*seen)) if a != b]
+    assert not differing, differing
 
 
 def test_state_lifetime_and_timing(gpu_ctx):

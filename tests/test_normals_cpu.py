@@ -78,6 +78,23 @@ def test_core_equals_the_restatement(exes):
 
 
 @needs_gxx
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_core_on_grids_off_the_default_origin(exes, grid):
+    """The core takes keys and centroids: those of V.downsample(rows, h, origin) on every grid of V.ORIGIN_GRIDS, at
+    radius 2 h and 4 h, held as above."""
+    tmp, builds = exes
+    for rel in (2.0, 4.0):
+        c = N.grid_case(grid, rel)
+        est, cent = c["est"], c["vox"]["rows"][:, :3]
+        assert 237 <= len(cent) <= 257 and est["R"] == int(rel)
+        for exe in builds:
+            got = run(exe, tmp, c)
+            assert len(got) == len(cent)
+            assert np.array_equal(got["kept"], kept_bits(est["kept"])), (grid, rel)
+            N.check_against(est, got["o"][:, :3], got["o"][:, 3], got["n"], got["C"], None, cent, (grid, rel))
+
+
+@needs_gxx
 def test_plane_normals_are_the_plane_s(exes):
     """The analytic normal of z = 0.3 x - 0.2 y + 100, within what the criterion and each voxel's own eigenvalue
     gap imply (tests/normals.py plane_angle_bound); most voxels have a wide gap, so the bound bites."""

@@ -3,7 +3,8 @@ stand-ins; (2) the scalar core, included by tests/host/plane_host.cpp, built wit
 ASan + UBSan, against the NumPy restatement of tests/planes.py on every cloud — score table, winner, samples, masks,
 the nine tree sums and the covariance bit for bit, the refit's normal by the eigenvector criterion, d^ recomputed from
 the returned normal; (3) the sampler; (4) what the builder clouds promise, and a least-squares fit that does not
-share the definition; (5) the module surface that needs no device."""
+share the definition; (5) the module surface that needs no device.  Under (2) also the multi-level tree at 32 769 and
+65 537 voxels and the grids off the default origin (tests/voxel.py ORIGIN_GRIDS)."""
 import math
 import os
 import re
@@ -16,6 +17,7 @@ import pytest
 import hostbuild
 import normals as N
 import planes as P
+import voxel as V
 from conftest import pkg
 
 ROOT = hostbuild.ROOT
@@ -107,6 +109,49 @@ def test_core_with_candidates_peels_the_wall(exes):
             assert np.array_equal(got["scores"], want["scores"]) and P.equal(got, want, refine)
             if refine:
                 assert np.array_equal(bits(got["sums"]), bits(want["sums"]))
+
+
+def hold(builds, tmp, c, want, refine, among=None, what=None):
+    """Both builds of the core on a case's centroids against the restatement `want`, as the tests above."""
+    seen = []
+    for exe in builds:
+        got, raw = run_host(exe, tmp, c["cent"], c["t"], c["K"], c["seed"], refine, among)
+        seen.append(raw)
+        assert np.array_equal(got["scores"], want["scores"]), what
+        assert np.array_equal(got["hyp_inliers"], want["hyp_inliers"]), what
+        assert P.equal(got, want, refine), what
+        if want["refined"]:
+            assert np.array_equal(bits(got["sums"]), bits(want["sums"])), what
+    assert seen[0] == seen[1], what
+
+
+@needs_gxx
+@pytest.mark.parametrize("name", ["slab 32769", "slab 65537"])
+def test_core_holds_the_multi_level_tree(exes, name):
+    """32 769 voxels: 65 536 leaves, half of them padding, the smallest tree the device sums in more than one level;
+    65 537: 131 072 leaves.  plane_tree against tests/planes.py's tree without a GPU: the nine sums bit for bit, with
+    and without candidates."""
+    tmp, builds = exes
+    c = P.case(name)
+    M = len(c["cent"])
+    assert M == int(name.split()[1]) and P.plane_leaves_of(M) == 2 * (M - 1)
+    for refine in (False, True):
+        hold(builds, tmp, c, P.expect(name, refine), refine, what=(name, refine))
+    among = P.among_of(M)
+    hold(builds, tmp, c, P.expect(name, True, among=among, key="among"), True, among, what=(name, "among"))
+
+
+@needs_gxx
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_core_on_grids_off_the_default_origin(exes, grid):
+    """The core takes centroids: those of V.downsample(rows, h, origin) on every grid of V.ORIGIN_GRIDS."""
+    tmp, builds = exes
+    c = P.grid_case(grid)
+    assert np.array_equal(c["cent"], V.downsample(c["rows"], c["h"], c["origin"])["rows"][:, :3]) and 237 <= len(c["cent"]) <= 257
+    if V.ORIGIN_GRIDS[grid]["moved"]:
+        assert np.abs(c["cent"] - c["origin"]).max() < 1000.0 < np.abs(c["cent"]).max()
+    for refine in (False, True):
+        hold(builds, tmp, c, P.grid_expect(grid, refine), refine, what=(grid, refine))
 
 
 # ---- (3) the sampler -----------------------------------------------------------------------------------------------

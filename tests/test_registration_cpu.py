@@ -3,7 +3,9 @@ the stand-ins; (2) the scalar core, included by tests/host/register_host.cpp, bu
 ASan + UBSan, against the NumPy restatement of tests/registration.py on every case — ids, d2, the 28 sums, every
 iteration's step, the final pose and the status bit for bit; (3) the restatement against code that does not share its
 definition: a brute-force nearest neighbour, numpy.linalg.solve, the orthonormality of the update; (4) the known
-answer; (5) what the builder clouds promise; (6) the module surface that needs no device."""
+answer; (5) what the builder clouds promise; (6) the module surface that needs no device.  Under (2) also the grids
+off the default origin (tests/voxel.py ORIGIN_GRIDS), the radius edge on each of them, and a mutant core whose skip
+forgets the origin: equal to the restatement on every case of the default origin, different on every grid."""
 import math
 import os
 import re
@@ -94,6 +96,89 @@ def test_core_equals_the_restatement_on_every_case(exes):
                 assert np.array_equal(G.bits(got["sums"][i]), G.bits(want["sums"][i])), (name, i)
         assert seen[0] == seen[1], name
         print(f"{name}: {want['status']} after {want['iterations']}, pairs {want['pairs']} of {len(c['src'])}")
+
+
+def holds(got, want):
+    """The harness's result equals the restatement's: every field, and every iteration's ids, d2 and sums bit for bit."""
+    return (G.equal(got, want) and all(np.array_equal(got["ids"][i], want["ids"][i])
+                                       and np.array_equal(G.bits(got["dist2"][i]), G.bits(want["dist2"][i]))
+                                       and np.array_equal(G.bits(got["sums"][i]), G.bits(want["sums"][i]))
+                                       for i in range(want["iterations"])))
+
+
+@needs_gxx
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_core_on_grids_off_the_default_origin(exes, grid):
+    """Every run of G.GRID_RUNS (W = 1, 2, 4; from the identity and from NEARBY) on every grid of V.ORIGIN_GRIDS: the
+    restatement's nearest walks every cell of the window, the core's leaves out what RegSkip, from cell faces
+    o + k h with o not zero, says cannot win."""
+    tmp, builds = exes
+    for rel, init in G.GRID_RUNS:
+        c = G.grid_case(grid, rel, init)
+        assert 237 <= len(c["keys"]) <= 257 and len(c["src"]) == 1281
+        seen = []
+        for exe in builds:
+            got, raw = run_host(exe, tmp, c)
+            seen.append(raw)
+            want = G.grid_expect(grid, rel, init, got["normals"], got["counts"])
+            assert holds(got, want), (grid, rel, init, got["status"], want["status"], got["history"], want["history"])
+        assert seen[0] == seen[1], (grid, rel, init)
+        found = int((want["ids"][0] >= 0).sum())
+        print(f"{grid}, {rel} h, {init}: {want['status']} after {want['iterations']}, pairs {want['pairs']}, found {found} of 1281")
+        assert found >= 200 and want["history"][0, 0] >= G.MIN_PAIRS          # the source is on the cloud
+
+
+@needs_gxx
+@pytest.mark.parametrize("grid", list(V.ORIGIN_GRIDS))
+def test_the_radius_edge_on_every_grid(exes, grid):
+    """G.radius_edges through the core, one run per query and max_distance: at the smallest float64 whose square
+    reaches the brute-force nearest centroid's d2 that centroid is taken, by the restatement and by the core; at the
+    float64 below neither takes it.  None of the 64 is left out."""
+    tmp, builds = exes
+    c = dict(G.grid_case(grid), max_iterations=1)
+    edges = G.radius_edges(grid)
+    assert len(edges) == G.EDGE_QUERIES == 64
+    for i, e in enumerate(edges):
+        assert e["at"] / c["h"] <= 3.5 < 4
+        brute = int(np.argmin(G.d2_of(c["cent"], e["q"][0])))
+        assert e["want_at"][0][0] == brute and e["want_under"][0][0] != brute, (grid, i)
+        assert G.bits(e["want_at"][1])[0] == G.bits(G.d2_of(c["cent"], e["q"][0])[brute])
+        for md, (ids, d2) in ((e["at"], e["want_at"]), (e["under"], e["want_under"])):
+            for exe in builds:
+                got, _ = run_host(exe, tmp, dict(c, src=e["q"], max_distance=md))
+                assert np.array_equal(got["ids"][0], ids), (grid, i, md, got["ids"][0], ids)
+                assert np.array_equal(G.bits(got["dist2"][0]), G.bits(d2)), (grid, i, md)
+
+
+SKIP_FACES = ("const double lo = o[a] + (double)k * h;", "const double hi = o[a] + (double)(k + 1) * h;")
+
+
+@needs_gxx
+def test_a_skip_that_forgets_the_origin_shows_only_off_the_default_origin(tmp_path):
+    """The mutant: RegSkip's cell faces computed without o[a].  It equals the restatement on every case of G.CASES,
+    which all have the origin (0, 0, 0) — the blind spot the grid cases close — and differs from it on each grid of
+    V.ORIGIN_GRIDS, so the grid cases cannot be simplified to ones that would miss it."""
+    core = hostbuild.preprocessed("register_host.cpp", "-ffp-contract=off")
+    for old in SKIP_FACES:
+        assert core.count(old) == 1, old
+        core = core.replace(old, old.replace("o[a] + ", ""))
+    ii = tmp_path / "skip_without_origin.ii"
+    ii.write_text(core)
+    mutant = hostbuild.build(tmp_path, ii, "-ffp-contract=off")
+    for name in G.CASES:
+        c = G.case(name)
+        assert c["origin"] == V.ZERO
+        got, _ = run_host(mutant, tmp_path, c)
+        assert holds(got, G.expect_case(name, got["normals"], got["counts"])), name
+    for grid in V.ORIGIN_GRIDS:
+        differing = 0
+        for rel, init in G.GRID_RUNS:
+            c = G.grid_case(grid, rel, init)
+            got, _ = run_host(mutant, tmp_path, c)
+            want = G.grid_expect(grid, rel, init, got["normals"], got["counts"])
+            differing += int((got["ids"][0] != want["ids"][0]).sum())
+            assert not holds(got, want), (grid, rel, init)
+        print(f"{grid}: the mutant's nearest differs from the restatement's in {differing} of {6 * 1281} ids")
 
 
 @needs_gxx

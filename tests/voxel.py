@@ -98,6 +98,38 @@ GRIDS = ((0.5, (0.0, 0.0, 0.0)),                       # h exact in binary
          (0.1, (5.0e6, 4.4e5, 100.0)))                 # a UTM-scale origin
 
 
+# ---- the grids off the default origin that every analysis of the voxel cloud runs on (tests/normals.py,
+# clusters.py, planes.py and registration.py build their grid cases on these; the test files of the four analyses
+# are parametrized over the names) ----------------------------------------------------------------------------
+ZERO = (0.0, 0.0, 0.0)
+# name: h, origin, moved (the cloud and the sources are moved by the origin), batch (float32 can hold the case)
+ORIGIN_GRIDS = {
+    # GRIDS' own UTM-scale origin, the cloud there: o + k h is dominated by o; float32 cannot resolve h
+    "utm": dict(h=0.2, origin=GRIDS[2][1], moved=True, batch=False),
+    # an origin that is no multiple of h on any axis: a cell's faces are not where the default grid has them
+    "fractional": dict(h=0.2, origin=(0.1, -0.37, 12.3456), moved=False, batch=True),
+    # the cloud stays near zero and the origin is far: keys near (825 000, -500 000, 250 000), in range, and
+    # o + k h cancels down to the cloud's small coordinates
+    "far keys": dict(h=0.4, origin=(-3.3e5 + 0.1, 2.0e5 + 0.07, -1.0e5 - 0.03), moved=False, batch=True),
+    # the same with a voxel size that is far from a power of two
+    "far keys, coarse": dict(h=7.3, origin=(5.0e6, -4.4e6, 3.0e6), moved=False, batch=False),
+}
+
+
+def on_grid(points, grid):
+    """points (n, >= 3) where the grid has its cloud: moved by the origin for a moved grid, else as they are."""
+    g = ORIGIN_GRIDS[grid]
+    out = np.array(points, np.float64)
+    if g["moved"]:
+        out[:, :3] = out[:, :3] + np.asarray(g["origin"], np.float64)
+    return out
+
+
+def as_float32(rows):
+    """The rows a batch can hold: every value rounded to float32, as float64."""
+    return np.asarray(rows, np.float64).astype(np.float32).astype(np.float64)
+
+
 def edge_rows(h, origin, dtype=np.float64):
     """-> (accepted rows, refused rows) of the grid's boundary and range values; ``dtype`` float32: the
     values a batch can hold (1 ulp is then a float32 ulp)."""
