@@ -171,6 +171,22 @@ static inline int read_timing(mc_ctx* c, EventPairs& v, double* ms, int64_t* n) 
   return sum_events(c, v, ms, n);
 }
 
+// a mc_timing_read_* of `count` lists, one per phase (ev null: the feature has no state yet): ms_phase[k]
+// = the ms of ev[k] since the last read, zero without a state; *launches = their regions together
+static inline int read_timing_phases(mc_ctx* c, EventPairs* ev, int count, double* ms_phase, int64_t* launches) {
+  DeviceGuard g(c->device);
+  if (int r = sync_all(c)) return r;
+  int64_t total = 0;
+  for (int k = 0; k < count; ++k) if (ms_phase) ms_phase[k] = 0.0;
+  for (int k = 0; ev && k < count; ++k) {
+    int64_t n = 0;
+    if (int r = sum_events(c, ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
+    total += n;
+  }
+  if (launches) *launches = total;
+  return MC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // a feature's state in its slot of the context (internal.hpp CtxExt)
 // ------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // internal.hpp — the opaque handles of include/mcdeskew.h, shared by every translation unit of the
-// library: mcdeskew.hip (the context, the batches, the deskew paths and, for now, the host side of the
-// two scanners), comm.cpp, codecs.hip and voxel.hip.  What only one feature reads — the scanners', the
-// codecs' and the voxel filter's state — is not here: it sits in that feature's slot of the context.
+// library: mcdeskew.hip (the context, the batches, the deskew paths and the host side of the two
+// scanners), comm.cpp, codecs.hip and voxel.hip.  What only one feature reads — the scanners' and the
+// codecs' state, and in the voxel slot the filter's with that of the analyses of its cloud (normals,
+// clusters, planes and selection, registration) — is not here: it sits in that feature's slot of the context.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <hip/hip_vector_types.h>

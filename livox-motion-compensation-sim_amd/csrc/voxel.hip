@@ -25,11 +25,22 @@ using namespace mc;
 
 namespace {
 
-enum { kInsert = 0, kRank = 1, kAccumulate = 2, kFinalise = 3, kPhases = 4 };
-enum { kNrmCentroids = 0, kNrmWindow = 1, kNrmCap = 2, kNrmPhases = 3 };
-enum { kClDensity = 0, kClUnion = 1, kClLabel = 2, kClNumber = 3, kClStats = 4 };
-enum { kPlCompact = 0, kPlSample = 1, kPlScore = 2, kPlMask = 3, kPlMoments = 4, kPlSelect = 5, kPlanePhases = 6 };
-enum { kRgNormals = 0, kRgCorrespond = 1, kRgLeaves = 2, kRgTree = 3, kRgSolve = 4, kRegPhases = 5 };
+// Every timed phase of the unit, one line per stage.  A stage's mc_timing_read_* reads its line: {first, count}, the
+// public phase index being the offset from `first`.  A new stage adds its line here and its range below, and nothing
+// else: the state's one array of pairs is recycled, destroyed and read by these alone.
+enum {
+  kInsert, kRank, kAccumulate, kFinalise,
+  kNrmCentroids, kNrmWindow, kNrmCap,
+  kClDensity, kClUnion, kClLabel, kClNumber, kClStats,
+  kPlCompact, kPlSample, kPlScore, kPlMask, kPlMoments, kPlSelect,
+  kRgNormals, kRgCorrespond, kRgLeaves, kRgTree,   // the register's fifth phase, the solve, is the host's: no events
+  kAllPhases
+};
+struct PhaseRange { int first, count; };
+constexpr PhaseRange kFilterPhases = {kInsert, 4}, kNormalsPhases = {kNrmCentroids, 3}, kClPhases = {kClDensity, kClusterPhases},
+                     kPlanePhases = {kPlCompact, 6}, kRegPhases = {kRgNormals, 4};
+constexpr int kRgSolve = 4;   // its public index
+static_assert(kRegPhases.first + kRegPhases.count == kAllPhases && kClPhases.first + kClPhases.count == kPlCompact, "the ranges");
 
 struct VoxState : mcimpl::CtxExt {
   // table (a power of two of slots), per-point arrays (points / chunks), per-voxel records
@@ -47,48 +58,124 @@ struct VoxState : mcimpl::CtxExt {
   double h = 0.0, o[3] = {0, 0, 0};
   int shift = 0;
   uint32_t mask = 0;
-  EventPairs ev[kPhases];
+  EventPairs ev[kAllPhases];   // by phase, of every stage
   // the normals of the last build: its centroids by voxel (written by the first mc_voxel_normals after the
   // build), the voxels the cap applies to and their number
   DevBuf<double> cent;
   bool cent_current = false;
   DevBuf<uint32_t> capped;
   DevBuf<uint32_t> n_capped;
-  EventPairs nrm_ev[kNrmPhases];
   // the last clustering of the last build: the union-find word and the label of every voxel (the cluster's
   // number, kClusterNone for noise), the roots per workgroup, and K
   DevBuf<uint32_t> cl_parent, cl_label, cl_chunk, cl_meta;
   bool cl_current = false;
   int64_t cl_K = 0;
-  EventPairs cl_ev[kClusterPhases];
   // the plane segmentation and the selection: the ascending voxel ids of a mask and their scan, the hypothesis
   // table, the scores, the inlier byte of every voxel under the last model, and the levels of the refit's tree
   DevBuf<uint32_t> pl_ids, pl_chunk, pl_meta, pl_score, pl_count;
   DevBuf<double> pl_hyp, pl_tree;
   DevBuf<int32_t> pl_samples;
   DevBuf<uint8_t> pl_mask;
-  EventPairs pl_ev[kPlanePhases];
   // the registration of a source against the cloud: the nearest voxel of every source point, the normals and
   // their neighbour counts by voxel id, and the levels of the 28-wide tree with the pair counter behind the last;
   // the solve is the host's, timed by its clock
   DevBuf<int32_t> rg_ids, rg_counts;
   DevBuf<double> rg_normals, rg_tree;
-  EventPairs rg_ev[kRegPhases];
   double rg_solve_ms = 0.0;
   int64_t rg_solve_n = 0;
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
     for (auto& v : ev) ev_destroy(v);
-    for (auto& v : nrm_ev) ev_destroy(v);
-    for (auto& v : cl_ev) ev_destroy(v);
-    for (auto& v : pl_ev) ev_destroy(v);
-    for (auto& v : rg_ev) ev_destroy(v);
   }
 };
 
 // the context's state (made on demand)
 VoxState* state_of(mc_ctx* c, bool create) { return ctx_ext<VoxState>(c, mcimpl::kSlotVoxel, create); }
+
+// the state of the live build, for the entry point `who`
+int live_build(mc_ctx* c, const char* who, VoxState** s) {
+  *s = state_of(c, false);
+  if (!*s || !(*s)->built) return fail(MC_ERR_STATE, "%s needs a successful mc_voxel_build_* first", who);
+  return MC_OK;
+}
+
+// a stage's mc_timing_read_*
+int read_phases(mc_ctx* c, PhaseRange p, double* ms_phase, int64_t* launches) {
+  VoxState* s = state_of(c, false);
+  return read_timing_phases(c, s ? s->ev + p.first : nullptr, p.count, ms_phase, launches);
+}
+
+// ---- views of the state: what the kernels' argument structs take of it ------------------------------------------------
+// the per-voxel sums and the grid, the outputs left null
+VoxOut out_of(const VoxState* s) {
+  VoxOut a = {};
+  a.keys = s->keys; a.vslot = s->vslot; a.sums = s->sums; a.cnt = s->cnt;
+  a.M = s->M;
+  a.h = s->h;
+  std::copy_n(s->o, 3, a.o);
+  return a;
+}
+
+// the key table and the centroids (written by centroids())
+NormalsGrid grid_of(const VoxState* s) {
+  NormalsGrid g = {};
+  g.keys = s->keys; g.vid = s->vid; g.cent = s->cent;
+  g.shift = s->shift; g.mask = s->mask;
+  return g;
+}
+
+// the cells a search of `radius` looks at on every axis, each way
+int window_cells(const VoxState* s, double radius) { return std::max(1, (int)std::ceil(radius / s->h)); }
+
+NormalsQuery query_of(const VoxState* s, double radius, int32_t max_nn) {
+  NormalsQuery q = {};
+  q.R = window_cells(s, radius);
+  q.max_nn = max_nn;
+  q.r2 = radius * radius;
+  return q;
+}
+
+// a search radius (`name`: radius, eps, max_distance) against the widest window the kernels walk
+int check_window(const VoxState* s, double v, const char* name) {
+  CHECK_ARG(v / s->h <= (double)kNormalsMaxR,
+            "%s %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius", name, v,
+            v / s->h, s->h, kNormalsMaxR);
+  return MC_OK;
+}
+
+// ---- small things ------------------------------------------------------------------------------------------------------
+uint32_t blocks_of(int64_t n) { return (uint32_t)((n + kVoxBlock - 1) / kVoxBlock); }
+
+// these bytes back to the host, and wait: a call's synchronisation
+int copy_back(mc_ctx* c, void* host, const void* dev, size_t bytes) {
+  HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return MC_OK;
+}
+
+// The scan of n per-workgroup counts, queued inside the caller's timed region between the kernels that count and
+// those that rank: chunk -> its exclusive scan in place, meta[1] the total.  The caller brings meta back with its one
+// synchronisation (copy_back) and bounds the total in its own words
+void scan_counts(mc_ctx* c, uint32_t* chunk, int64_t n, uint32_t* meta) {
+  hipLaunchKernelGGL(k_vox_scan, dim3(1), dim3(kVoxBlock), 0, c->stream, chunk, n, meta);
+}
+
+// RegPose <-> a row-major 4 x 4 (the last row is the caller's to check or to write)
+void pose_from_rows(const double* m, RegPose* T) {
+  for (int r = 0; r < 3; ++r) {
+    std::copy_n(m + 4 * r, 3, T->R + 3 * r);
+    T->t[r] = m[4 * r + 3];
+  }
+}
+void pose_to_rows(const RegPose& T, double* m) {
+  for (int r = 0; r < 3; ++r) {
+    std::copy_n(T.R + 3 * r, 3, m + 4 * r);
+    m[4 * r + 3] = T.t[r];
+  }
+  m[12] = m[13] = m[14] = 0.0;
+  m[15] = 1.0;
+}
 
 int check_grid(double voxel, const double* origin) {
   CHECK_ARG(std::isfinite(voxel) && voxel > 0.0, "voxel must be finite and > 0 (got %g)", voxel);
@@ -129,7 +216,7 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   t.meta = s->meta;
   s->shift = t.shift;
   s->mask = t.mask;
-  const dim3 blk(kVoxBlock), pgrid((uint32_t)((lanes + kVoxBlock - 1) / kVoxBlock)), cgrid((uint32_t)n_chunks);
+  const dim3 blk(kVoxBlock), pgrid(blocks_of(lanes)), cgrid((uint32_t)n_chunks);
   {
     TimedRegion tr(c, &s->ev[kInsert], c->stream);
     HIPCHK(hipMemsetAsync(s->keys, 0xFF, cap * sizeof(unsigned long long), c->stream));
@@ -140,14 +227,13 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   {
     TimedRegion tr(c, &s->ev[kRank], c->stream);
     hipLaunchKernelGGL(k_vox_flag, cgrid, blk, 0, c->stream, t, n, s->flags, s->chunk);
-    hipLaunchKernelGGL(k_vox_scan, dim3(1), blk, 0, c->stream, s->chunk, n_chunks, s->meta);
+    scan_counts(c, s->chunk, n_chunks, s->meta);
     hipLaunchKernelGGL(k_vox_rank, cgrid, blk, 0, c->stream, t, n, (const uint8_t*)s->flags, (const uint32_t*)s->chunk,
                        s->vslot);
   }
   HIPCHK(hipGetLastError());
   uint32_t meta[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(meta, s->meta, sizeof meta, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int r = copy_back(c, meta, s->meta, sizeof meta)) return r;
   if (meta[0] != kVoxNone) {
     *bad = (int64_t)meta[0];
     return MC_ERR_INVALID;   // the caller words the message (frame / index or row)
@@ -174,14 +260,11 @@ const char* kRefused =
     "a coordinate or (v - origin) / voxel is not finite, a voxel index is outside [-2^20, 2^20), or the intensity is "
     "not finite or beyond +-65536";
 
-int emit(mc_ctx* c, VoxState* s, VoxOut a, bool batch, int64_t P) {
-  a.keys = s->keys; a.vslot = s->vslot; a.sums = s->sums; a.cnt = s->cnt;
-  a.M = s->M;
-  a.h = s->h;
-  std::copy_n(s->o, 3, a.o);
+// a: out_of(s) with its outputs set
+int emit(mc_ctx* c, VoxState* s, const VoxOut& a, bool batch, int64_t P) {
   const int64_t lanes = batch ? P / 4 : s->M;
   if (lanes == 0) return MC_OK;
-  const dim3 blk(kVoxBlock), grid((uint32_t)((lanes + kVoxBlock - 1) / kVoxBlock));
+  const dim3 blk(kVoxBlock), grid(blocks_of(lanes));
   {
     TimedRegion tr(c, &s->ev[kFinalise], c->stream);
     if (batch) hipLaunchKernelGGL(k_vox_emit_batch, grid, blk, 0, c->stream, a, P);
@@ -197,15 +280,9 @@ int centroids(mc_ctx* c, VoxState* s) {
   const int64_t M = s->M;
   if (int r = ctx_reserve(c, s->cent, kNormalsCent * (size_t)M)) return r;
   if (s->cent_current) return MC_OK;
-  VoxOut o = {};
-  o.keys = s->keys; o.vslot = s->vslot; o.sums = s->sums; o.cnt = s->cnt;
-  o.M = M;
-  o.h = s->h;
-  std::copy_n(s->o, 3, o.o);
   {
-    TimedRegion tr(c, &s->nrm_ev[kNrmCentroids], c->stream);
-    hipLaunchKernelGGL(k_nrm_centroids, dim3((uint32_t)((M + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, o,
-                       s->cent.get());
+    TimedRegion tr(c, &s->ev[kNrmCentroids], c->stream);
+    hipLaunchKernelGGL(k_nrm_centroids, dim3(blocks_of(M)), dim3(kVoxBlock), 0, c->stream, out_of(s), s->cent.get());
   }
   HIPCHK(hipGetLastError());
   s->cent_current = true;
@@ -215,21 +292,20 @@ int centroids(mc_ctx* c, VoxState* s) {
 // the ascending voxel ids of the set bytes of d_mask (M > 0) into pl_ids, and their number (one synchronisation)
 int compact(mc_ctx* c, VoxState* s, const uint8_t* d_mask, int phase, int64_t* n) {
   const int64_t M = s->M;
-  const uint32_t blocks = (uint32_t)((M + kVoxBlock - 1) / kVoxBlock);
+  const uint32_t blocks = blocks_of(M);
   if (int r = ctx_reserve(c, s->pl_ids, (size_t)M)) return r;
   if (int r = ctx_reserve(c, s->pl_chunk, (size_t)blocks)) return r;
   if (!s->pl_meta) if (int r = s->pl_meta.alloc(2)) return r;
   {
-    TimedRegion tr(c, &s->pl_ev[phase], c->stream);
+    TimedRegion tr(c, &s->ev[phase], c->stream);
     hipLaunchKernelGGL(k_pl_flag, dim3(blocks), dim3(kVoxBlock), 0, c->stream, d_mask, M, s->pl_chunk.get());
-    hipLaunchKernelGGL(k_vox_scan, dim3(1), dim3(kVoxBlock), 0, c->stream, s->pl_chunk.get(), (int64_t)blocks, s->pl_meta.get());
+    scan_counts(c, s->pl_chunk, blocks, s->pl_meta);
     hipLaunchKernelGGL(k_pl_scatter, dim3(blocks), dim3(kVoxBlock), 0, c->stream, d_mask, M, (const uint32_t*)s->pl_chunk.get(),
                        s->pl_ids.get());
   }
   HIPCHK(hipGetLastError());
   uint32_t meta[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(meta, s->pl_meta, sizeof meta, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int r = copy_back(c, meta, s->pl_meta, sizeof meta)) return r;
   if ((int64_t)meta[1] > M) return fail(MC_ERR_STATE, "voxel mask: %u set bytes of %lld voxels", meta[1], (long long)M);
   *n = (int64_t)meta[1];
   return MC_OK;
@@ -246,14 +322,13 @@ int plane_mask(mc_ctx* c, VoxState* s, const uint8_t* d_among, const double mode
   a.refined = refined ? 1 : 0;
   a.mask = s->pl_mask; a.count = s->pl_count;
   {
-    TimedRegion tr(c, &s->pl_ev[kPlMask], c->stream);
+    TimedRegion tr(c, &s->ev[kPlMask], c->stream);
     HIPCHK(hipMemsetAsync(s->pl_count, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_pl_mask, dim3((uint32_t)((s->M + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, a);
+    hipLaunchKernelGGL(k_pl_mask, dim3(blocks_of(s->M)), dim3(kVoxBlock), 0, c->stream, a);
   }
   HIPCHK(hipGetLastError());
   uint32_t count = 0;
-  HIPCHK(hipMemcpyAsync(&count, s->pl_count, sizeof count, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int r = copy_back(c, &count, s->pl_count, sizeof count)) return r;
   *n_inliers = (int64_t)count;
   return MC_OK;
 }
@@ -293,15 +368,14 @@ int plane_moments(mc_ctx* c, VoxState* s, const double p0[3], double sums[kPlane
   int64_t cnt = L / kVoxBlock;
   double* cur = s->pl_tree;
   {
-    TimedRegion tr(c, &s->pl_ev[kPlMoments], c->stream);
+    TimedRegion tr(c, &s->ev[kPlMoments], c->stream);
     hipLaunchKernelGGL(k_pl_moments, dim3((uint32_t)cnt), dim3(kVoxBlock), 0, c->stream, (const double*)s->cent.get(),
                        (const uint8_t*)s->pl_mask.get(), s->M, p0[0], p0[1], p0[2], cur);
     cur = tree_levels<kPlaneSums>(c, cur, &cnt);
   }
   HIPCHK(hipGetLastError());
   std::vector<double> top((size_t)kPlaneSums * cnt);
-  HIPCHK(hipMemcpyAsync(top.data(), cur, top.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int r = copy_back(c, top.data(), cur, top.size() * sizeof(double))) return r;
   tree_top(top.data(), cnt, kPlaneSums, sums);
   return MC_OK;
 }
@@ -317,11 +391,9 @@ int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoin
     for (int k = 0; k < 3; ++k)
       CHECK_ARG(std::isfinite(viewpoint[k]), "viewpoint must be finite (axis %d: %g)", k, viewpoint[k]);
   CHECK_ARG(((uintptr_t)d_normals & 15) == 0 && ((uintptr_t)d_cov & 15) == 0, "d_normals and d_cov must be 16-byte aligned");
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "%s needs a successful mc_voxel_build_* first", who);
-  CHECK_ARG(radius / s->h <= (double)kNormalsMaxR,
-            "radius %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius",
-            radius, radius / s->h, s->h, kNormalsMaxR);
+  VoxState* s;
+  if (int r = live_build(c, who, &s)) return r;
+  if (int r = check_window(s, radius, "radius")) return r;
   const int64_t M = s->M;
   if (M == 0) return MC_OK;
   CHECK_ARG(d_normals, "d_normals is NULL");
@@ -329,17 +401,13 @@ int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoin
   if (int r = centroids(c, s)) return r;
   if (int r = ctx_reserve(c, s->capped, (size_t)M)) return r;
   if (!s->n_capped) if (int r = s->n_capped.alloc(1)) return r;
-  const dim3 blk(kVoxBlock), grid((uint32_t)((M + kVoxBlock - 1) / kVoxBlock));
-  EventPairs* window = for_register ? &s->rg_ev[kRgNormals] : &s->nrm_ev[kNrmWindow];
-  EventPairs* cap = for_register ? &s->rg_ev[kRgNormals] : &s->nrm_ev[kNrmCap];
+  EventPairs* window = &s->ev[for_register ? kRgNormals : kNrmWindow];
+  EventPairs* cap = &s->ev[for_register ? kRgNormals : kNrmCap];
   NrmArgs a = {};
-  a.g.keys = s->keys; a.g.vid = s->vid; a.g.cent = s->cent;
-  a.g.shift = s->shift; a.g.mask = s->mask;
+  a.g = grid_of(s);
   a.vslot = s->vslot;
   a.M = M;
-  a.q.R = std::max(1, (int)std::ceil(radius / s->h));
-  a.q.max_nn = max_nn;
-  a.q.r2 = radius * radius;
+  a.q = query_of(s, radius, max_nn);
   a.has_viewpoint = viewpoint ? 1 : 0;
   if (viewpoint) std::copy_n(viewpoint, 3, a.viewpoint);
   a.normals = d_normals; a.counts = d_counts; a.cov = d_cov;
@@ -347,13 +415,12 @@ int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoin
   {
     TimedRegion tr(c, window, c->stream);
     HIPCHK(hipMemsetAsync(s->n_capped, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_nrm_window, grid, blk, 0, c->stream, a);
+    hipLaunchKernelGGL(k_nrm_window, dim3(blocks_of(M)), dim3(kVoxBlock), 0, c->stream, a);
   }
   HIPCHK(hipGetLastError());
   // the one synchronisation: how many voxels the cap applies to (none: no third launch)
   uint32_t n_capped = 0;
-  HIPCHK(hipMemcpyAsync(&n_capped, s->n_capped, sizeof n_capped, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int r = copy_back(c, &n_capped, s->n_capped, sizeof n_capped)) return r;
   if ((int64_t)n_capped > M) return fail(MC_ERR_STATE, "voxel normals: %u capped voxels of %lld", n_capped, (long long)M);
   if (n_capped) {
     {
@@ -374,20 +441,14 @@ int reg_pose(const double* m, const char* name, RegPose* T) {
     return MC_OK;
   }
   CHECK_ARG(m[12] == 0.0 && m[13] == 0.0 && m[14] == 0.0 && m[15] == 1.0, "%s: the last row must be 0, 0, 0, 1", name);
-  for (int r = 0; r < 3; ++r) {
-    for (int k = 0; k < 3; ++k) T->R[3 * r + k] = m[4 * r + k];
-    T->t[r] = m[4 * r + 3];
-  }
+  pose_from_rows(m, T);
   CHECK_ARG(register_pose_ok(*T), "%s: the entries must be finite and the rotation orthonormal (|R^T R - I| <= 1e-6)", name);
   return MC_OK;
 }
 
 int reg_distance(const VoxState* s, double max_distance) {
   CHECK_ARG(std::isfinite(max_distance) && max_distance > 0.0, "max_distance must be finite and > 0 (got %g)", max_distance);
-  CHECK_ARG(max_distance / s->h <= (double)kNormalsMaxR,
-            "max_distance %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius",
-            max_distance, max_distance / s->h, s->h, kNormalsMaxR);
-  return MC_OK;
+  return check_window(s, max_distance, "max_distance");
 }
 
 // the points of a batch (frame < 0: all of them, as one body) or of device rows as a source
@@ -422,22 +483,18 @@ int reg_args(mc_ctx* c, VoxState* s, const RegSrc& src, double max_distance, Reg
   a->M = s->M;
   a->h = s->h;
   std::copy_n(s->o, 3, a->o);
-  a->w.R = std::max(1, (int)std::ceil(max_distance / s->h));
-  a->w.max_nn = 0;
-  a->w.r2 = max_distance * max_distance;
+  a->w = query_of(s, max_distance, 0);
   if (s->M == 0) return MC_OK;   // no table and no centroids: every point is without a pair
   if (int r = centroids(c, s)) return r;
-  a->g.keys = s->keys; a->g.vid = s->vid; a->g.cent = s->cent;
-  a->g.shift = s->shift; a->g.mask = s->mask;
+  a->g = grid_of(s);
   return MC_OK;
 }
 
 template <bool BATCH>
 int reg_correspond(mc_ctx* c, VoxState* s, const RegArgs& a) {
   {
-    TimedRegion tr(c, &s->rg_ev[kRgCorrespond], c->stream);
-    hipLaunchKernelGGL(k_rg_correspond<BATCH>, dim3((uint32_t)((a.src.n + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0,
-                       c->stream, a);
+    TimedRegion tr(c, &s->ev[kRgCorrespond], c->stream);
+    hipLaunchKernelGGL(k_rg_correspond<BATCH>, dim3(blocks_of(a.src.n)), dim3(kVoxBlock), 0, c->stream, a);
   }
   HIPCHK(hipGetLastError());
   return MC_OK;
@@ -446,8 +503,8 @@ int reg_correspond(mc_ctx* c, VoxState* s, const RegArgs& a) {
 template <bool BATCH>
 int nearest_run(mc_ctx* c, const RegSrc& src, double max_distance, const double* transform, int32_t* d_ids, double* d_dist2,
                 const char* who) {
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "%s needs a successful mc_voxel_build_* first", who);
+  VoxState* s;
+  if (int r = live_build(c, who, &s)) return r;
   if (int r = reg_distance(s, max_distance)) return r;
   RegPose T;
   if (int r = reg_pose(transform, "transform", &T)) return r;
@@ -464,8 +521,8 @@ int nearest_run(mc_ctx* c, const RegSrc& src, double max_distance, const double*
 template <bool BATCH>
 int register_run(mc_ctx* c, const RegSrc& src, const mc_register_params* p, double* transformation, double* history,
                  int64_t* stats, const char* who) {
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "%s needs a successful mc_voxel_build_* first", who);
+  VoxState* s;
+  if (int r = live_build(c, who, &s)) return r;
   if (int r = reg_distance(s, p->max_distance)) return r;
   CHECK_ARG(p->max_iterations >= 1 && p->max_iterations <= kRegMaxIterations, "max_iterations must be in 1..%d (got %d)",
             kRegMaxIterations, p->max_iterations);
@@ -503,18 +560,17 @@ int register_run(mc_ctx* c, const RegSrc& src, const mc_register_params* p, doub
     int64_t cnt = L / kVoxBlock;
     double* cur = s->rg_tree;
     {
-      TimedRegion tr(c, &s->rg_ev[kRgLeaves], c->stream);
+      TimedRegion tr(c, &s->ev[kRgLeaves], c->stream);
       HIPCHK(hipMemsetAsync(a.pairs, 0, sizeof(unsigned long long), c->stream));
       hipLaunchKernelGGL(k_rg_leaves<BATCH>, dim3((uint32_t)cnt), dim3(kVoxBlock), 0, c->stream, a);
     }
     if (cnt >= kVoxBlock) {
-      TimedRegion tr(c, &s->rg_ev[kRgTree], c->stream);
+      TimedRegion tr(c, &s->ev[kRgTree], c->stream);
       cur = tree_levels<kRegSums>(c, cur, &cnt);
     }
     HIPCHK(hipGetLastError());
     // the iteration's one copy: the last level's partials and the pair counter behind them
-    HIPCHK(hipMemcpyAsync(top.data(), cur, top.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    if (int r = copy_back(c, top.data(), cur, top.size() * sizeof(double))) return r;
     const auto t0 = std::chrono::steady_clock::now();
     unsigned long long found = 0;
     std::memcpy(&found, &top[(size_t)kRegSums * cnt], sizeof found);
@@ -530,12 +586,7 @@ int register_run(mc_ctx* c, const RegSrc& src, const mc_register_params* p, doub
     }
   }
   if (status == kRegGoOn) status = kRegMaxIter;
-  for (int r = 0; r < 3; ++r) {
-    for (int k = 0; k < 3; ++k) transformation[4 * r + k] = a.T.R[3 * r + k];
-    transformation[4 * r + 3] = a.T.t[r];
-  }
-  transformation[12] = transformation[13] = transformation[14] = 0.0;
-  transformation[15] = 1.0;
+  pose_to_rows(a.T, transformation);
   stats[0] = pairs;
   stats[1] = it;
   stats[2] = status;
@@ -600,12 +651,12 @@ int mc_voxel_build_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n, d
 int mc_voxel_emit_batch(mc_ctx* c, mc_batch* out) {
   CHECK_ARG(c && out, "NULL argument");
   CHECK_ARG(out->ctx == c, "batch belongs to another context");
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_emit_batch needs a successful mc_voxel_build_* first");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_emit_batch", &s)) return r;
   CHECK_ARG(out->F == 1 && out->N == s->M, "the out batch must be one frame of exactly %lld points (it has %d frames, %lld points)",
             (long long)s->M, out->F, (long long)out->N);
   DeviceGuard g(c->device);
-  VoxOut a = {};
+  VoxOut a = out_of(s);
   a.cols = out->d_cols;
   a.C = out->C;
   if (int r = emit(c, s, a, true, out->P)) return r;
@@ -615,11 +666,11 @@ int mc_voxel_emit_batch(mc_ctx* c, mc_batch* out) {
 int mc_voxel_emit_f64(mc_ctx* c, double* d_rows, int32_t* d_counts, int32_t* d_keys) {
   CHECK_ARG(c, "ctx is NULL");
   CHECK_ARG(((uintptr_t)d_rows & 15) == 0, "d_rows must be 16-byte aligned");
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_emit_f64 needs a successful mc_voxel_build_* first");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_emit_f64", &s)) return r;
   if (!d_rows && !d_counts && !d_keys) return MC_OK;
   DeviceGuard g(c->device);
-  VoxOut a = {};
+  VoxOut a = out_of(s);
   a.rows = d_rows;
   a.counts = d_counts;
   a.keys_out = d_keys;
@@ -628,19 +679,7 @@ int mc_voxel_emit_f64(mc_ctx* c, double* d_rows, int32_t* d_counts, int32_t* d_k
 
 int mc_timing_read_voxel(mc_ctx* c, double* ms_phase, int64_t* launches) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  int64_t total = 0;
-  for (int k = 0; k < kPhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
-  if (VoxState* s = state_of(c, false)) {
-    for (int k = 0; k < kPhases; ++k) {
-      int64_t n = 0;
-      if (int r = sum_events(c, s->ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
-      total += n;
-    }
-  }
-  if (launches) *launches = total;
-  return MC_OK;
+  return read_phases(c, kFilterPhases, ms_phase, launches);
 }
 
 int mc_voxel_normals(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoint, double* d_normals,
@@ -651,19 +690,7 @@ int mc_voxel_normals(mc_ctx* c, double radius, int32_t max_nn, const double* vie
 
 int mc_timing_read_normals(mc_ctx* c, double* ms_phase, int64_t* launches) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  int64_t total = 0;
-  for (int k = 0; k < kNrmPhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
-  if (VoxState* s = state_of(c, false)) {
-    for (int k = 0; k < kNrmPhases; ++k) {
-      int64_t n = 0;
-      if (int r = sum_events(c, s->nrm_ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
-      total += n;
-    }
-  }
-  if (launches) *launches = total;
-  return MC_OK;
+  return read_phases(c, kNormalsPhases, ms_phase, launches);
 }
 
 int mc_voxel_clusters(mc_ctx* c, double eps, int32_t min_points, int32_t weighted, int32_t* d_labels, int32_t* d_density,
@@ -673,59 +700,55 @@ int mc_voxel_clusters(mc_ctx* c, double eps, int32_t min_points, int32_t weighte
   CHECK_ARG(std::isfinite(eps) && eps > 0.0, "eps must be finite and > 0 (got %g)", eps);
   CHECK_ARG(min_points >= 1, "min_points must be >= 1 (got %d)", min_points);
   CHECK_ARG(weighted == 0 || weighted == 1, "weighted must be 0 or 1 (got %d)", weighted);
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_clusters needs a successful mc_voxel_build_* first");
-  CHECK_ARG(eps / s->h <= (double)kNormalsMaxR,
-            "eps %g is %g voxels of %g and the search window takes at most %d: voxelise coarser or shrink the radius",
-            eps, eps / s->h, s->h, kNormalsMaxR);
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_clusters", &s)) return r;
+  if (int r = check_window(s, eps, "eps")) return r;
   const int64_t M = s->M;
   CHECK_ARG(M == 0 || d_labels, "d_labels is NULL");
   s->cl_current = false;   // a refused call leaves the last clustering; one that starts replaces it
   s->cl_K = 0;
   if (M == 0) { s->cl_current = true; return MC_OK; }
   DeviceGuard g(c->device);
-  const uint32_t blocks = (uint32_t)((M + kVoxBlock - 1) / kVoxBlock);
+  const uint32_t blocks = blocks_of(M);
   if (int r = centroids(c, s)) return r;
   if (int r = ctx_reserve(c, s->cl_parent, (size_t)M)) return r;
   if (int r = ctx_reserve(c, s->cl_label, (size_t)M)) return r;
   if (int r = ctx_reserve(c, s->cl_chunk, (size_t)blocks)) return r;
   if (!s->cl_meta) if (int r = s->cl_meta.alloc(2)) return r;
   ClusterArgs a = {};
-  a.g.keys = s->keys; a.g.vid = s->vid; a.g.cent = s->cent;
-  a.g.shift = s->shift; a.g.mask = s->mask;
+  a.g = grid_of(s);
   a.vslot = s->vslot;
   a.cnt = s->cnt;
   a.M = M;
-  a.q = cluster_query(std::max(1, (int)std::ceil(eps / s->h)), eps * eps);
+  a.q = cluster_query(window_cells(s, eps), eps * eps);
   a.min_points = min_points;
   a.weighted = weighted;
   a.parent = s->cl_parent; a.label = s->cl_label; a.chunk = s->cl_chunk;
   a.labels_out = d_labels; a.density_out = d_density;
   const dim3 blk(kVoxBlock), grid(blocks);
   {
-    TimedRegion tr(c, &s->cl_ev[kClDensity], c->stream);
+    TimedRegion tr(c, &s->ev[kClDensity], c->stream);
     hipLaunchKernelGGL(k_cl_density, grid, blk, 0, c->stream, a);
   }
   {
-    TimedRegion tr(c, &s->cl_ev[kClUnion], c->stream);
+    TimedRegion tr(c, &s->ev[kClUnion], c->stream);
     hipLaunchKernelGGL(k_cl_union, grid, blk, 0, c->stream, a);
   }
   {
-    TimedRegion tr(c, &s->cl_ev[kClLabel], c->stream);
+    TimedRegion tr(c, &s->ev[kClLabel], c->stream);
     hipLaunchKernelGGL(k_cl_label, grid, blk, 0, c->stream, a);
   }
   {
-    TimedRegion tr(c, &s->cl_ev[kClNumber], c->stream);
+    TimedRegion tr(c, &s->ev[kClNumber], c->stream);
     hipLaunchKernelGGL(k_cl_flag, grid, blk, 0, c->stream, a);
-    hipLaunchKernelGGL(k_vox_scan, dim3(1), blk, 0, c->stream, s->cl_chunk.get(), (int64_t)blocks, s->cl_meta.get());
+    scan_counts(c, s->cl_chunk, blocks, s->cl_meta);
     hipLaunchKernelGGL(k_cl_rank, grid, blk, 0, c->stream, a);
     hipLaunchKernelGGL(k_cl_number, grid, blk, 0, c->stream, a);
   }
   HIPCHK(hipGetLastError());
   // the one synchronisation: K
   uint32_t meta[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(meta, s->cl_meta, sizeof meta, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int r = copy_back(c, meta, s->cl_meta, sizeof meta)) return r;
   if ((int64_t)meta[1] > M) return fail(MC_ERR_STATE, "voxel clusters: %u clusters of %lld voxels", meta[1], (long long)M);
   s->cl_K = (int64_t)meta[1];
   s->cl_current = true;
@@ -748,13 +771,13 @@ int mc_voxel_cluster_stats(mc_ctx* c, int32_t* d_voxels, int64_t* d_points, int3
   a.points = reinterpret_cast<long long*>(d_points);
   a.cell_min = d_cell_min; a.cell_max = d_cell_max;
   {
-    TimedRegion tr(c, &s->cl_ev[kClStats], c->stream);
+    TimedRegion tr(c, &s->ev[kClStats], c->stream);
     // every cluster holds a voxel, so no start value survives: 0x7F7F7F7F is above and 0x80808080 below any key
     if (d_voxels) HIPCHK(hipMemsetAsync(d_voxels, 0, (size_t)K * sizeof(int32_t), c->stream));
     if (d_points) HIPCHK(hipMemsetAsync(d_points, 0, (size_t)K * sizeof(int64_t), c->stream));
     if (d_cell_min) HIPCHK(hipMemsetAsync(d_cell_min, 0x7F, (size_t)K * 3 * sizeof(int32_t), c->stream));
     if (d_cell_max) HIPCHK(hipMemsetAsync(d_cell_max, 0x80, (size_t)K * 3 * sizeof(int32_t), c->stream));
-    hipLaunchKernelGGL(k_cl_stats, dim3((uint32_t)((s->M + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, a);
+    hipLaunchKernelGGL(k_cl_stats, dim3(blocks_of(s->M)), dim3(kVoxBlock), 0, c->stream, a);
   }
   HIPCHK(hipGetLastError());
   return MC_OK;
@@ -762,19 +785,7 @@ int mc_voxel_cluster_stats(mc_ctx* c, int32_t* d_voxels, int64_t* d_points, int3
 
 int mc_timing_read_clusters(mc_ctx* c, double* ms_phase, int64_t* launches) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  int64_t total = 0;
-  for (int k = 0; k < kClusterPhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
-  if (VoxState* s = state_of(c, false)) {
-    for (int k = 0; k < kClusterPhases; ++k) {
-      int64_t n = 0;
-      if (int r = sum_events(c, s->cl_ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
-      total += n;
-    }
-  }
-  if (launches) *launches = total;
-  return MC_OK;
+  return read_phases(c, kClPhases, ms_phase, launches);
 }
 
 int mc_voxel_plane_chunk(void) { return kPlaneChunk; }
@@ -790,8 +801,8 @@ int mc_voxel_plane(mc_ctx* c, double distance, int32_t num_iterations, uint64_t 
   CHECK_ARG(num_iterations >= 1 && num_iterations <= kPlaneMaxIterations, "num_iterations must be in 1..%d (got %d)",
             kPlaneMaxIterations, num_iterations);
   CHECK_ARG(refine == 0 || refine == 1, "refine must be 0 or 1 (got %d)", refine);
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_plane needs a successful mc_voxel_build_* first");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_plane", &s)) return r;
   const int64_t M = s->M;
   CHECK_ARG(M >= 3, "a plane needs three candidate voxels (the cloud has %lld)", (long long)M);
   DeviceGuard g(c->device);
@@ -816,13 +827,13 @@ int mc_voxel_plane(mc_ctx* c, double distance, int32_t num_iterations, uint64_t 
     a.K = K;
     a.tt = distance * distance;
     a.hyp = s->pl_hyp; a.samples = s->pl_samples;
-    TimedRegion tr(c, &s->pl_ev[kPlSample], c->stream);
-    hipLaunchKernelGGL(k_pl_sample, dim3((uint32_t)((K + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0, c->stream, a);
+    TimedRegion tr(c, &s->ev[kPlSample], c->stream);
+    hipLaunchKernelGGL(k_pl_sample, dim3(blocks_of(K)), dim3(kVoxBlock), 0, c->stream, a);
   }
   {
     const int64_t tiles = (M + kPlaneTile - 1) / kPlaneTile;
     const dim3 grid((uint32_t)std::min<int64_t>(tiles, kPlaneScoreGrid));
-    TimedRegion tr(c, &s->pl_ev[kPlScore], c->stream);
+    TimedRegion tr(c, &s->ev[kPlScore], c->stream);
     HIPCHK(hipMemsetAsync(s->pl_score, 0, (size_t)K * sizeof(uint32_t), c->stream));
     for (int32_t k0 = 0; k0 < K; k0 += kPlaneChunk)
       hipLaunchKernelGGL(k_pl_score, grid, dim3(kVoxBlock), 0, c->stream, (const double*)s->cent.get(), d_among, M,
@@ -831,8 +842,7 @@ int mc_voxel_plane(mc_ctx* c, double distance, int32_t num_iterations, uint64_t 
   HIPCHK(hipGetLastError());
   // pick, on the host: the scores come back with the call's first synchronisation
   std::vector<uint32_t> score((size_t)K);
-  HIPCHK(hipMemcpyAsync(score.data(), s->pl_score, score.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int r = copy_back(c, score.data(), s->pl_score, score.size() * sizeof(uint32_t))) return r;
   const int32_t k = plane_pick(score.data(), K);
   if (k < 0) {   // no valid hypothesis with three inliers: an all-false mask and the zero model
     HIPCHK(hipMemsetAsync(s->pl_mask, 0, (size_t)M, c->stream));
@@ -842,8 +852,7 @@ int mc_voxel_plane(mc_ctx* c, double distance, int32_t num_iterations, uint64_t 
   PlaneHyp h;
   static_assert(sizeof(PlaneHyp) == kPlaneHyp * sizeof(double), "the hypothesis record");
   HIPCHK(hipMemcpyAsync(&h, s->pl_hyp + (size_t)kPlaneHyp * k, sizeof h, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(samples, s->pl_samples + (size_t)3 * k, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int r = copy_back(c, samples, s->pl_samples + (size_t)3 * k, 3 * sizeof(int32_t))) return r;
   const double raw[4] = {h.n[0], h.n[1], h.n[2], h.d};
   int64_t n_in = 0;
   if (int r = plane_mask(c, s, d_among, raw, h.tau, false, &n_in)) return r;
@@ -869,8 +878,8 @@ int mc_voxel_plane(mc_ctx* c, double distance, int32_t num_iterations, uint64_t 
 int mc_voxel_emit_selected(mc_ctx* c, const uint8_t* d_mask, mc_batch* out) {
   CHECK_ARG(c && out, "NULL argument");
   CHECK_ARG(out->ctx == c, "batch belongs to another context");
-  VoxState* s = state_of(c, false);
-  if (!s || !s->built) return fail(MC_ERR_STATE, "mc_voxel_emit_selected needs a successful mc_voxel_build_* first");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_emit_selected", &s)) return r;
   CHECK_ARG(s->M == 0 || d_mask, "d_mask is NULL");
   DeviceGuard g(c->device);
   int64_t n = 0;
@@ -878,17 +887,13 @@ int mc_voxel_emit_selected(mc_ctx* c, const uint8_t* d_mask, mc_batch* out) {
   CHECK_ARG(out->F == 1 && out->N == n, "the out batch must be one frame of exactly %lld points (it has %d frames, %lld points)",
             (long long)n, out->F, (long long)out->N);
   if (out->P > 0) {
-    VoxOut a = {};
-    a.keys = s->keys; a.vslot = s->vslot; a.sums = s->sums; a.cnt = s->cnt;
-    a.M = s->M;
-    a.h = s->h;
-    std::copy_n(s->o, 3, a.o);
+    VoxOut a = out_of(s);
     a.cols = out->d_cols;
     a.C = out->C;
     {
-      TimedRegion tr(c, &s->pl_ev[kPlSelect], c->stream);
-      hipLaunchKernelGGL(k_pl_emit_selected, dim3((uint32_t)((out->P / 4 + kVoxBlock - 1) / kVoxBlock)), dim3(kVoxBlock), 0,
-                         c->stream, a, out->P, (const uint32_t*)s->pl_ids.get(), n);
+      TimedRegion tr(c, &s->ev[kPlSelect], c->stream);
+      hipLaunchKernelGGL(k_pl_emit_selected, dim3(blocks_of(out->P / 4)), dim3(kVoxBlock), 0, c->stream, a, out->P,
+                         (const uint32_t*)s->pl_ids.get(), n);
     }
     HIPCHK(hipGetLastError());
   }
@@ -897,19 +902,7 @@ int mc_voxel_emit_selected(mc_ctx* c, const uint8_t* d_mask, mc_batch* out) {
 
 int mc_timing_read_plane(mc_ctx* c, double* ms_phase, int64_t* launches) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  int64_t total = 0;
-  for (int k = 0; k < kPlanePhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
-  if (VoxState* s = state_of(c, false)) {
-    for (int k = 0; k < kPlanePhases; ++k) {
-      int64_t n = 0;
-      if (int r = sum_events(c, s->pl_ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
-      total += n;
-    }
-  }
-  if (launches) *launches = total;
-  return MC_OK;
+  return read_phases(c, kPlanePhases, ms_phase, launches);
 }
 
 int mc_voxel_nearest_batch(mc_ctx* c, const mc_batch* src, int32_t frame, double max_distance, const double* transform,
@@ -953,22 +946,15 @@ int mc_voxel_register_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n
 
 int mc_timing_read_register(mc_ctx* c, double* ms_phase, int64_t* launches) {
   CHECK_ARG(c, "ctx is NULL");
-  DeviceGuard g(c->device);
-  if (int r = sync_all(c)) return r;
-  int64_t total = 0;
-  for (int k = 0; k < kRegPhases; ++k) if (ms_phase) ms_phase[k] = 0.0;
-  if (VoxState* s = state_of(c, false)) {
-    for (int k = 0; k < kRgSolve; ++k) {
-      int64_t n = 0;
-      if (int r = sum_events(c, s->rg_ev[k], ms_phase ? ms_phase + k : nullptr, &n)) return r;
-      total += n;
-    }
-    if (ms_phase) ms_phase[kRgSolve] = s->rg_solve_ms;
-    total += s->rg_solve_n;
+  if (int r = read_phases(c, kRegPhases, ms_phase, launches)) return r;
+  // the solve's slot, by the host's clock
+  VoxState* s = state_of(c, false);
+  if (ms_phase) ms_phase[kRgSolve] = s ? s->rg_solve_ms : 0.0;
+  if (s) {
+    if (launches) *launches += s->rg_solve_n;
     s->rg_solve_ms = 0.0;
     s->rg_solve_n = 0;
   }
-  if (launches) *launches = total;
   return MC_OK;
 }
 
@@ -979,10 +965,6 @@ int mc_voxel_release(mc_ctx* c) {
   DeviceGuard g(c->device);
   (void)sync_all(c);
   for (auto& v : s->ev) ev_recycle(c, v);
-  for (auto& v : s->nrm_ev) ev_recycle(c, v);
-  for (auto& v : s->cl_ev) ev_recycle(c, v);
-  for (auto& v : s->pl_ev) ev_recycle(c, v);
-  for (auto& v : s->rg_ev) ev_recycle(c, v);
   c->ext[mcimpl::kSlotVoxel].reset();
   return MC_OK;
 }

@@ -361,45 +361,35 @@ class Context:
         check(self.lib.mc_timing_read_spans(self.handle, ptr(buf, c_double), cap, ctypes.byref(n)), "timing_read_spans")
         return buf[:min(n.value, cap)].tolist()
 
+    def _read_phases(self, fn: str, keys: tuple) -> dict:
+        """One ``mc_timing_read_*`` of a voxel stage: its phases' ms under ``keys``, then the regions timed."""
+        ms = np.zeros(len(keys), np.float64)
+        n = c_int64()
+        check(getattr(self.lib, "mc_" + fn)(self.handle, ptr(ms, c_double), ctypes.byref(n)), fn)
+        return {**dict(zip(keys, ms)), "regions": n.value}
+
     def read_timing_voxel(self) -> dict:
         """Event time (ms) of the voxel filter's phases since the last read (mc_timing_read_voxel)."""
-        ms = np.zeros(4, np.float64)
-        n = c_int64()
-        check(self.lib.mc_timing_read_voxel(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_voxel")
-        return {"insert_ms": ms[0], "rank_ms": ms[1], "accumulate_ms": ms[2], "finalise_ms": ms[3], "regions": n.value}
+        return self._read_phases("timing_read_voxel", ("insert_ms", "rank_ms", "accumulate_ms", "finalise_ms"))
 
     def read_timing_normals(self) -> dict:
         """Event time (ms) of the phases of VoxelCloud.normals since the last read (mc_timing_read_normals)."""
-        ms = np.zeros(3, np.float64)
-        n = c_int64()
-        check(self.lib.mc_timing_read_normals(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_normals")
-        return {"centroids_ms": ms[0], "window_ms": ms[1], "cap_ms": ms[2], "regions": n.value}
+        return self._read_phases("timing_read_normals", ("centroids_ms", "window_ms", "cap_ms"))
 
     def read_timing_clusters(self) -> dict:
         """Event time (ms) of the phases of VoxelCloud.clusters since the last read (mc_timing_read_clusters)."""
-        ms = np.zeros(5, np.float64)
-        n = c_int64()
-        check(self.lib.mc_timing_read_clusters(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_clusters")
-        return {"density_ms": ms[0], "union_ms": ms[1], "label_ms": ms[2], "number_ms": ms[3], "stats_ms": ms[4],
-                "regions": n.value}
+        return self._read_phases("timing_read_clusters", ("density_ms", "union_ms", "label_ms", "number_ms", "stats_ms"))
 
     def read_timing_plane(self) -> dict:
         """Event time (ms) of the phases of VoxelCloud.segment_plane and VoxelCloud.select since the last read
         (mc_timing_read_plane)."""
-        ms = np.zeros(6, np.float64)
-        n = c_int64()
-        check(self.lib.mc_timing_read_plane(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_plane")
-        return {"compact_ms": ms[0], "sample_ms": ms[1], "score_ms": ms[2], "mask_ms": ms[3], "moments_ms": ms[4],
-                "select_ms": ms[5], "regions": n.value}
+        return self._read_phases("timing_read_plane",
+                                 ("compact_ms", "sample_ms", "score_ms", "mask_ms", "moments_ms", "select_ms"))
 
     def read_timing_register(self) -> dict:
         """Time (ms) of the phases of VoxelCloud.register and VoxelCloud.nearest since the last read
         (mc_timing_read_register); the solve is the host's, by its clock."""
-        ms = np.zeros(5, np.float64)
-        n = c_int64()
-        check(self.lib.mc_timing_read_register(self.handle, ptr(ms, c_double), ctypes.byref(n)), "timing_read_register")
-        return {"normals_ms": ms[0], "correspond_ms": ms[1], "leaves_ms": ms[2], "tree_ms": ms[3], "solve_ms": ms[4],
-                "regions": n.value}
+        return self._read_phases("timing_read_register", ("normals_ms", "correspond_ms", "leaves_ms", "tree_ms", "solve_ms"))
 
     def device_buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)

@@ -116,6 +116,7 @@ frame outside the batch, max_iterations not an integer in 1..2^16, a tolerance t
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 from ctypes import c_double, c_int32, c_int64
@@ -129,22 +130,65 @@ from .runtime import Batch, Context, default_context
 MAX_POINTS = 2 ** 31 - 1
 
 
+MAX_RADIUS_VOXELS = 4      # the neighbour search is a window of (2 ceil(radius / h) + 1)^3 <= 9^3 table probes
+MAX_NN = 64
+
+
+# ---- one checker per kind of argument: every method's checks come before its first touch of a device ----------------
+def _number(value, name, positive=True):
+    """``value`` as a finite float > 0 (``positive=False``: >= 0)."""
+    bound = "> 0" if positive else ">= 0"
+    try:
+        x = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a number {bound}, got {value!r}") from None
+    if not (math.isfinite(x) and (x > 0.0 if positive else x >= 0.0)):
+        raise ValueError(f"{name} must be finite and {bound}, got {value!r}")
+    return x
+
+
+def _window(x, name, h):
+    """``x``, a search radius of a cloud of voxel size ``h`` (None: not known here, the library checks)."""
+    if h is not None and x / h > MAX_RADIUS_VOXELS:
+        raise ValueError(f"{name} {x!r} is {x / h:.3g} voxels of {h!r} and the search window takes at most "
+                         f"{MAX_RADIUS_VOXELS}: voxelise coarser or shrink the radius")
+    return x
+
+
+def _integer(value, name, lo, hi, wording, also=()):
+    """``value`` as an int: an integer, not a bool, in lo..hi or one of ``also``; ``wording`` says so to the caller."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not (value in also or lo <= value <= hi):
+        raise ValueError(f"{name} must be {wording}, got {value!r}")
+    return int(value)
+
+
+def _flag(value, name):
+    """A bool as 0 / 1."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{name} must be True or False, got {value!r}")
+    return int(bool(value))
+
+
+class _Buffers(contextlib.ExitStack):
+    """The device buffers of one call: each is closed on every way out of the ``with``."""
+
+    def __init__(self, ctx):
+        super().__init__()
+        self._ctx = ctx
+
+    def take(self, nbytes):
+        buf = self._ctx.device_buffer(nbytes)
+        self.callback(buf.close)
+        return buf
+
+
 def _grid(voxel, origin):
     """(h, origin as 3 float64), checked before a device is touched."""
-    try:
-        h = float(voxel)
-    except (TypeError, ValueError):
-        raise ValueError(f"voxel must be a number > 0, got {voxel!r}") from None
-    if not (math.isfinite(h) and h > 0.0):
-        raise ValueError(f"voxel must be finite and > 0, got {voxel!r}")
+    h = _number(voxel, "voxel")
     o = np.ascontiguousarray(origin, dtype=np.float64)
     if o.shape != (3,) or not np.isfinite(o).all():
         raise ValueError(f"origin must be three finite numbers, got {origin!r}")
     return h, o
-
-
-MAX_RADIUS_VOXELS = 4      # the neighbour search is a window of (2 ceil(radius / h) + 1)^3 <= 9^3 table probes
-MAX_NN = 64
 
 
 class VoxelNormals(NamedTuple):
@@ -157,17 +201,8 @@ class VoxelNormals(NamedTuple):
 
 def _normals_args(radius, max_nn, viewpoint, h):
     """(radius, max_nn, viewpoint as 3 float64 or None), checked before a device is touched."""
-    try:
-        r = float(radius)
-    except (TypeError, ValueError):
-        raise ValueError(f"radius must be a number > 0, got {radius!r}") from None
-    if not (math.isfinite(r) and r > 0.0):
-        raise ValueError(f"radius must be finite and > 0, got {radius!r}")
-    if h is not None and r / h > MAX_RADIUS_VOXELS:
-        raise ValueError(f"radius {r!r} is {r / h:.3g} voxels of {h!r} and the search window takes at most "
-                         f"{MAX_RADIUS_VOXELS}: voxelise coarser or shrink the radius")
-    if isinstance(max_nn, bool) or not isinstance(max_nn, (int, np.integer)) or not (max_nn == 0 or 3 <= max_nn <= MAX_NN):
-        raise ValueError(f"max_nn must be 0 (no cap) or an integer in 3..{MAX_NN}, got {max_nn!r}")
+    r = _window(_number(radius, "radius"), "radius", h)
+    nn = _integer(max_nn, "max_nn", 3, MAX_NN, f"0 (no cap) or an integer in 3..{MAX_NN}", also=(0,))
     vp = None
     if viewpoint is not None:
         try:
@@ -176,7 +211,7 @@ def _normals_args(radius, max_nn, viewpoint, h):
             raise ValueError(f"viewpoint must be three finite numbers, got {viewpoint!r}") from None
         if vp.shape != (3,) or not np.isfinite(vp).all():
             raise ValueError(f"viewpoint must be three finite numbers, got {viewpoint!r}")
-    return r, int(max_nn), vp
+    return r, nn, vp
 
 
 class VoxelClusters(NamedTuple):
@@ -192,20 +227,8 @@ class VoxelClusters(NamedTuple):
 
 def _clusters_args(eps, min_points, weighted, h):
     """(eps, min_points, weighted as 0 / 1), checked before a device is touched."""
-    try:
-        e = float(eps)
-    except (TypeError, ValueError):
-        raise ValueError(f"eps must be a number > 0, got {eps!r}") from None
-    if not (math.isfinite(e) and e > 0.0):
-        raise ValueError(f"eps must be finite and > 0, got {eps!r}")
-    if h is not None and e / h > MAX_RADIUS_VOXELS:
-        raise ValueError(f"eps {e!r} is {e / h:.3g} voxels of {h!r} and the search window takes at most "
-                         f"{MAX_RADIUS_VOXELS}: voxelise coarser or shrink the radius")
-    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or not 1 <= min_points <= MAX_POINTS:
-        raise ValueError(f"min_points must be an integer >= 1, got {min_points!r}")
-    if not isinstance(weighted, (bool, np.bool_)):
-        raise ValueError(f"weighted must be True or False, got {weighted!r}")
-    return e, int(min_points), int(bool(weighted))
+    e = _window(_number(eps, "eps"), "eps", h)
+    return e, _integer(min_points, "min_points", 1, MAX_POINTS, "an integer >= 1"), _flag(weighted, "weighted")
 
 
 MAX_ITERATIONS = 2 ** 20
@@ -233,20 +256,10 @@ def _mask_arg(mask, M, name):
 
 def _plane_args(distance_threshold, num_iterations, seed, refine, among, M):
     """(t, K, seed, refine as 0 / 1, among as bytes or None), checked before a device is touched."""
-    try:
-        t = float(distance_threshold)
-    except (TypeError, ValueError):
-        raise ValueError(f"distance_threshold must be a number > 0, got {distance_threshold!r}") from None
-    if not (math.isfinite(t) and t > 0.0):
-        raise ValueError(f"distance_threshold must be finite and > 0, got {distance_threshold!r}")
-    if (isinstance(num_iterations, bool) or not isinstance(num_iterations, (int, np.integer))
-            or not 1 <= num_iterations <= MAX_ITERATIONS):
-        raise ValueError(f"num_iterations must be an integer in 1..{MAX_ITERATIONS}, got {num_iterations!r}")
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
-        raise ValueError(f"seed must be an integer in 0..2^64-1, got {seed!r}")
-    if not isinstance(refine, (bool, np.bool_)):
-        raise ValueError(f"refine must be True or False, got {refine!r}")
-    return t, int(num_iterations), int(seed), int(bool(refine)), None if among is None else _mask_arg(among, M, "among")
+    t = _number(distance_threshold, "distance_threshold")
+    K = _integer(num_iterations, "num_iterations", 1, MAX_ITERATIONS, f"an integer in 1..{MAX_ITERATIONS}")
+    sd = _integer(seed, "seed", 0, 2 ** 64 - 1, "an integer in 0..2^64-1")
+    return t, K, sd, _flag(refine, "refine"), None if among is None else _mask_arg(among, M, "among")
 
 
 class VoxelNearest(NamedTuple):
@@ -271,16 +284,7 @@ MAX_REGISTER_ITERATIONS = 2 ** 16
 
 
 def _distance_arg(max_distance, h):
-    try:
-        d = float(max_distance)
-    except (TypeError, ValueError):
-        raise ValueError(f"max_distance must be a number > 0, got {max_distance!r}") from None
-    if not (math.isfinite(d) and d > 0.0):
-        raise ValueError(f"max_distance must be finite and > 0, got {max_distance!r}")
-    if h is not None and d / h > MAX_RADIUS_VOXELS:
-        raise ValueError(f"max_distance {d!r} is {d / h:.3g} voxels of {h!r} and the search window takes at most "
-                         f"{MAX_RADIUS_VOXELS}: voxelise coarser or shrink the radius")
-    return d
+    return _window(_number(max_distance, "max_distance"), "max_distance", h)
 
 
 def _pose_arg(pose, name):
@@ -308,9 +312,7 @@ def _source_arg(ctx, src, frame):
             raise ValueError("the batch belongs to another context")
         f = -1
         if frame is not None:
-            if isinstance(frame, bool) or not isinstance(frame, (int, np.integer)) or not 0 <= frame < src.n_frames:
-                raise ValueError(f"frame must be an integer in 0..{src.n_frames - 1}, got {frame!r}")
-            f = int(frame)
+            f = _integer(frame, "frame", 0, src.n_frames - 1, f"an integer in 0..{src.n_frames - 1}")
         n = src.n_points if f < 0 else int(src.counts[f])
         if n == 0:
             raise ValueError("the source is empty")
@@ -330,19 +332,8 @@ def _source_arg(ctx, src, frame):
 
 
 def _register_args(max_iterations, tol_rotation, tol_translation):
-    if (isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer))
-            or not 1 <= max_iterations <= MAX_REGISTER_ITERATIONS):
-        raise ValueError(f"max_iterations must be an integer in 1..{MAX_REGISTER_ITERATIONS}, got {max_iterations!r}")
-    tol = []
-    for name, v in (("tol_rotation", tol_rotation), ("tol_translation", tol_translation)):
-        try:
-            t = float(v)
-        except (TypeError, ValueError):
-            raise ValueError(f"{name} must be a number >= 0, got {v!r}") from None
-        if not (math.isfinite(t) and t >= 0.0):
-            raise ValueError(f"{name} must be finite and >= 0, got {v!r}")
-        tol.append(t)
-    return int(max_iterations), tol[0], tol[1]
+    iters = _integer(max_iterations, "max_iterations", 1, MAX_REGISTER_ITERATIONS, f"an integer in 1..{MAX_REGISTER_ITERATIONS}")
+    return iters, _number(tol_rotation, "tol_rotation", positive=False), _number(tol_translation, "tol_translation", positive=False)
 
 
 def plane_score_chunk() -> int:
@@ -375,14 +366,12 @@ class VoxelCloud:
         if self.n_voxels == 0:
             return np.zeros((0, width) if width > 1 else (0,), dtype)
         n = self.n_voxels * width
-        buf = self.ctx.device_buffer(n * np.dtype(dtype).itemsize)
-        try:
+        with _Buffers(self.ctx) as bufs:
+            buf = bufs.take(n * np.dtype(dtype).itemsize)
             args = [None, None, None]
             args[which] = buf.ptr
             check(self.ctx.lib.mc_voxel_emit_f64(self.ctx.handle, *args), "voxel_downsample")
             a = buf.to_host(dtype, count=n)
-        finally:
-            buf.close()
         return a.reshape(self.n_voxels, width) if width > 1 else a
 
     def rows(self) -> np.ndarray:
@@ -411,17 +400,13 @@ class VoxelCloud:
         if M == 0:
             return VoxelNormals(np.zeros((0, 3)), np.zeros(0), np.zeros(0, np.int32), np.zeros((0, 6)) if covariance else None)
         ctx = self.ctx
-        bufs = [ctx.device_buffer(M * 32), ctx.device_buffer(M * 4), ctx.device_buffer(M * 48) if covariance else None]
-        try:
-            check(ctx.lib.mc_voxel_normals(ctx.handle, r, nn, ptr(vp, c_double), bufs[0].ptr, bufs[1].ptr,
-                                           bufs[2].ptr if covariance else None), "normals")
-            out = bufs[0].to_host(np.float64, count=4 * M).reshape(M, 4)
-            counts = bufs[1].to_host(np.int32, count=M)
-            cov = bufs[2].to_host(np.float64, count=6 * M).reshape(M, 6) if covariance else None
-        finally:
-            for b in bufs:
-                if b is not None:
-                    b.close()
+        with _Buffers(ctx) as bufs:
+            d_out, d_counts, d_cov = bufs.take(M * 32), bufs.take(M * 4), bufs.take(M * 48) if covariance else None
+            check(ctx.lib.mc_voxel_normals(ctx.handle, r, nn, ptr(vp, c_double), d_out.ptr, d_counts.ptr,
+                                           d_cov.ptr if covariance else None), "normals")
+            out = d_out.to_host(np.float64, count=4 * M).reshape(M, 4)
+            counts = d_counts.to_host(np.int32, count=M)
+            cov = d_cov.to_host(np.float64, count=6 * M).reshape(M, 6) if covariance else None
         return VoxelNormals(np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]), counts, cov)
 
     def clusters(self, eps, min_points: int = 10, weighted: bool = False) -> "VoxelClusters":
@@ -438,24 +423,21 @@ class VoxelCloud:
             return VoxelClusters(np.zeros(0, np.int32), np.zeros(0, np.int32), 0, np.zeros(0, np.int32), np.zeros(0, np.int64),
                                  np.zeros((0, 3), np.int32), np.zeros((0, 3), np.int32))
         ctx = self.ctx
-        bufs = [ctx.device_buffer(M * 4), ctx.device_buffer(M * 4)]
-        try:
+        with _Buffers(ctx) as bufs:
+            d_labels, d_density = bufs.take(M * 4), bufs.take(M * 4)
             k = c_int64(0)
-            check(ctx.lib.mc_voxel_clusters(ctx.handle, e, mp, w, bufs[0].ptr, bufs[1].ptr, ctypes.byref(k)), "clusters")
+            check(ctx.lib.mc_voxel_clusters(ctx.handle, e, mp, w, d_labels.ptr, d_density.ptr, ctypes.byref(k)), "clusters")
             K = k.value
-            labels = bufs[0].to_host(np.int32, count=M)
-            density = bufs[1].to_host(np.int32, count=M)
+            labels = d_labels.to_host(np.int32, count=M)
+            density = d_density.to_host(np.int32, count=M)
             if K == 0:
                 return VoxelClusters(labels, density, 0, np.zeros(0, np.int32), np.zeros(0, np.int64),
                                      np.zeros((0, 3), np.int32), np.zeros((0, 3), np.int32))
             # one buffer, the int64 array first: voxels (K,), points (K,), cell_min (K, 3), cell_max (K, 3)
-            bufs.append(ctx.device_buffer(K * 36))
-            base = bufs[2].ptr.value
+            d_stats = bufs.take(K * 36)
+            base = d_stats.ptr.value
             check(ctx.lib.mc_voxel_cluster_stats(ctx.handle, base + 8 * K, base, base + 12 * K, base + 24 * K), "clusters")
-            raw = bufs[2].to_host(np.int32, count=9 * K)
-        finally:
-            for b in bufs:
-                b.close()
+            raw = d_stats.to_host(np.int32, count=9 * K)
         return VoxelClusters(labels, density, K, np.ascontiguousarray(raw[2 * K:3 * K]),
                              np.ascontiguousarray(raw[:2 * K]).view(np.int64), np.ascontiguousarray(raw[3 * K:6 * K]).reshape(K, 3),
                              np.ascontiguousarray(raw[6 * K:]).reshape(K, 3))
@@ -473,20 +455,16 @@ class VoxelCloud:
         if (M if cand is None else int(np.count_nonzero(cand))) < 3:
             raise ValueError("a plane needs three candidate voxels")
         ctx = self.ctx
-        bufs = [ctx.device_buffer(M), ctx.device_buffer(M) if cand is not None else None]
-        try:
+        with _Buffers(ctx) as bufs:
+            d_inliers, d_among = bufs.take(M), bufs.take(M) if cand is not None else None
             if cand is not None:
-                bufs[1].from_host(cand)
+                d_among.from_host(cand)
             model, cov = np.zeros(4), np.zeros(6)
             samples, stats = np.zeros(3, np.int32), np.zeros(4, np.int64)
-            check(ctx.lib.mc_voxel_plane(ctx.handle, t, K, sd, rf, bufs[1].ptr if cand is not None else None, bufs[0].ptr,
+            check(ctx.lib.mc_voxel_plane(ctx.handle, t, K, sd, rf, d_among.ptr if cand is not None else None, d_inliers.ptr,
                                          ptr(model, c_double), ptr(cov, c_double), ptr(samples, c_int32), ptr(stats, c_int64)),
                   "segment_plane")
-            inliers = bufs[0].to_host(np.uint8, count=M).view(np.bool_)
-        finally:
-            for b in bufs:
-                if b is not None:
-                    b.close()
+            inliers = d_inliers.to_host(np.uint8, count=M).view(np.bool_)
         refined = bool(stats[3])
         return VoxelPlane(model, inliers, int(stats[2]), int(stats[1]), int(stats[0]), samples, cov if refined else None, refined)
 
@@ -497,13 +475,11 @@ class VoxelCloud:
         self._live()
         ctx = self.ctx
         out = Batch(ctx, [int(np.count_nonzero(m))], with_pcd_len=with_pcd_len)
-        buf = ctx.device_buffer(max(len(m), 1))
-        try:
+        with _Buffers(ctx) as bufs:
+            buf = bufs.take(max(len(m), 1))
             if len(m):
                 buf.from_host(m)
             check(ctx.lib.mc_voxel_emit_selected(ctx.handle, buf.ptr, out.handle), "select")
-        finally:
-            buf.close()
         return out
 
     def nearest(self, src, max_distance, transform=None, frame=None) -> "VoxelNearest":
@@ -516,22 +492,17 @@ class VoxelCloud:
         batch, f, rows, n = _source_arg(self.ctx, src, frame)
         self._live()
         ctx = self.ctx
-        bufs = [ctx.device_buffer(4 * n), ctx.device_buffer(8 * n), None]
-        try:
+        with _Buffers(ctx) as bufs:
+            d_ids, d_dist2 = bufs.take(4 * n), bufs.take(8 * n)
             if batch is not None:
-                rc = ctx.lib.mc_voxel_nearest_batch(ctx.handle, batch.handle, f, d, ptr(T, c_double), bufs[0].ptr, bufs[1].ptr)
+                rc = ctx.lib.mc_voxel_nearest_batch(ctx.handle, batch.handle, f, d, ptr(T, c_double), d_ids.ptr, d_dist2.ptr)
             else:
-                bufs[2] = ctx.device_buffer(rows.nbytes)
-                bufs[2].from_host(rows)
-                rc = ctx.lib.mc_voxel_nearest_f64(ctx.handle, bufs[2].ptr, rows.shape[1], n, d, ptr(T, c_double), bufs[0].ptr,
-                                                  bufs[1].ptr)
+                d_rows = bufs.take(rows.nbytes)
+                d_rows.from_host(rows)
+                rc = ctx.lib.mc_voxel_nearest_f64(ctx.handle, d_rows.ptr, rows.shape[1], n, d, ptr(T, c_double), d_ids.ptr,
+                                                  d_dist2.ptr)
             check(rc, "nearest")
-            out = VoxelNearest(bufs[0].to_host(np.int32, count=n), bufs[1].to_host(np.float64, count=n))
-        finally:
-            for b in bufs:
-                if b is not None:
-                    b.close()
-        return out
+            return VoxelNearest(d_ids.to_host(np.int32, count=n), d_dist2.to_host(np.float64, count=n))
 
     def register(self, src, max_distance, init=None, max_iterations: int = 30, normals_radius=None, max_nn: int = 30,
                  tol_rotation: float = 1e-6, tol_translation: float = 1e-6, frame=None) -> "VoxelRegistration":
@@ -555,18 +526,14 @@ class VoxelCloud:
         par = RegisterParams(d, radius, tol_r, tol_t, (c_double * 16)(*T.reshape(-1).tolist()), nn, iters)
         out, history, stats = np.zeros((4, 4)), np.zeros((iters, 8)), np.zeros(4, np.int64)
         tail = (ctypes.byref(par), ptr(out, c_double), ptr(history, c_double), ptr(stats, c_int64))
-        buf = None
-        try:
+        with _Buffers(ctx) as bufs:
             if batch is not None:
                 rc = ctx.lib.mc_voxel_register_batch(ctx.handle, batch.handle, f, *tail)
             else:
-                buf = ctx.device_buffer(rows.nbytes)
-                buf.from_host(rows)
-                rc = ctx.lib.mc_voxel_register_f64(ctx.handle, buf.ptr, rows.shape[1], n, *tail)
+                d_rows = bufs.take(rows.nbytes)
+                d_rows.from_host(rows)
+                rc = ctx.lib.mc_voxel_register_f64(ctx.handle, d_rows.ptr, rows.shape[1], n, *tail)
             check(rc, "register")
-        finally:
-            if buf is not None:
-                buf.close()
         pairs, done = int(stats[0]), int(stats[1])
         history = np.ascontiguousarray(history[:done])
         rmse = math.sqrt(float(history[-1, 1]) / pairs) if pairs else 0.0
@@ -604,15 +571,13 @@ def voxel_downsample(src, voxel, origin=(0.0, 0.0, 0.0), context: Context | None
         ctx = context or default_context()
         a = np.ascontiguousarray(a, dtype=np.float64)
         ctx._voxel_gen = None
-        d_rows = ctx.device_buffer(max(a.nbytes, 8))
-        try:
+        with _Buffers(ctx) as bufs:
+            d_rows = bufs.take(max(a.nbytes, 8))
             if a.size:
                 d_rows.from_host(a)
             bad = c_int64(-1)
             check(ctx.lib.mc_voxel_build_f64(ctx.handle, d_rows.ptr, a.shape[1], a.shape[0], h, ptr(o, c_double),
                                              ctypes.byref(m), ctypes.byref(bad)), "voxel_downsample")
-        finally:
-            d_rows.close()
     ctx._voxel_serial += 1
     ctx._voxel_gen = ctx._voxel_serial
     return VoxelCloud(ctx, m.value, ctx._voxel_gen, h)

@@ -246,3 +246,66 @@ def test_scan_ray_and_codec_state_is_per_context_and_dies_with_it():
     assert got_a[3] == got_b[3]
     destroy_only(m, b)
     assert live(m) == start
+
+
+def every_analysis(m, ctx, rows):
+    """A build of ``rows`` at h = 0.5 and every analysis of it once, from rows and from a small batch, with nothing
+    of the timing read and the cloud left live -> every result, arrays as their bytes."""
+    cloud = m.voxel_downsample(rows, 0.5, context=ctx)
+    src = rows[:200] + np.array([0.05, -0.03, 0.02, 0.0])
+    normals = cloud.normals(1.0, max_nn=8, covariance=True)          # eight of more neighbours: the cap's launch too
+    clusters = cloud.clusters(0.8, min_points=3)
+    ground = cloud.segment_plane(0.3, num_iterations=64, seed=3)
+    rest = ~ground.inliers
+    assert ground.n_inliers >= 3 and rest.sum() >= 3 and clusters.n_clusters > 0 and normals.counts.max() == 8
+    second = cloud.segment_plane(0.3, num_iterations=64, seed=4, refine=True, among=rest)
+    picked = cloud.select(rest)
+    selected = picked.download_aos()
+    picked.close()
+    batch = ctx.batch([40, 0, 25])
+    batch.upload_aos(src[:65])
+    near = (cloud.nearest(src[:, :3], 1.0), cloud.nearest(batch, 1.0, frame=2))
+    reg = (cloud.register(src[:, :3], 1.0, max_iterations=3), cloud.register(batch, 1.0, max_iterations=3))
+    batch.close()
+    assert (near[0].ids >= 0).any() and reg[0].pairs >= 6 and reg[0].iterations >= 1
+    out = [cloud.rows(), cloud.keys(), cloud.point_counts(), selected]
+    for result in (normals, clusters, ground, second) + near + reg:
+        out.extend(result)
+    return [v.tobytes() if isinstance(v, np.ndarray) else v for v in out]
+
+
+def test_the_analyses_scratch_and_unread_timing_die_with_the_state():
+    """The filter's neighbour above, for what the four analyses keep in the voxel state: their scratch and the timing
+    pairs of every phase, none of them read, go with mc_destroy alone and with mc_voxel_release."""
+    m = pkg()
+    lib = m._lib.load()
+    rows = cloud_rows(700, 10, spread=4.0)
+    gc.collect()
+    start = live(m)
+    # (a) destroy alone
+    a = fresh_context(m)
+    a.timing(True)
+    first = every_analysis(m, a, rows)
+    assert live(m) > start
+    destroy_only(m, a)
+    assert live(m) == start
+    # (b) release: the level the context idles at once its own scratch exists
+    b = fresh_context(m)
+    b.timing(True)
+    assert every_analysis(m, b, rows) == first
+    m._lib.check(lib.mc_voxel_release(b.handle), "voxel_release")
+    idle = live(m)
+    m._lib.check(lib.mc_voxel_release(b.handle), "voxel_release (again)")          # (c)
+    assert live(m) == idle
+    for read in (b.read_timing_voxel, b.read_timing_normals, b.read_timing_clusters, b.read_timing_plane,
+                 b.read_timing_register):                                            # (d)
+        t = read()
+        assert t.pop("regions") == 0 and len(t) >= 3 and not any(t.values()), (read.__name__, t)
+    assert every_analysis(m, b, rows) == first                                       # (e)
+    assert live(m) > idle
+    t = b.read_timing_register()
+    assert t["regions"] > 0 and t["solve_ms"] > 0.0
+    m._lib.check(lib.mc_voxel_release(b.handle), "voxel_release")
+    assert live(m) == idle
+    destroy_only(m, b)
+    assert live(m) == start
