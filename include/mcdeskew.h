@@ -688,6 +688,35 @@ int mc_voxel_register_f64(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t
  * *launches = timed regions */
 int mc_timing_read_register(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 
+/* ---- every frame of a batch registered against the voxel cloud in one call (csrc/register.hpp k_rg_frames_*) ------
+ * F independent registrations advanced together.  The contract: for every non-empty frame f, every output of frame
+ * f is bit for bit what mc_voxel_register_batch(ctx, src, f, params with init = inits[f], ...) returns.  A source
+ * point's index is its place within its frame, so frame f has its own tree over the power of two >= max(N_f, 256)
+ * leaves, its own pair count, its own Cholesky step and its own stop; nothing couples the frames but the cloud and
+ * its normals, which are computed once per call.  A frame that has ended (converged, max_iterations, too_few_pairs,
+ * singular) is not touched again while the others go on: its pose, history rows, pairs and iterations are those of
+ * its last evaluated iteration.
+ * inits: F x 16, one row-major 4 x 4 per frame, or NULL: params->init for every frame.  transformations: F x 16.
+ * history: (F, max_iterations, 8), frame f's rows as above, the rows past its iterations +0.0.  stats: (F, 4) =
+ * pairs, iterations, status, N_f per frame; status 4 (empty): a frame without points, which is no error: its
+ * transformation is its init and its pairs and iterations are 0.  A batch without any point is no error either.
+ * Per iteration: one launch over the points of the live frames (frame f owns its tree's first level of workgroups,
+ * found through a block map; correspond and leaves in one kernel), one launch per further tree level over all the
+ * frames of more than 32 768 points, one launch of a workgroup per frame for the last fewer than 256 partials, the
+ * step and the frame's record, then one synchronisation and one word copied: the frames still live.  Poses, stats
+ * and history are copied once, at the end.  The scratch is the voxel state's (36 B per voxel, 224 B per 256 source
+ * points of every frame's padded tree, 64 B per history row, 184 B per frame) and is not reallocated by an
+ * iteration.  The result is the same bits on every run.
+ * MC_ERR_INVALID before any launch: what mc_voxel_register_batch refuses of ctx, params and the batch (every matrix
+ * of inits held to the rule of init, the message naming the frame), a NULL output, and F x max_iterations > 2^22
+ * history rows (256 MB: lower max_iterations).  No successful build: MC_ERR_STATE. */
+int mc_voxel_register_frames(mc_ctx* ctx, const mc_batch* src, const mc_register_params* params, const double* inits,
+                             double* transformations, double* history, int64_t* stats);
+/* event time (ms) of the phases since the last read: ms_phase[4] = normals (once per call), step (correspond,
+ * leaves and the first tree level of every live frame), tree (the further levels), solve (the last levels, the step
+ * and the records, on the device); *launches = timed regions */
+int mc_timing_read_register_frames(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

@@ -33,7 +33,9 @@ Drop-in surface (reference file:line in each docstring):
                          VoxelCloud.select(mask) -> Batch, the cloud cut by a mask on the device;
                          VoxelCloud.nearest(src, max_distance, transform, frame) -> VoxelNearest and
                          VoxelCloud.register(src, max_distance, init, ...) -> VoxelRegistration, a scan registered
-                         against the cloud by point-to-plane ICP, the whole iteration history the same on every run
+                         against the cloud by point-to-plane ICP, the whole iteration history the same on every run;
+                         VoxelCloud.register_frames(batch, max_distance, init, ...) -> VoxelFrameRegistrations, every
+                         frame of a batch registered on its own in one call, row f bit for bit register(..., frame=f)
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
 from . import _lib, codecs, config, coords, csim_export, dist, ingest, las, raymarch, runtime, trajectory, voxel  # noqa: F401
@@ -48,7 +50,7 @@ from .config import default_config, validate_config  # noqa: F401
 from .raymarch import LiDARSimulator  # noqa: F401
 from .runtime import Batch, Context, default_context  # noqa: F401
 from .simulator import LiDARMotionSimulator  # noqa: F401
-from .voxel import (VoxelCloud, VoxelClusters, VoxelNearest, VoxelNormals, VoxelPlane, VoxelRegistration,  # noqa: F401
-                    voxel_downsample)  # noqa: F401
+from .voxel import (VoxelCloud, VoxelClusters, VoxelFrameRegistrations, VoxelNearest, VoxelNormals, VoxelPlane,  # noqa: F401
+                    VoxelRegistration, voxel_downsample)  # noqa: F401
 
 __version__ = "0.1.0"

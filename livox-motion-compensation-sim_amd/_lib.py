@@ -159,6 +159,9 @@ _SIGS = {
     "mc_voxel_register_batch": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, _pd, _pd, _pi64]),
     "mc_voxel_register_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, _pd, _pd, _pi64]),
     "mc_timing_read_register": (c_int, [c_void_p, _pd, _pi64]),
+    # every frame of a batch registered in one call (inits: F x 16 or NULL)
+    "mc_voxel_register_frames": (c_int, [c_void_p, c_void_p, c_void_p, _pd, _pd, _pd, _pi64]),
+    "mc_timing_read_register_frames": (c_int, [c_void_p, _pd, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

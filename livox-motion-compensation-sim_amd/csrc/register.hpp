@@ -9,6 +9,17 @@
 //               leaves, and the first level of the tree over the point index (plane_block_tree of plane.hpp);
 //               the pairs are counted with an integer atomic per wave
 //   tree        the further levels: k_pl_tree<kRegSums> of plane.hpp
+//
+// The frames of a batch registered together (mc_voxel_register_frames): every frame a source of its own with its own
+// pose, tree, pair count and stop, all of them advanced by one launch sequence per iteration; a workgroup whose frame
+// has ended returns at once, so an ended frame is not written again.
+//   frames step   frame f owns plane_leaves(n_f) / 256 consecutive workgroups (the block map boff, searched in scalar
+//                 registers); one lane per point: correspond and leaves in one, the point moved once and no ids array;
+//                 the first level of the frame's tree.  Workgroups past the frame's last point leave their partials
+//                 as the call zeroed them
+//   frames tree   a further level of every frame that has one, one launch per level (a block map per level)
+//   frames solve  one workgroup per frame: the last fewer than 256 partials of the 28 sums, one lane each, then one
+//                 lane's register_step, the history row and the frame's record; the frames still live are counted
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -108,6 +119,102 @@ __global__ __launch_bounds__(kVoxBlock) void k_rg_leaves(RegArgs a) {
   const uint32_t wave = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(pair));
   if ((threadIdx.x & 63) == 0 && wave) atomicAdd(a.pairs, (unsigned long long)wave);
   plane_block_tree<kRegSums>(x, a.out + blockIdx.x, gridDim.x);
+}
+
+static_assert(kRegBlock == kVoxBlock, "a workgroup is a node of the tree");
+
+struct RegFramesArgs {
+  const float* cols;          // the batch's blocked columns
+  int32_t C, F;
+  const int64_t* poff;        // (F + 1,) the frames' padded offsets
+  const int64_t* boff;        // (F + 1,) the block map of the launch
+  RegFrame* fr;               // (F,)
+  NormalsGrid g;
+  int64_t M;
+  double h, o[3];
+  NormalsQuery w;
+  const double* normals;
+  const int32_t* counts;
+  double* tree;               // every frame's levels (RegFrame::tree), zeroed once per call
+  int32_t level;              // k_rg_frames_tree: the level written (2: the second)
+  int32_t max_iterations;
+  double tol_rotation, tol_translation;
+  double* history;            // (F, max_iterations, kRegHistory), zeroed once per call
+  uint32_t* live;             // [0] += the frames that go on
+};
+
+__global__ __launch_bounds__(kVoxBlock) void k_rg_frames_step(RegFramesArgs a) {
+  const int64_t b = blockIdx.x;
+  const int32_t f = register_block_frame(a.boff, a.F, b);   // of blockIdx alone: wave-uniform
+  const RegFrame* fr = a.fr + f;
+  // the record through the scalar unit: nothing here but `count` is written while this kernel runs
+  if (ldu(&fr->status) != kRegGoOn) return;
+  const int64_t lb = b - a.boff[f], n = ldu(&fr->n);         // 0 <= lb < fr->blocks
+  if (lb * kVoxBlock >= n) return;                           // no point here: the partials stay +0.0
+  const RegPose T = ldu(&fr->T);
+  const int64_t i = lb * kVoxBlock + threadIdx.x;
+  double q[3] = {0.0, 0.0, 0.0}, c[3] = {0.0, 0.0, 0.0}, nn[3] = {0.0, 0.0, 0.0};
+  bool pair = false;
+  if (i < n) {
+    const float* src = a.cols + bidx(a.C, 0, a.poff[f] + i);   // i < n: inside frame f's padded span
+    const double p[3] = {(double)src[0], (double)src[kBlkPts], (double)src[2 * kBlkPts]};
+    register_move(T, p, q);
+    int32_t id = -1;
+    double d2;
+    if (a.M > 0) register_nearest(a.g, a.h, a.o, a.w, q, &id, &d2);
+    if (id >= 0 && a.counts[id] >= kNormalsMinNN) {            // 0 <= id < M: a voxel of the table
+      const double* cv = a.g.cent + (int64_t)kNormalsCent * id;
+      const double* nv = a.normals + 4 * (int64_t)id;
+      c[0] = cv[0]; c[1] = cv[1]; c[2] = cv[2];
+      nn[0] = nv[0]; nn[1] = nv[1]; nn[2] = nv[2];
+      pair = true;
+    }
+  }
+  double x[kRegSums];
+  register_leaf(pair, q, c, nn, x);
+  const uint32_t wave = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(pair));
+  if ((threadIdx.x & 63) == 0 && wave) atomicAdd(&a.fr[f].count, (unsigned long long)wave);
+  plane_block_tree<kRegSums>(x, a.tree + ldu(&fr->tree) + lb, ldu(&fr->blocks));
+}
+
+// level a.level >= 2 of every live frame that has it: k_pl_tree<kRegSums> on the frame's own levels
+__global__ __launch_bounds__(kVoxBlock) void k_rg_frames_tree(RegFramesArgs a) {
+  const int64_t b = blockIdx.x;
+  const int32_t f = register_block_frame(a.boff, a.F, b);
+  const RegFrame* fr = a.fr + f;
+  if (fr->status != kRegGoOn) return;
+  int64_t cnt;
+  const int64_t at = register_level(fr->blocks, a.level - 1, &cnt);   // the level read: cnt >= 256 partials per sum
+  const double* in = a.tree + fr->tree + at;
+  double* out = a.tree + fr->tree + at + (int64_t)kRegSums * cnt;
+  const int64_t lb = b - a.boff[f];                                   // < cnt / 256
+  const int64_t i = lb * kVoxBlock + threadIdx.x;
+  double x[kRegSums];
+#pragma unroll
+  for (int c = 0; c < kRegSums; ++c) x[c] = in[c * cnt + i];
+  plane_block_tree<kRegSums>(x, out + lb, cnt / kVoxBlock);
+}
+
+__global__ __launch_bounds__(kVoxBlock) void k_rg_frames_solve(RegFramesArgs a) {
+  __shared__ double top[kRegSums][kRegTopMax];
+  __shared__ double sums[kRegSums];
+  RegFrame* fr = a.fr + blockIdx.x;
+  if (fr->status != kRegGoOn) return;
+  const int32_t cnt = fr->top_n;                                      // 1 .. 128, a power of two
+  const double* in = a.tree + fr->top;
+  for (int k = threadIdx.x; k < kRegSums * cnt; k += kVoxBlock) top[k / cnt][k % cnt] = in[k];
+  __syncthreads();
+  if (threadIdx.x < kRegSums) sums[threadIdx.x] = register_tail(top[threadIdx.x], cnt);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    RegFrame r = *fr;
+    double s[kRegSums];
+    for (int c = 0; c < kRegSums; ++c) s[c] = sums[c];
+    const bool on = register_frame_end(&r, s, a.max_iterations, a.tol_rotation, a.tol_translation,
+                                       a.history + (int64_t)blockIdx.x * a.max_iterations * kRegHistory);
+    *fr = r;
+    if (on) atomicAdd(a.live, 1u);
+  }
 }
 
 }  // namespace mc

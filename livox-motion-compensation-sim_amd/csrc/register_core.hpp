@@ -1,7 +1,7 @@
 // register_core.hpp — the scalar core of the point-to-plane registration of a source against the voxel cloud
 // (register.hpp), on plain values so the same text compiles for the device and for the host
-// (tests/host/register_host.cpp includes it; built with g++ -ffp-contract=off).  A core header (DESIGN.md
-// "Core headers"); needs no stand-in.  No HIP include.
+// (tests/host/register_host.cpp and register_frames_host.cpp include it; built with g++ -ffp-contract=off).  A core
+// header (DESIGN.md "Core headers"); needs no stand-in.  No HIP include.
 //
 // Defined op for op (include/mcdeskew.h "registration against the voxel cloud"); p a source point, (R, t) the pose:
 //   move      q = R p + t, each component ((R0 x + R1 y) + R2 z) + t
@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "normals_core.hpp"
+#include "plane_core.hpp"
 
 namespace mc {
 
@@ -304,6 +305,97 @@ MC_CORE_HD int register_step(const double sums[kRegSums], int64_t pairs, double 
   for (int i = 0; i < 6; ++i) row[2 + i] = x[i];
   register_update(T, x);
   return register_small(x, tol_rotation, tol_translation) ? kRegConverged : kRegGoOn;
+}
+
+// ---- the frames of a batch registered together (register.hpp k_rg_frames_*; mc_voxel_register_frames) -------------
+// Frame f is a source of its own: its points indexed within the frame, its own tree over plane_leaves(n) leaves, its
+// own pair count, step and stop; nothing couples the frames.  A frame that has ended is not touched again.
+constexpr int kRegEmpty = 4;          // the status of a frame without points (after the four of a registration)
+constexpr int kRegBlock = (int)kPlaneLeavesMin;   // leaves per workgroup of the first level and per node of every further one
+constexpr int kRegTopMax = kRegBlock / 2;   // a frame's last level holds fewer than 256 partials per sum: <= 128
+
+struct RegFrame {
+  RegPose T;
+  unsigned long long count;   // the pairs of the iteration under way (the step kernel adds, the solve takes and zeroes)
+  int64_t pairs;              // of the last evaluated iteration
+  int64_t n;                  // points
+  int64_t blocks;             // first-level partials per sum: plane_leaves(n) / 256; 0 for an empty frame
+  int64_t tree;               // where the frame's levels start in the tree scratch (words), back to back as tree_words
+  int64_t top;                // where its last level starts
+  int32_t top_n;              // partials per sum there: < 256
+  int32_t status;             // kRegGoOn while live
+  int32_t iterations;
+  int32_t pad_;
+};
+
+// The block map: off[0 .. F] a prefix of the frames' block counts, b in [0, off[F]) -> the frame that owns block b,
+// the last one starting at or before it (a frame without blocks starts where the next begins and owns none)
+MC_CORE_HD int32_t register_block_frame(const int64_t* off, int32_t F, int64_t b) {
+  int32_t lo = 0, hi = F - 1;
+  while (lo < hi) {
+    const int32_t mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// Where a frame of `blocks` first-level partials keeps level `level` (1: the first) relative to its `tree`, and the
+// partials per sum there; a level has a successor while it holds 256 or more
+MC_CORE_HD int64_t register_level(int64_t blocks, int level, int64_t* cnt) {
+  int64_t at = 0, n = blocks;
+  for (int l = 1; l < level; ++l) {
+    at += (int64_t)kRegSums * n;
+    n /= kRegBlock;
+  }
+  *cnt = n;
+  return at;
+}
+
+// the record of a frame of n points from the pose T whose levels start at word `tree`: -> the words they take
+MC_CORE_HD int64_t register_frame_init(RegFrame* fr, const RegPose& T, int64_t n, int64_t tree) {
+  fr->T = T;
+  fr->count = 0;
+  fr->pairs = 0;
+  fr->n = n;
+  fr->tree = tree;
+  fr->iterations = 0;
+  fr->pad_ = 0;
+  if (n == 0) {
+    fr->blocks = 0;
+    fr->top = tree;
+    fr->top_n = 0;
+    fr->status = kRegEmpty;
+    return 0;
+  }
+  fr->blocks = plane_leaves(n) / kRegBlock;
+  int64_t cnt = fr->blocks, at = 0;
+  while (cnt >= kRegBlock) {
+    at += (int64_t)kRegSums * cnt;
+    cnt /= kRegBlock;
+  }
+  fr->top = tree + at;
+  fr->top_n = (int32_t)cnt;
+  fr->status = kRegGoOn;
+  return at + (int64_t)kRegSums * cnt;
+}
+
+// the last levels of one sum: top[0 .. cnt) (cnt a power of two below 256) by plane_tree's pairing, in place
+MC_CORE_HD double register_tail(double* top, int64_t cnt) { return plane_tree(top, cnt, 1); }
+
+// The end of a live frame's iteration from its 28 sums: register_step with the pairs counted, the history row
+// rows[iterations], and the record for the next iteration (the counter zeroed).  max_iterations reached without
+// another ending: kRegMaxIter.  -> the frame is still live
+MC_CORE_HD bool register_frame_end(RegFrame* fr, const double sums[kRegSums], int32_t max_iterations, double tol_rotation,
+                                   double tol_translation, double* rows) {
+  const int64_t pairs = (int64_t)fr->count;
+  int status = register_step(sums, pairs, tol_rotation, tol_translation, &fr->T, rows + (int64_t)kRegHistory * fr->iterations);
+  fr->pairs = pairs;
+  fr->count = 0;
+  fr->iterations += 1;
+  if (status == kRegGoOn && fr->iterations >= max_iterations) status = kRegMaxIter;
+  fr->status = status;
+  return status == kRegGoOn;
 }
 
 // what a pose argument must hold: finite entries and |R^T R - I| <= 1e-6 in every entry

@@ -6,7 +6,8 @@
 // normals of the built cloud (mc_voxel_normals; kernels in normals.hpp) and its density clustering
 // (mc_voxel_clusters; kernels in cluster.hpp) read that state and keep theirs in it; so do its plane segmentation
 // and the selection of a subset into a batch (mc_voxel_plane, mc_voxel_emit_selected; kernels in plane.hpp), and the
-// registration of a source against the cloud (mc_voxel_nearest_*, mc_voxel_register_*; kernels in register.hpp).
+// registration of a source against the cloud (mc_voxel_nearest_*, mc_voxel_register_*, and every frame of a batch
+// on its own in one call, mc_voxel_register_frames; kernels in register.hpp).
 #include "../../include/mcdeskew.h"
 #include "voxel.hpp"
 #include "normals.hpp"
@@ -34,13 +35,15 @@ enum {
   kClDensity, kClUnion, kClLabel, kClNumber, kClStats,
   kPlCompact, kPlSample, kPlScore, kPlMask, kPlMoments, kPlSelect,
   kRgNormals, kRgCorrespond, kRgLeaves, kRgTree,   // the register's fifth phase, the solve, is the host's: no events
+  kRfNormals, kRfStep, kRfTree, kRfSolve,
   kAllPhases
 };
 struct PhaseRange { int first, count; };
 constexpr PhaseRange kFilterPhases = {kInsert, 4}, kNormalsPhases = {kNrmCentroids, 3}, kClPhases = {kClDensity, kClusterPhases},
-                     kPlanePhases = {kPlCompact, 6}, kRegPhases = {kRgNormals, 4};
+                     kPlanePhases = {kPlCompact, 6}, kRegPhases = {kRgNormals, 4}, kRegFramesPhases = {kRfNormals, 4};
 constexpr int kRgSolve = 4;   // its public index
-static_assert(kRegPhases.first + kRegPhases.count == kAllPhases && kClPhases.first + kClPhases.count == kPlCompact, "the ranges");
+static_assert(kRegPhases.first + kRegPhases.count == kRfNormals && kRegFramesPhases.first + kRegFramesPhases.count == kAllPhases &&
+              kClPhases.first + kClPhases.count == kPlCompact, "the ranges");
 
 struct VoxState : mcimpl::CtxExt {
   // table (a power of two of slots), per-point arrays (points / chunks), per-voxel records
@@ -83,6 +86,12 @@ struct VoxState : mcimpl::CtxExt {
   DevBuf<double> rg_normals, rg_tree;
   double rg_solve_ms = 0.0;
   int64_t rg_solve_n = 0;
+  // the frames of a batch registered together: a record per frame, the block maps of the first level and of the two
+  // further ones, every frame's levels back to back, the history of every frame, and the frames still live
+  DevBuf<RegFrame> rf_frames;
+  DevBuf<int64_t> rf_map;
+  DevBuf<double> rf_tree, rf_history;
+  DevBuf<uint32_t> rf_live;
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
@@ -381,9 +390,9 @@ int plane_moments(mc_ctx* c, VoxState* s, const double p0[3], double sums[kPlane
 }
 
 // The normals of the live build (include/mcdeskew.h mc_voxel_normals) for `who`; for_register: the window and cap
-// phases are timed as the registration's normals phase, not as the normals' own
+// phases are timed as the registration's normals phase, not as the normals' own; as_phase >= 0: as that phase
 int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoint, double* d_normals, int32_t* d_counts,
-                double* d_cov, const char* who, bool for_register) {
+                double* d_cov, const char* who, bool for_register, int as_phase = -1) {
   CHECK_ARG(std::isfinite(radius) && radius > 0.0, "radius must be finite and > 0 (got %g)", radius);
   CHECK_ARG(max_nn == 0 || (max_nn >= kNormalsMinNN && max_nn <= kNormalsMaxNN),
             "max_nn must be 0 (no cap) or in %d..%d (got %d)", kNormalsMinNN, kNormalsMaxNN, max_nn);
@@ -401,8 +410,8 @@ int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoin
   if (int r = centroids(c, s)) return r;
   if (int r = ctx_reserve(c, s->capped, (size_t)M)) return r;
   if (!s->n_capped) if (int r = s->n_capped.alloc(1)) return r;
-  EventPairs* window = &s->ev[for_register ? kRgNormals : kNrmWindow];
-  EventPairs* cap = &s->ev[for_register ? kRgNormals : kNrmCap];
+  EventPairs* window = &s->ev[as_phase >= 0 ? as_phase : for_register ? kRgNormals : kNrmWindow];
+  EventPairs* cap = &s->ev[as_phase >= 0 ? as_phase : for_register ? kRgNormals : kNrmCap];
   NrmArgs a = {};
   a.g = grid_of(s);
   a.vslot = s->vslot;
@@ -590,6 +599,131 @@ int register_run(mc_ctx* c, const RegSrc& src, const mc_register_params* p, doub
   stats[0] = pairs;
   stats[1] = it;
   stats[2] = status;
+  return MC_OK;
+}
+
+// ---- the frames of a batch registered together -----------------------------------------------------------------------
+constexpr int64_t kRegFramesHistoryRows = (int64_t)1 << 22;   // F x max_iterations at most: 256 MB of history
+constexpr int kRegFramesLevels = 3;                            // fewer than 2^31 points: 2^23 partials, 2^15, 2^7
+
+// Every frame of `in` registered on its own (include/mcdeskew.h mc_voxel_register_frames): per iteration the step
+// over every live frame's points, the further levels of the frames that have them, the solve of every live frame,
+// and one synchronisation with one word copied: the frames still live.  inits: F x 16, or null: p->init for all
+int register_frames_run(mc_ctx* c, const mc_batch* in, const mc_register_params* p, const double* inits, double* transformations,
+                        double* history, int64_t* stats, const char* who) {
+  VoxState* s;
+  if (int r = live_build(c, who, &s)) return r;
+  if (int r = reg_distance(s, p->max_distance)) return r;
+  CHECK_ARG(p->max_iterations >= 1 && p->max_iterations <= kRegMaxIterations, "max_iterations must be in 1..%d (got %d)",
+            kRegMaxIterations, p->max_iterations);
+  CHECK_ARG(std::isfinite(p->tol_rotation) && p->tol_rotation >= 0.0 && std::isfinite(p->tol_translation) &&
+                p->tol_translation >= 0.0,
+            "tol_rotation and tol_translation must be finite and >= 0 (got %g, %g)", p->tol_rotation, p->tol_translation);
+  const int32_t F = in->F;
+  CHECK_ARG((int64_t)F * p->max_iterations <= kRegFramesHistoryRows,
+            "%d frames x max_iterations %d is more than %lld history rows (256 MB): lower max_iterations", F, p->max_iterations,
+            (long long)kRegFramesHistoryRows);
+  // the records, the block maps of the levels and the words of the trees, on the host
+  std::vector<RegFrame> fr((size_t)F);
+  std::vector<int64_t> map((size_t)kRegFramesLevels * (F + 1), 0);
+  int64_t words = 0;
+  for (int32_t f = 0; f < F; ++f) {
+    const int64_t n = in->counts[f];
+    CHECK_ARG(n < ((int64_t)1 << 31), "frame %d: %lld points: a source takes fewer than 2^31", f, (long long)n);
+    RegPose T;
+    char name[48] = "init";
+    if (inits) std::snprintf(name, sizeof name, "init of frame %d", f);
+    if (int r = reg_pose(inits ? inits + 16 * (size_t)f : p->init, name, &T)) return r;
+    words += register_frame_init(&fr[f], T, n, words);
+    int64_t cnt = fr[f].blocks;
+    for (int l = 0; l < kRegFramesLevels; ++l) {
+      int64_t* off = map.data() + (size_t)l * (F + 1);
+      off[f + 1] = off[f] + cnt;
+      cnt = cnt >= kRegBlock ? cnt / kRegBlock : 0;     // the workgroups of the next level; none below 256 partials
+    }
+    stats[4 * f + 3] = n;
+  }
+  const int64_t* top_map = map.data();
+  CHECK_ARG(top_map[F] < ((int64_t)1 << 31), "%lld workgroups of 256 points: a launch takes fewer than 2^31", (long long)top_map[F]);
+  const int64_t M = s->M;
+  DeviceGuard g(c->device);
+  // the normals of the call, once for all frames
+  if (int r = ctx_reserve(c, s->rg_normals, 4 * (size_t)std::max<int64_t>(M, 1))) return r;
+  if (int r = ctx_reserve(c, s->rg_counts, (size_t)std::max<int64_t>(M, 1))) return r;
+  if (int r = normals_run(c, p->normals_radius, p->max_nn, nullptr, s->rg_normals, s->rg_counts, nullptr, who, true, kRfNormals)) return r;
+  const size_t rows = (size_t)F * p->max_iterations;
+  int32_t live = 0;
+  for (int32_t f = 0; f < F; ++f) live += fr[f].status == kRegGoOn;
+  if (live > 0) {
+    if (int r = ctx_reserve(c, s->rf_frames, (size_t)F)) return r;
+    if (int r = ctx_reserve(c, s->rf_map, map.size())) return r;
+    if (int r = ctx_reserve(c, s->rf_tree, (size_t)words)) return r;
+    if (int r = ctx_reserve(c, s->rf_history, (size_t)kRegHistory * rows)) return r;
+    if (!s->rf_live) if (int r = s->rf_live.alloc(1)) return r;
+    RegFramesArgs a = {};
+    a.cols = in->d_cols; a.C = in->C; a.F = F;
+    a.poff = in->d_poff;
+    a.fr = s->rf_frames;
+    a.M = M;
+    a.h = s->h;
+    std::copy_n(s->o, 3, a.o);
+    a.w = query_of(s, p->max_distance, 0);
+    if (M > 0) {
+      if (int r = centroids(c, s)) return r;
+      a.g = grid_of(s);
+    }
+    a.normals = s->rg_normals; a.counts = s->rg_counts;
+    a.tree = s->rf_tree;
+    a.max_iterations = p->max_iterations;
+    a.tol_rotation = p->tol_rotation; a.tol_translation = p->tol_translation;
+    a.history = s->rf_history;
+    a.live = s->rf_live;
+    HIPCHK(hipMemcpyAsync(s->rf_frames, fr.data(), fr.size() * sizeof(RegFrame), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(s->rf_map, map.data(), map.size() * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(s->rf_tree, 0, (size_t)words * sizeof(double), c->stream));
+    HIPCHK(hipMemsetAsync(s->rf_history, 0, (size_t)kRegHistory * rows * sizeof(double), c->stream));
+    for (int32_t it = 0; live > 0 && it < p->max_iterations; ++it) {
+      {
+        TimedRegion tr(c, &s->ev[kRfStep], c->stream);
+        HIPCHK(hipMemsetAsync(s->rf_live, 0, sizeof(uint32_t), c->stream));
+        a.boff = s->rf_map.get();
+        hipLaunchKernelGGL(k_rg_frames_step, dim3((uint32_t)top_map[F]), dim3(kVoxBlock), 0, c->stream, a);
+      }
+      for (int l = 1; l < kRegFramesLevels; ++l) {
+        const int64_t blocks = map[(size_t)l * (F + 1) + F];
+        if (blocks == 0) break;
+        TimedRegion tr(c, &s->ev[kRfTree], c->stream);
+        a.boff = s->rf_map.get() + (size_t)l * (F + 1);
+        a.level = l + 1;
+        hipLaunchKernelGGL(k_rg_frames_tree, dim3((uint32_t)blocks), dim3(kVoxBlock), 0, c->stream, a);
+      }
+      {
+        TimedRegion tr(c, &s->ev[kRfSolve], c->stream);
+        hipLaunchKernelGGL(k_rg_frames_solve, dim3((uint32_t)F), dim3(kVoxBlock), 0, c->stream, a);
+      }
+      HIPCHK(hipGetLastError());
+      // the iteration's one synchronisation and its one word
+      uint32_t on = 0;
+      if (int r = copy_back(c, &on, s->rf_live, sizeof on)) return r;
+      if ((int64_t)on > live) return fail(MC_ERR_STATE, "voxel register frames: %u live frames of %d", on, live);
+      live = (int32_t)on;
+    }
+    // the call's one copy of the records and of the history
+    HIPCHK(hipMemcpyAsync(fr.data(), s->rf_frames, fr.size() * sizeof(RegFrame), hipMemcpyDeviceToHost, c->stream));
+    if (int r = copy_back(c, history, s->rf_history, (size_t)kRegHistory * rows * sizeof(double))) return r;
+  } else {
+    std::fill_n(history, (size_t)kRegHistory * rows, 0.0);
+  }
+  for (int32_t f = 0; f < F; ++f) {
+    const RegFrame& r = fr[f];
+    if (r.pairs < 0 || r.pairs > r.n || r.iterations < 0 || r.iterations > p->max_iterations || r.status < 0 || r.status > kRegEmpty)
+      return fail(MC_ERR_STATE, "voxel register frames: frame %d ended with %lld pairs of %lld points, %d iterations, status %d", f,
+                  (long long)r.pairs, (long long)r.n, r.iterations, r.status);
+    pose_to_rows(r.T, transformations + 16 * (size_t)f);
+    stats[4 * f + 0] = r.pairs;
+    stats[4 * f + 1] = r.iterations;
+    stats[4 * f + 2] = r.status;
+  }
   return MC_OK;
 }
 
@@ -942,6 +1076,19 @@ int mc_voxel_register_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n
   RegSrc s;
   if (int r = reg_source_rows(d_rows, ld, n, &s)) return r;
   return register_run<false>(c, s, p, transformation, history, stats, "mc_voxel_register_f64");
+}
+
+int mc_voxel_register_frames(mc_ctx* c, const mc_batch* src, const mc_register_params* p, const double* inits,
+                             double* transformations, double* history, int64_t* stats) {
+  CHECK_ARG(c && src && p && transformations && history && stats, "NULL argument");
+  CHECK_ARG(src->ctx == c, "batch belongs to another context");
+  for (int32_t f = 0; f < src->F; ++f) register_clear(transformations + 16 * (size_t)f, stats + 4 * (size_t)f);
+  return register_frames_run(c, src, p, inits, transformations, history, stats, "mc_voxel_register_frames");
+}
+
+int mc_timing_read_register_frames(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  return read_phases(c, kRegFramesPhases, ms_phase, launches);
 }
 
 int mc_timing_read_register(mc_ctx* c, double* ms_phase, int64_t* launches) {

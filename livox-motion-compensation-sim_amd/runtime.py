@@ -391,6 +391,12 @@ class Context:
         (mc_timing_read_register); the solve is the host's, by its clock."""
         return self._read_phases("timing_read_register", ("normals_ms", "correspond_ms", "leaves_ms", "tree_ms", "solve_ms"))
 
+    def read_timing_register_frames(self) -> dict:
+        """Event time (ms) of the phases of VoxelCloud.register_frames since the last read
+        (mc_timing_read_register_frames): the normals once per call, then per iteration the step over the live
+        frames' points, the further tree levels and the solve, all on the device."""
+        return self._read_phases("timing_read_register_frames", ("normals_ms", "step_ms", "tree_ms", "solve_ms"))
+
     def device_buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)
 

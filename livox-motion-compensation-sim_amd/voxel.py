@@ -11,6 +11,8 @@ of a drive are accumulated into one cloud and most points re-observe the same su
   VoxelCloud.nearest(src, max_distance, transform=None, frame=None)  -> VoxelNearest
   VoxelCloud.register(src, max_distance, init=None, max_iterations=30, normals_radius=None, max_nn=30,
                       tol_rotation=1e-6, tol_translation=1e-6, frame=None)  -> VoxelRegistration
+  VoxelCloud.register_frames(batch, max_distance, init=None, max_iterations=30, normals_radius=None, max_nn=30,
+                             tol_rotation=1e-6, tol_translation=1e-6)  -> VoxelFrameRegistrations
 
 One output point per occupied voxel: the mean of the voxel's points and of their intensities.  The
 per-voxel sums are integers (the coordinate inside its voxel in 2^-32 voxel units, the intensity in
@@ -113,6 +115,17 @@ Refused with ValueError: max_distance not finite and > 0 or beyond 4 h, a pose t
 with last row (0, 0, 0, 1) and |R^T R - I| <= 1e-6 in every entry, an empty source, a batch of another context, a
 frame outside the batch, max_iterations not an integer in 1..2^16, a tolerance that is not finite and >= 0, and what
 ``normals`` refuses of normals_radius (None: 2 h) and max_nn.
+
+Every frame of a batch (csrc/register.hpp ``k_rg_frames_*``; ``mc_voxel_register_frames``): ``register_frames`` is one
+correction per frame in one call.  For every non-empty frame f, every field of result f is bit for bit what
+``register(batch, max_distance, frame=f, init=init_f, ...)`` returns: a point's index is its place within its frame, so
+each frame has its own tree, pair count, Cholesky step and stop, and nothing couples the frames but the cloud and its
+normals, computed once per call.  All frames advance together, one launch sequence and one synchronisation per
+iteration; a frame that has ended keeps the pose, history, pairs and iterations of its last evaluated iteration while
+the others go on.  An empty frame is not an error: status "empty", its init as transformation, zeros elsewhere.
+``ctx.transform_affine(batch, mats=r.transformations)`` is the corrected batch.  Refused with ValueError: what
+``register`` refuses, a source that is not a Batch of this context, an init that is not None, one 4 x 4 or (F, 4, 4)
+(the message names the frame), and F x max_iterations above 2^22 history rows.
 """
 from __future__ import annotations
 
@@ -281,6 +294,23 @@ class VoxelRegistration(NamedTuple):
 
 REGISTER_STATUS = ("converged", "max_iterations", "too_few_pairs", "singular")
 MAX_REGISTER_ITERATIONS = 2 ** 16
+FRAME_REGISTER_STATUS = REGISTER_STATUS + ("empty",)
+MAX_FRAME_HISTORY_ROWS = 2 ** 22      # F x max_iterations: 256 MB of history
+
+
+class VoxelFrameRegistrations(NamedTuple):
+    """What :meth:`VoxelCloud.register_frames` returns, rows in frame order; row f is ``register(..., frame=f)``."""
+    transformations: np.ndarray     # (F, 4, 4) float64, source to cloud; an empty frame: its init
+    fitness: np.ndarray             # (F,) float64 pairs / N_f of the frame's last evaluated iteration; empty: 0
+    inlier_rmse: np.ndarray         # (F,) float64 sqrt(sum r^2 / pairs) of the same iteration; no pairs: 0
+    pairs: np.ndarray               # (F,) int64
+    iterations: np.ndarray          # (F,) int32 iterations evaluated
+    status: np.ndarray              # (F,) int8 indices into FRAME_REGISTER_STATUS
+    history: np.ndarray             # (F, max(iterations), 8) float64; rows past a frame's iterations are +0.0
+
+    @property
+    def status_names(self) -> tuple:
+        return tuple(FRAME_REGISTER_STATUS[int(k)] for k in self.status)
 
 
 def _distance_arg(max_distance, h):
@@ -329,6 +359,24 @@ def _source_arg(ctx, src, frame):
     if a.shape[0] > MAX_POINTS:
         raise ValueError(f"{a.shape[0]} points: a source takes fewer than 2^31")
     return None, -1, np.ascontiguousarray(a, dtype=np.float64), a.shape[0]
+
+
+def _frame_poses_arg(init, F):
+    """(F, 4, 4) float64 from None, one 4 x 4 for all frames or one per frame, each held to _pose_arg's rules."""
+    if init is None:
+        return np.tile(np.eye(4), (F, 1, 1))
+    if isinstance(init, np.ndarray):
+        per_frame = init.ndim == 3
+    else:               # a sequence of matrices, which may be ragged: never made into one array
+        per_frame = isinstance(init, (list, tuple)) and len(init) > 0 and np.ndim(init[0]) == 2
+    if per_frame:
+        if len(init) != F:
+            raise ValueError(f"init must be None, one 4 x 4 matrix or one per frame ({F}, 4, 4); got {len(init)} matrices")
+        out = np.empty((F, 4, 4))
+        for f in range(F):
+            out[f] = _pose_arg(init[f], f"init of frame {f}")
+        return out
+    return np.tile(_pose_arg(init, "init"), (F, 1, 1))
 
 
 def _register_args(max_iterations, tol_rotation, tol_translation):
@@ -538,6 +586,45 @@ class VoxelCloud:
         history = np.ascontiguousarray(history[:done])
         rmse = math.sqrt(float(history[-1, 1]) / pairs) if pairs else 0.0
         return VoxelRegistration(out, pairs / n, rmse, pairs, done, REGISTER_STATUS[int(stats[2])], history)
+
+    def register_frames(self, batch, max_distance, init=None, max_iterations: int = 30, normals_radius=None, max_nn: int = 30,
+                        tol_rotation: float = 1e-6, tol_translation: float = 1e-6) -> "VoxelFrameRegistrations":
+        """:meth:`register` of every frame of ``batch`` on its own, in one call: row f of the result is bit for bit
+        ``register(batch, max_distance, frame=f, init=init_f, ...)`` (module docstring; include/mcdeskew.h
+        ``mc_voxel_register_frames``).  ``init``: None, one 4 x 4 for all frames, or (F, 4, 4).  The normals are
+        computed once; the frames advance together, and one that has ended is left as it ended.  An empty frame
+        gets the status "empty".  ``ctx.transform_affine(batch, mats=result.transformations)`` applies the result."""
+        d = _distance_arg(max_distance, self._h)
+        if not isinstance(batch, Batch):
+            raise ValueError("register_frames takes a Batch: one registration per frame (rows have no frames)")
+        if batch.ctx is not self.ctx:
+            raise ValueError("the batch belongs to another context")
+        F = batch.n_frames
+        T = _frame_poses_arg(init, F)
+        iters, tol_r, tol_t = _register_args(max_iterations, tol_rotation, tol_translation)
+        if F * iters > MAX_FRAME_HISTORY_ROWS:
+            raise ValueError(f"{F} frames x max_iterations {iters} is more than 2^22 history rows (256 MB): lower max_iterations")
+        if normals_radius is None:
+            if self._h is None:
+                raise ValueError("normals_radius=None means twice the voxel size, which this cloud does not know")
+            normals_radius = 2 * self._h
+        radius, nn, _ = _normals_args(normals_radius, max_nn, None, self._h)
+        counts = np.asarray(batch.counts, np.int64).reshape(-1)
+        if len(counts) and int(counts.max()) > MAX_POINTS:
+            raise ValueError(f"{int(counts.max())} points in a frame: a source takes fewer than 2^31")
+        self._live()
+        ctx = self.ctx
+        par = RegisterParams(d, radius, tol_r, tol_t, (c_double * 16)(*np.eye(4).reshape(-1).tolist()), nn, iters)
+        out, history, stats = np.zeros((F, 4, 4)), np.zeros((F, iters, 8)), np.zeros((F, 4), np.int64)
+        check(ctx.lib.mc_voxel_register_frames(ctx.handle, batch.handle, ctypes.byref(par), ptr(T, c_double), ptr(out, c_double),
+                                               ptr(history, c_double), ptr(stats, c_int64)), "register_frames")
+        pairs, done = stats[:, 0].copy(), stats[:, 1].astype(np.int32)
+        last = history[np.arange(F), np.maximum(done - 1, 0), 1]
+        # per frame what register computes: pairs / N_f and math.sqrt(sum r^2 / pairs), both on Python floats
+        fitness = np.array([int(p) / int(n) if n else 0.0 for p, n in zip(pairs, counts)], np.float64)
+        rmse = np.array([math.sqrt(float(s) / int(p)) if p else 0.0 for s, p in zip(last, pairs)], np.float64)
+        history = np.ascontiguousarray(history[:, :int(done.max()) if F else 0])
+        return VoxelFrameRegistrations(out, fitness, rmse, pairs, done, stats[:, 2].astype(np.int8), history)
 
     def close(self):
         """Give the filter's device scratch back (a later call allocates it again)."""
