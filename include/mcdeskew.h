@@ -480,6 +480,57 @@ int mc_voxel_emit_f64(mc_ctx* ctx, double* d_rows, int32_t* d_counts, int32_t* d
 int mc_timing_read_voxel(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 int mc_voxel_release(mc_ctx* ctx);
 
+/* ---- growing a voxel cloud: inserting points and merging exact sums --------------------------------
+ * The definition: after any sequence of mc_voxel_insert_* / mc_voxel_merge_sums calls on a live build, the
+ * cloud is BIT FOR BIT the cloud mc_voxel_build_* returns for the concatenation of the sources in call
+ * order.  The per-voxel record is integer, so adding records is exact and independent of order, and
+ * voxels are numbered by first appearance, so later voxels follow earlier ones.
+ * An item is a point, or a voxel record (key, n, S[3], SI) that stands for n points of that voxel
+ * arriving together.  Items are indexed in source order: frame-major, then the index within the frame,
+ * for a batch (padding slots are not points); the row for rows; the record index for records.  For a
+ * call on a cloud of M voxels and N points:
+ *   1. every item is quantised, or checked, with the cloud's own voxel size and origin (no grid arguments)
+ *   2. an item whose key the cloud holds adds into that voxel's record; a voxel's id never changes:
+ *      ids 0 .. M-1 keep their keys and their order
+ *   3. keys new to the cloud become voxels M, M+1, ... in order of the lowest item index that holds them
+ *      (a key may occur in any number of records of one merge); *n_new is their number
+ *   4. N grows by the points of the call (the sum of n for records).  A call that would make N >= 2^31 is
+ *      refused: the uint32 count, the int32 emit and |S| < 2^63 stay safe
+ *   5. a refused call changes nothing: a point the build refuses, a record with n < 1, a key outside
+ *      [-2^20, 2^20), S[c] outside 0 .. n * 2^32 or |SI| > n * 2^32, or the 2^31 limit is MC_ERR_INVALID,
+ *      naming the lowest refused item (*bad_frame / *bad_index, *bad_row, *bad_record; -1 when none, as
+ *      for the limit); afterwards the cloud is live and every emit is bit-equal to what it was.  (A failure that
+ *      is no refusal, MC_ERR_NOMEM or MC_ERR_HIP once the table has been touched, leaves no live build.)
+ *   6. the centroids, normals and clustering derived from the cloud are invalidated as by a new build:
+ *      the next analysis sees the grown cloud
+ * The build of an empty source (n = 0) is a valid target: the way to start a map from nothing.  An empty
+ * call is MC_OK and changes nothing.  Without a live build: MC_ERR_STATE.  The cost is that of the call's
+ * items (one pass that validates, one that inserts, the rank scan, one that accumulates; two
+ * synchronisations), apart from growth: the table stays at most half full for the worst case of every
+ * item bringing a new key, so M + items > slots / 2 makes a table of the power of two >= 2 (M + items)
+ * slots and re-inserts the M keys; the per-voxel records grow geometrically, their contents copied.
+ * Outputs never depend on the table's size. */
+int mc_voxel_insert_batch(mc_ctx* ctx, const mc_batch* in, int64_t* n_new, int32_t* bad_frame, int64_t* bad_index);
+/* d_rows: device (n, ld) float64 rows x, y, z, intensity, ...; the definition above */
+int mc_voxel_insert_f64(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t n, int64_t* n_new, int64_t* bad_row);
+/* The raw sums of the live build, queued: d_sums (M, 4) int64 Sx, Sy, Sz, SI in the cloud's order.  With the
+ * d_keys and d_counts of mc_voxel_emit_f64 they are the cloud's records: what mc_voxel_merge_sums takes, and by
+ * the definition above merging them into a cloud of the same grid equals inserting the points they stand for. */
+int mc_voxel_emit_sums(mc_ctx* ctx, int64_t* d_sums);
+/* m records as items (the definition above): device d_keys (m, 3) int32, d_counts (m,) int32, d_sums (m, 4)
+ * int64.  The records must come from the cloud's own grid (voxel size and origin, bit for bit): the caller's
+ * to check, the keys carry no grid. */
+int mc_voxel_merge_sums(mc_ctx* ctx, const int32_t* d_keys, const int32_t* d_counts, const int64_t* d_sums, int64_t m,
+                        int64_t* n_new, int64_t* bad_record);
+/* N of the definition above: the points the live build holds.  Host state; needs no synchronisation. */
+int mc_voxel_points(mc_ctx* ctx, int64_t* n_points);
+/* For tests of the growth rule (either may be NULL): the slots of the live build's table (0: the build of an
+ * empty source has none yet) and the times an insert or a merge has made a new table since the build. */
+int mc_voxel_table(mc_ctx* ctx, int64_t* slots, int64_t* growths);
+/* event time (ms) of the phases of the inserts and merges since the last read: ms_phase[4] = validate,
+ * insert (with the table's growth), rank, accumulate; *launches = timed regions */
+int mc_timing_read_voxel_insert(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* ---- surface normals of the voxel cloud (csrc/normals_core.hpp, normals.hpp) ---------------------
  * The reference's viewer runs, on every cloud without normals (read_pointcloud.py:81-84),
  *   pcd.estimate_normals(search_param=KDTreeSearchParamHybrid(radius=0.1, max_nn=30))

@@ -24,6 +24,8 @@ Drop-in surface (reference file:line in each docstring):
                          or a Batch, read_las / read_las_batch back, records packed and unpacked on the device
   voxel                  build-added: voxel_downsample(batch or rows, voxel, origin) -> VoxelCloud, the voxel-grid
                          filter after a global deskew, with integer sums: bit-identical on every run;
+                         VoxelCloud.insert(batch or rows) / .state() -> VoxelSums / .merge(state): the cloud grown in
+                         place, bit for bit the one-shot cloud of the concatenated sources;
                          VoxelCloud.normals(radius, max_nn=30, viewpoint, covariance) -> VoxelNormals, the viewer's
                          estimate_normals (read_pointcloud.py:81-84) from the live build, a function of the voxel set;
                          VoxelCloud.clusters(eps, min_points=10, weighted) -> VoxelClusters, DBSCAN over the live build:
@@ -51,6 +53,6 @@ from .raymarch import LiDARSimulator  # noqa: F401
 from .runtime import Batch, Context, default_context  # noqa: F401
 from .simulator import LiDARMotionSimulator  # noqa: F401
 from .voxel import (VoxelCloud, VoxelClusters, VoxelFrameRegistrations, VoxelNearest, VoxelNormals, VoxelPlane,  # noqa: F401
-                    VoxelRegistration, voxel_downsample)  # noqa: F401
+                    VoxelRegistration, VoxelSums, voxel_downsample)  # noqa: F401
 
 __version__ = "0.1.0"

@@ -141,6 +141,14 @@ _SIGS = {
     "mc_voxel_emit_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "mc_timing_read_voxel": (c_int, [c_void_p, _pd, _pi64]),
     "mc_voxel_release": (c_int, [c_void_p]),
+    # growing the voxel cloud: points inserted, exact sums emitted and merged
+    "mc_voxel_insert_batch": (c_int, [c_void_p, c_void_p, _pi64, _pi32, _pi64]),
+    "mc_voxel_insert_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, _pi64, _pi64]),
+    "mc_voxel_emit_sums": (c_int, [c_void_p, c_void_p]),
+    "mc_voxel_merge_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, _pi64, _pi64]),
+    "mc_voxel_points": (c_int, [c_void_p, _pi64]),
+    "mc_voxel_table": (c_int, [c_void_p, _pi64, _pi64]),
+    "mc_timing_read_voxel_insert": (c_int, [c_void_p, _pd, _pi64]),
     # the surface normals of the voxel cloud
     "mc_voxel_normals": (c_int, [c_void_p, c_double, c_int32, _pd, c_void_p, c_void_p, c_void_p]),
     "mc_timing_read_normals": (c_int, [c_void_p, _pd, _pi64]),

@@ -18,6 +18,7 @@ enum hipError_t { hipSuccess = 0, hipErrorOutOfMemory = 2 };
 #include <stdint.h>
 #include <atomic>
 #include <cstddef>
+#include <utility>
 
 #include "../../include/mcdeskew.h"
 
@@ -111,6 +112,26 @@ struct DevBuf {
   T* p_ = nullptr;
   size_t cap_ = 0;
 };
+
+// Grow-only with the contents kept: at least n elements in buf, the first `keep` of them what they were.  A new
+// block (twice the old capacity when that is more than n, so a stream of small steps copies a record O(1) times;
+// exactly n when the larger block cannot be had), copy(dst, src, bytes) — which returns MC_OK only once the bytes
+// are there and nothing uses the old block any more — then a move-assign.  On any failure buf is what it was.
+template <typename T, int Where, typename Copy>
+int devbuf_grow_keep(DevBuf<T, Where>& buf, size_t keep, size_t n, Copy&& copy, bool* grew = nullptr) {
+  if (grew) *grew = false;
+  if (n <= buf.capacity()) return MC_OK;
+  if (keep > buf.capacity()) return fail(MC_ERR_STATE, "keeping %zu elements of a block of %zu", keep, buf.capacity());
+  DevBuf<T, Where> next;
+  const size_t twice = 2 * buf.capacity();
+  if (twice <= n || next.alloc(twice) != MC_OK)
+    if (int r = next.alloc(n)) return r;
+  if (keep > 0)
+    if (int r = copy(static_cast<void*>(next.get()), static_cast<const void*>(buf.get()), keep * sizeof(T))) return r;
+  buf = std::move(next);
+  if (grew) *grew = true;
+  return MC_OK;
+}
 
 // pinned host memory: the same body over hipHostMalloc / hipHostFree
 template <typename T, unsigned Flags>

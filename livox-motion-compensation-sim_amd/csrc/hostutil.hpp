@@ -34,6 +34,18 @@ static inline int ctx_reserve(mc_ctx* c, Buf& buf, size_t n, bool* grew = nullpt
   return buf.reserve(n, grew);
 }
 
+// At least n elements in buf, the first `keep` kept (devbuf.hpp devbuf_grow_keep: geometric growth): a device copy
+// on the main stream, which then drains, so the old block is idle when it goes back.  On failure buf is unchanged.
+template <typename Buf>
+static inline int ctx_reserve_keep(mc_ctx* c, Buf& buf, size_t keep, size_t n, bool* grew = nullptr) {
+  if (buf && n > buf.capacity() && keep == 0) (void)hipStreamSynchronize(c->stream);   // ctx_reserve's rule
+  return mcimpl::devbuf_grow_keep(buf, keep, n, [c](void* dst, const void* src, size_t bytes) -> int {
+    HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MC_OK;
+  }, grew);
+}
+
 static inline int ctx_stage(mc_ctx* c, size_t bytes, void** out) {
   if (int r = ctx_reserve(c, c->d_stage, bytes)) return r;
   *out = c->d_stage;

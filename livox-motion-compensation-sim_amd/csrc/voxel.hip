@@ -36,13 +36,17 @@ enum {
   kPlCompact, kPlSample, kPlScore, kPlMask, kPlMoments, kPlSelect,
   kRgNormals, kRgCorrespond, kRgLeaves, kRgTree,   // the register's fifth phase, the solve, is the host's: no events
   kRfNormals, kRfStep, kRfTree, kRfSolve,
+  kInsValidate, kInsInsert, kInsRank, kInsAccumulate,   // growing the live cloud; the insert's phase holds the table's growth
   kAllPhases
 };
 struct PhaseRange { int first, count; };
 constexpr PhaseRange kFilterPhases = {kInsert, 4}, kNormalsPhases = {kNrmCentroids, 3}, kClPhases = {kClDensity, kClusterPhases},
-                     kPlanePhases = {kPlCompact, 6}, kRegPhases = {kRgNormals, 4}, kRegFramesPhases = {kRfNormals, 4};
+                     kPlanePhases = {kPlCompact, 6}, kRegPhases = {kRgNormals, 4}, kRegFramesPhases = {kRfNormals, 4},
+                     kInsertPhases = {kInsValidate, 4};
 constexpr int kRgSolve = 4;   // its public index
-static_assert(kRegPhases.first + kRegPhases.count == kRfNormals && kRegFramesPhases.first + kRegFramesPhases.count == kAllPhases &&
+constexpr int kVoxMeta = 4;   // the words of VoxTable::meta
+static_assert(kRegPhases.first + kRegPhases.count == kRfNormals && kRegFramesPhases.first + kRegFramesPhases.count == kInsValidate &&
+              kInsertPhases.first + kInsertPhases.count == kAllPhases &&
               kClPhases.first + kClPhases.count == kPlCompact, "the ranges");
 
 struct VoxState : mcimpl::CtxExt {
@@ -58,9 +62,12 @@ struct VoxState : mcimpl::CtxExt {
   // the last build
   bool built = false;
   int64_t M = 0;
+  int64_t N = 0;        // the points the cloud holds: the build's, plus every insert's and merge's
   double h = 0.0, o[3] = {0, 0, 0};
+  int log2cap = 0;      // the table's slots (0: the build was of an empty source and left no table)
   int shift = 0;
   uint32_t mask = 0;
+  int64_t growths = 0;  // the times an insert or a merge made a new table since the build
   EventPairs ev[kAllPhases];   // by phase, of every stage
   // the normals of the last build: its centroids by voxel (written by the first mc_voxel_normals after the
   // build), the voxels the cap applies to and their number
@@ -203,6 +210,9 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   s->cent_current = false;
   s->cl_current = false;
   s->M = 0;
+  s->N = 0;
+  s->log2cap = 0;
+  s->growths = 0;
   s->h = src.h;
   std::copy_n(src.o, 3, s->o);
   if (n == 0) { s->built = true; return MC_OK; }
@@ -210,7 +220,7 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   while (((int64_t)1 << log2cap) < 2 * n) ++log2cap;   // n < 2^31: at most 2^32 slots
   const size_t cap = (size_t)1 << log2cap;
   const int64_t n_chunks = (n + kVoxChunk - 1) / kVoxChunk;
-  if (!s->meta) if (int r = s->meta.alloc(2)) return r;
+  if (!s->meta) if (int r = s->meta.alloc(kVoxMeta)) return r;
   if (int r = ctx_reserve(c, s->keys, cap)) return r;
   if (int r = ctx_reserve(c, s->first, cap)) return r;
   if (int r = ctx_reserve(c, s->vid, cap)) return r;
@@ -235,10 +245,10 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   }
   {
     TimedRegion tr(c, &s->ev[kRank], c->stream);
-    hipLaunchKernelGGL(k_vox_flag, cgrid, blk, 0, c->stream, t, n, s->flags, s->chunk);
+    hipLaunchKernelGGL(k_vox_flag<false>, cgrid, blk, 0, c->stream, t, n, s->flags, s->chunk);
     scan_counts(c, s->chunk, n_chunks, s->meta);
-    hipLaunchKernelGGL(k_vox_rank, cgrid, blk, 0, c->stream, t, n, (const uint8_t*)s->flags, (const uint32_t*)s->chunk,
-                       s->vslot);
+    hipLaunchKernelGGL(k_vox_rank<false>, cgrid, blk, 0, c->stream, t, n, (const uint8_t*)s->flags, (const uint32_t*)s->chunk,
+                       s->vslot, 0u);
   }
   HIPCHK(hipGetLastError());
   uint32_t meta[2] = {0, 0};
@@ -260,9 +270,150 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   s->M = M;
+  s->N = n;
+  s->log2cap = log2cap;
   s->built = true;
   *n_voxels = M;
   return MC_OK;
+}
+
+// ---- growing the live cloud -------------------------------------------------------------------------------------------
+// the view of the state's table the kernels take
+VoxTable table_of(const VoxState* s) {
+  VoxTable t;
+  t.keys = s->keys; t.first = s->first; t.vid = s->vid; t.slot = s->slot;
+  t.shift = s->shift;
+  t.mask = s->mask;
+  t.meta = s->meta;
+  return t;
+}
+
+// A fresh table of 2^log2cap slots holding the cloud's M voxels (the invariant of voxel.hpp's header): the keys
+// re-inserted by voxel through vslot, queued; the stream drains before the old blocks go back
+int grow_table(mc_ctx* c, VoxState* s, int log2cap) {
+  const size_t cap = (size_t)1 << log2cap;
+  DevBuf<unsigned long long> keys;
+  DevBuf<uint32_t> first, vid;
+  if (int r = keys.alloc(cap)) return r;
+  if (int r = first.alloc(cap)) return r;
+  if (int r = vid.alloc(cap)) return r;
+  VoxTable t = {};
+  t.keys = keys; t.first = first; t.vid = vid;
+  t.shift = 64 - log2cap;
+  t.mask = (uint32_t)(cap - 1);
+  HIPCHK(hipMemsetAsync(keys, 0xFF, cap * sizeof(unsigned long long), c->stream));
+  HIPCHK(hipMemsetAsync(first, 0xFF, cap * sizeof(uint32_t), c->stream));
+  if (s->M > 0)
+    hipLaunchKernelGGL(k_vox_rehash, dim3(blocks_of(s->M)), dim3(kVoxBlock), 0, c->stream, (const unsigned long long*)s->keys.get(),
+                       s->vslot.get(), s->M, t);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  s->keys = std::move(keys);
+  s->first = std::move(first);
+  s->vid = std::move(vid);
+  s->log2cap = log2cap;
+  s->shift = t.shift;
+  s->mask = t.mask;
+  ++s->growths;
+  return MC_OK;
+}
+
+// The n items of src into the live cloud s (include/mcdeskew.h "growing a voxel cloud").  points: what they hold when
+// the host knows it (a point each), -1 for records, whose counts the validation adds up.  *bad: the lowest refused
+// item (-1: none; the caller words the message); a refused call has not touched the table
+template <int KIND, typename Src>
+int insert(mc_ctx* c, VoxState* s, Src src, int64_t n, int64_t lanes, int64_t points, int64_t* n_new, int64_t* bad) {
+  *bad = -1;
+  *n_new = 0;
+  if (n == 0) return MC_OK;
+  if constexpr (KIND != kVoxRecords) {   // points are quantised on the cloud's own grid
+    src.h = s->h;
+    std::copy_n(s->o, 3, src.o);
+  }
+  if (!s->meta) if (int r = s->meta.alloc(kVoxMeta)) return r;
+  const int64_t n_chunks = (n + kVoxChunk - 1) / kVoxChunk;
+  const dim3 blk(kVoxBlock), pgrid(blocks_of(lanes)), cgrid((uint32_t)n_chunks);
+  uint32_t meta[kVoxMeta] = {0, 0, 0, 0};
+  {
+    TimedRegion tr(c, &s->ev[kInsValidate], c->stream);
+    HIPCHK(hipMemsetAsync(s->meta, 0xFF, 2 * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(s->meta + 2, 0, 2 * sizeof(uint32_t), c->stream));
+    // records are validated a chunk per workgroup (k_vox_validate), points a group per lane
+    hipLaunchKernelGGL((k_vox_validate<KIND, Src>), KIND == kVoxRecords ? cgrid : pgrid, blk, 0, c->stream, src, s->meta.get());
+  }
+  HIPCHK(hipGetLastError());
+  if (int r = copy_back(c, meta, s->meta, sizeof meta)) return r;
+  if (meta[0] != kVoxNone) {
+    *bad = (int64_t)meta[0];
+    return MC_ERR_INVALID;
+  }
+  if (points < 0) points = (int64_t)((uint64_t)meta[2] | (uint64_t)meta[3] << 32);
+  if (points < n || s->N + points >= kVoxelPointsEnd)
+    return fail(MC_ERR_INVALID, "the cloud holds %lld points and the call brings %lld: a cloud takes fewer than 2^31 in all",
+                (long long)s->N, (long long)points);
+  const int64_t M = s->M;
+  const int log2cap = voxel_table_log2(M, n, s->log2cap);
+  if (int r = ctx_reserve(c, s->slot, (size_t)n)) return r;
+  if (int r = ctx_reserve(c, s->flags, (size_t)n_chunks * kVoxBlock)) return r;
+  if (int r = ctx_reserve(c, s->chunk, (size_t)n_chunks)) return r;
+  VoxTable t;
+  {
+    TimedRegion tr(c, &s->ev[kInsInsert], c->stream);
+    if (log2cap != s->log2cap) if (int r = grow_table(c, s, log2cap)) return r;   // the same cloud in a larger table
+    s->built = false;   // from here the call's keys go in: a failure that is no refusal (memory, HIP) leaves no live build
+    t = table_of(s);
+    hipLaunchKernelGGL((k_vox_insert_live<KIND, Src>), pgrid, blk, 0, c->stream, src, t);
+  }
+  {
+    TimedRegion tr(c, &s->ev[kInsRank], c->stream);
+    hipLaunchKernelGGL(k_vox_flag<true>, cgrid, blk, 0, c->stream, t, n, s->flags, s->chunk);
+    scan_counts(c, s->chunk, n_chunks, s->meta);
+  }
+  HIPCHK(hipGetLastError());
+  // the call's second synchronisation: the new voxels, which size the records
+  if (int r = copy_back(c, meta, s->meta, 2 * sizeof(uint32_t))) return r;
+  const int64_t fresh = (int64_t)meta[1], Mn = M + fresh;
+  if (fresh > n || Mn >= kVoxelPointsEnd) return fail(MC_ERR_STATE, "voxel insert: %lld new voxels of %lld items", (long long)fresh, (long long)n);
+  if (int r = ctx_reserve_keep(c, s->vslot, (size_t)M, (size_t)Mn)) return r;
+  if (int r = ctx_reserve_keep(c, s->sums, kVoxRec * (size_t)M, kVoxRec * (size_t)Mn)) return r;
+  if (int r = ctx_reserve_keep(c, s->cnt, (size_t)M, (size_t)Mn)) return r;
+  {
+    TimedRegion tr(c, &s->ev[kInsRank], c->stream);
+    hipLaunchKernelGGL(k_vox_rank<true>, cgrid, blk, 0, c->stream, t, n, (const uint8_t*)s->flags, (const uint32_t*)s->chunk,
+                       s->vslot, (uint32_t)M);
+  }
+  {
+    TimedRegion tr(c, &s->ev[kInsAccumulate], c->stream);
+    if (fresh > 0) {
+      HIPCHK(hipMemsetAsync(s->sums + kVoxRec * M, 0, kVoxRec * (size_t)fresh * sizeof(long long), c->stream));
+      HIPCHK(hipMemsetAsync(s->cnt + M, 0, (size_t)fresh * sizeof(uint32_t), c->stream));
+    }
+    hipLaunchKernelGGL((k_vox_accumulate_items<KIND, Src>), pgrid, blk, 0, c->stream, src, t, s->sums.get(), s->cnt.get());
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(c->stream));
+  s->M = Mn;
+  s->N += points;
+  s->built = true;
+  s->cent_current = false;   // as a new build: the next analysis sees the grown cloud
+  s->cl_current = false;
+  *n_new = fresh;
+  return MC_OK;
+}
+
+// the frame of dense point p of a batch: the last one starting at or before it (empty frames start where the next
+// begins and come earlier in the order)
+int32_t frame_of(const mc_batch* in, int64_t p) {
+  return (int32_t)(std::upper_bound(in->doff.begin(), in->doff.begin() + in->F + 1, p) - in->doff.begin()) - 1;
+}
+
+VoxSrc batch_source(const mc_batch* in) {
+  VoxSrc src = {};
+  src.cols = in->d_cols; src.C = in->C; src.F = in->F;
+  src.poff = in->d_poff; src.doff = in->d_doff; src.counts = in->d_counts;
+  src.P = in->P;
+  src.n = in->N;
+  return src;
 }
 
 const char* kRefused =
@@ -740,19 +891,13 @@ int mc_voxel_build_batch(mc_ctx* c, const mc_batch* in, double voxel, const doub
   if (int r = check_grid(voxel, origin)) return r;
   CHECK_ARG(in->N < ((int64_t)1 << 31), "%lld points: the voxel filter takes fewer than 2^31", (long long)in->N);
   DeviceGuard g(c->device);
-  VoxSrc src = {};
-  src.cols = in->d_cols; src.C = in->C; src.F = in->F;
-  src.poff = in->d_poff; src.doff = in->d_doff; src.counts = in->d_counts;
-  src.P = in->P;
-  src.n = in->N;
+  VoxSrc src = batch_source(in);
   src.h = voxel;
   std::copy_n(origin, 3, src.o);
   int64_t bad = -1;
   const int r = build<true>(c, src, in->N, in->P / 4, n_voxels, &bad);
   if (bad >= 0) {
-    // the frame holding dense point `bad`: the last one starting at or before it (empty frames start
-    // where the next begins and come earlier in the order)
-    const int32_t f = (int32_t)(std::upper_bound(in->doff.begin(), in->doff.begin() + in->F + 1, bad) - in->doff.begin()) - 1;
+    const int32_t f = frame_of(in, bad);
     if (bad_frame) *bad_frame = f;
     if (bad_index) *bad_index = bad - in->doff[f];
     return fail(MC_ERR_INVALID, "frame %d, point %lld (the lowest refused): %s", f, (long long)(bad - in->doff[f]), kRefused);
@@ -809,6 +954,106 @@ int mc_voxel_emit_f64(mc_ctx* c, double* d_rows, int32_t* d_counts, int32_t* d_k
   a.counts = d_counts;
   a.keys_out = d_keys;
   return emit(c, s, a, false, 0);
+}
+
+int mc_voxel_insert_batch(mc_ctx* c, const mc_batch* in, int64_t* n_new, int32_t* bad_frame, int64_t* bad_index) {
+  if (bad_frame) *bad_frame = -1;
+  if (bad_index) *bad_index = -1;
+  if (n_new) *n_new = 0;
+  CHECK_ARG(c && in && n_new, "NULL argument");
+  CHECK_ARG(in->ctx == c, "batch belongs to another context");
+  CHECK_ARG(in->N < kVoxelPointsEnd, "%lld points: a cloud takes fewer than 2^31 in all", (long long)in->N);
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_insert_batch", &s)) return r;
+  DeviceGuard g(c->device);
+  int64_t bad = -1;
+  const int r = insert<kVoxBatch>(c, s, batch_source(in), in->N, in->P / 4, in->N, n_new, &bad);
+  if (bad >= 0) {
+    const int32_t f = frame_of(in, bad);
+    if (bad_frame) *bad_frame = f;
+    if (bad_index) *bad_index = bad - in->doff[f];
+    return fail(MC_ERR_INVALID, "frame %d, point %lld (the lowest refused; the cloud is unchanged): %s", f,
+                (long long)(bad - in->doff[f]), kRefused);
+  }
+  return r;
+}
+
+int mc_voxel_insert_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n, int64_t* n_new, int64_t* bad_row) {
+  if (bad_row) *bad_row = -1;
+  if (n_new) *n_new = 0;
+  CHECK_ARG(c && n_new, "NULL argument");
+  CHECK_ARG(ld >= 4, "voxel rows are x, y, z, intensity: ld >= 4; got %lld", (long long)ld);
+  CHECK_ARG(n >= 0 && n < kVoxelPointsEnd, "%lld points: a cloud takes 0 to 2^31 - 1 in all", (long long)n);
+  CHECK_ARG(n == 0 || d_rows, "d_rows is NULL");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_insert_f64", &s)) return r;
+  DeviceGuard g(c->device);
+  VoxSrc src = {};
+  src.rows = d_rows; src.ld = ld; src.n = n;
+  int64_t bad = -1;
+  const int r = insert<kVoxRows>(c, s, src, n, n, n, n_new, &bad);
+  if (bad >= 0) {
+    if (bad_row) *bad_row = bad;
+    return fail(MC_ERR_INVALID, "row %lld (the lowest refused; the cloud is unchanged): %s", (long long)bad, kRefused);
+  }
+  return r;
+}
+
+int mc_voxel_merge_sums(mc_ctx* c, const int32_t* d_keys, const int32_t* d_counts, const int64_t* d_sums, int64_t m,
+                        int64_t* n_new, int64_t* bad_record) {
+  if (bad_record) *bad_record = -1;
+  if (n_new) *n_new = 0;
+  CHECK_ARG(c && n_new, "NULL argument");
+  CHECK_ARG(m >= 0 && m < kVoxelPointsEnd, "%lld records: a merge takes 0 to 2^31 - 1", (long long)m);
+  CHECK_ARG(m == 0 || (d_keys && d_counts && d_sums), "d_keys, d_counts or d_sums is NULL");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_merge_sums", &s)) return r;
+  DeviceGuard g(c->device);
+  VoxRecSrc src = {};
+  src.keys = d_keys; src.counts = d_counts; src.sums = reinterpret_cast<const long long*>(d_sums);
+  src.n = m;
+  int64_t bad = -1;
+  const int r = insert<kVoxRecords>(c, s, src, m, m, -1, n_new, &bad);
+  if (bad >= 0) {
+    if (bad_record) *bad_record = bad;
+    return fail(MC_ERR_INVALID,
+                "record %lld (the lowest refused; the cloud is unchanged): a count below 1, a key outside [-2^20, 2^20), a "
+                "coordinate sum outside 0 .. count * 2^32 or an intensity sum beyond +-count * 2^32", (long long)bad);
+  }
+  return r;
+}
+
+int mc_voxel_emit_sums(mc_ctx* c, int64_t* d_sums) {
+  CHECK_ARG(c, "ctx is NULL");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_emit_sums", &s)) return r;
+  if (s->M == 0) return MC_OK;
+  CHECK_ARG(d_sums, "d_sums is NULL");
+  DeviceGuard g(c->device);
+  HIPCHK(hipMemcpyAsync(d_sums, s->sums, kVoxRec * (size_t)s->M * sizeof(long long), hipMemcpyDeviceToDevice, c->stream));
+  return MC_OK;
+}
+
+int mc_voxel_points(mc_ctx* c, int64_t* n_points) {
+  CHECK_ARG(c && n_points, "NULL argument");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_points", &s)) return r;
+  *n_points = s->N;
+  return MC_OK;
+}
+
+int mc_voxel_table(mc_ctx* c, int64_t* slots, int64_t* growths) {
+  CHECK_ARG(c, "ctx is NULL");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_table", &s)) return r;
+  if (slots) *slots = s->log2cap ? (int64_t)1 << s->log2cap : 0;
+  if (growths) *growths = s->growths;
+  return MC_OK;
+}
+
+int mc_timing_read_voxel_insert(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  return read_phases(c, kInsertPhases, ms_phase, launches);
 }
 
 int mc_timing_read_voxel(mc_ctx* c, double* ms_phase, int64_t* launches) {

@@ -10,6 +10,23 @@
 //   accumulate  per point 64-bit integer atomic adds of Q[3] and QI and a 32-bit add of 1 into the
 //               voxel's record: integer sums do not depend on the order the atomics arrive in
 //   finalise    one lane per voxel (four voxels per lane into a batch), 16-byte stores
+//
+// Growing a live cloud (mc_voxel_insert_*, mc_voxel_merge_sums).  An item is a point, or a voxel record (key, n,
+// S[3], SI) standing for n points of that voxel arriving together; its index p is its place in the call's source.
+// Between calls the table holds this invariant, which the build leaves and every insert restores:
+//   keys[slot]   kVoxelEmpty, or the key of voxel vid[slot], with vslot[vid[slot]] == slot
+//   first[slot]  kVoxNone in an empty slot, a value below kVoxNewBit in an occupied one
+// so an insert tells a voxel of the cloud (first < kVoxNewBit) from a key of its own call (first >= kVoxNewBit)
+// without a pass over the table, and its cost is that of its items:
+//   validate    every item quantised or checked, atomicMin of a refused p; the table is not touched before the
+//               host has seen that none is refused, so a refused call changes nothing
+//   grow        M + items > cap / 2 (voxel_table_log2): a fresh table, one lane per voxel re-inserts the key it
+//               finds through vslot (keys are distinct: CAS alone) and writes vid, first and the new vslot
+//   insert      the build's probe; a lane that ends in a slot with first >= kVoxNewBit takes part in the
+//               atomicMin of kVoxNewBit | p, a lane at a voxel of the cloud leaves first alone
+//   rank        the build's flag / scan / rank over the call's items: flag[p] = (first[slot[p]] == kVoxNewBit | p);
+//               the new voxels are M_old + rank, and the flagged lane puts first[slot] below kVoxNewBit again
+//   accumulate  as the build's, a record adding its sums and its n
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +40,8 @@ constexpr int kVoxBlock = 256;          // threads per workgroup
 constexpr int kVoxPerThread = 8;        // points per thread of the rank kernels
 constexpr int kVoxChunk = kVoxBlock * kVoxPerThread;   // points per workgroup of the rank kernels
 constexpr uint32_t kVoxNone = kVoxelNoSlot;   // no slot (a refused point) / no first index yet
+constexpr uint32_t kVoxNewBit = 0x80000000u;  // first[slot] of a key the running insert created: kVoxNewBit | lowest p
+enum VoxKind { kVoxRows = 0, kVoxBatch = 1, kVoxRecords = 2 };   // the source of an insert
 
 typedef float vox_f4 __attribute__((ext_vector_type(4)));
 
@@ -41,6 +60,14 @@ struct VoxSrc {
   double h, o[3];
 };
 
+// voxel records as the source of a merge
+struct VoxRecSrc {
+  const int32_t* keys;     // (n, 3)
+  const int32_t* counts;   // (n,)
+  const long long* sums;   // (n, 4) = Sx, Sy, Sz, SI
+  int64_t n;
+};
+
 struct VoxTable {
   unsigned long long* keys;   // cap
   uint32_t* first;            // cap: the lowest p of the slot's key
@@ -48,7 +75,7 @@ struct VoxTable {
   uint32_t* slot;             // n: the point's slot (kVoxNone: refused)
   int shift;                  // 64 - log2(cap)
   uint32_t mask;              // cap - 1
-  uint32_t* meta;             // [0] lowest refused p (kVoxNone: none), [1] M
+  uint32_t* meta;             // [0] lowest refused p (kVoxNone: none), [1] M, [2..3] an insert's points (64 bits)
 };
 
 // the points of one lane: BATCH, the float4 group g of the padded columns (4 points of one frame);
@@ -140,7 +167,8 @@ __device__ __forceinline__ uint32_t vox_block_scan(uint32_t v, uint32_t* excl) {
 }
 
 // flags of the chunk's points (bit j of byte t: point chunk * kVoxChunk + 8 t + j is the first of its
-// voxel) and the chunk's count
+// voxel) and the chunk's count.  LIVE: of an insert, whose first indices carry kVoxNewBit
+template <bool LIVE>
 __global__ __launch_bounds__(kVoxBlock) void k_vox_flag(VoxTable t, int64_t n, uint8_t* flags, uint32_t* chunk_count) {
   const int64_t base = ((int64_t)blockIdx.x * kVoxBlock + threadIdx.x) * kVoxPerThread;
   uint32_t bits = 0;
@@ -149,7 +177,7 @@ __global__ __launch_bounds__(kVoxBlock) void k_vox_flag(VoxTable t, int64_t n, u
     const int64_t p = base + j;
     if (p < n) {
       const uint32_t at = t.slot[p];
-      if (at != kVoxNone && t.first[at] == (uint32_t)p) bits |= 1u << j;
+      if (at != kVoxNone && t.first[at] == (LIVE ? kVoxNewBit | (uint32_t)p : (uint32_t)p)) bits |= 1u << j;
     }
   }
   flags[(int64_t)blockIdx.x * kVoxBlock + threadIdx.x] = (uint8_t)bits;
@@ -172,20 +200,23 @@ __global__ __launch_bounds__(kVoxBlock) void k_vox_scan(uint32_t* chunk_count, i
   if (threadIdx.x == 0) meta[1] = carry;
 }
 
-// vid[slot] and vslot[rank] of every flagged point
+// vid[slot] and vslot[rank] of every flagged point.  LIVE: ranks follow the cloud's `base` voxels, and the slot's
+// first index goes back below kVoxNewBit (the table's invariant between calls)
+template <bool LIVE>
 __global__ __launch_bounds__(kVoxBlock) void k_vox_rank(VoxTable t, int64_t n, const uint8_t* flags,
-                                                        const uint32_t* chunk_off, uint32_t* vslot) {
+                                                        const uint32_t* chunk_off, uint32_t* vslot, uint32_t base_rank) {
   const int64_t base = ((int64_t)blockIdx.x * kVoxBlock + threadIdx.x) * kVoxPerThread;
   const uint32_t bits = flags[(int64_t)blockIdx.x * kVoxBlock + threadIdx.x];
   uint32_t excl;
   vox_block_scan(__builtin_popcount(bits), &excl);
-  uint32_t rank = chunk_off[blockIdx.x] + excl;
+  uint32_t rank = (LIVE ? base_rank : 0u) + chunk_off[blockIdx.x] + excl;
 #pragma unroll
   for (int j = 0; j < kVoxPerThread; ++j) {
     if (bits & (1u << j)) {   // a set bit has p < n and a slot
       const uint32_t at = t.slot[base + j];
       t.vid[at] = rank;
       vslot[rank] = at;
+      if (LIVE) t.first[at] = (uint32_t)(base + j);
       ++rank;
     }
   }
@@ -209,6 +240,115 @@ __global__ __launch_bounds__(kVoxBlock) void k_vox_accumulate(VoxSrc s, VoxTable
     (void)__hip_atomic_fetch_add(r + 2, (long long)q.Q[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     (void)__hip_atomic_fetch_add(r + 3, (long long)q.QI, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     (void)__hip_atomic_fetch_add(cnt + vox, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  });
+}
+
+// ---- growing a live cloud ---------------------------------------------------------------------------------------------
+// the items of one lane: fn(p, q, n) with q the point quantised (n = 1) or the record as a VoxelPoint (Q = S, QI = SI,
+// bad: refused by voxel_record_ok)
+template <int KIND, typename Src, typename Fn>
+__device__ __forceinline__ void vox_items(const Src& s, int64_t g, Fn&& fn) {
+  if constexpr (KIND == kVoxRecords) {
+    if (g >= s.n) return;
+    VoxelPoint q;
+    const int64_t n = s.counts[g];
+    const long long* r = s.sums + 4 * g;
+    for (int c = 0; c < 3; ++c) {
+      q.k[c] = s.keys[3 * g + c];
+      q.Q[c] = r[c];
+    }
+    q.QI = r[3];
+    q.bad = voxel_record_ok(q.k, n, q.Q, q.QI) ? 0 : 1;
+    fn(g, q, (uint32_t)n);
+  } else {
+    vox_points<KIND == kVoxBatch>(s, g, [&](int64_t p, const double v[3], double inten) {
+      fn(p, voxel_quantise(v, inten, s.h, s.o), 1u);
+    });
+  }
+}
+
+// meta[0] = the lowest refused item (kVoxNone: none); records: meta[2..3] += the points of the accepted ones.
+// Points: a lane per group, as the other phases.  Records: a workgroup per chunk of kVoxChunk, so the one word that
+// takes the sum sees one add per 2048 records (a single word takes ~88 atomics per microsecond, MI355X_MICROARCH.md
+// "dequeue": one add per wave was 10 ms for 59 M records).
+template <int KIND, typename Src>
+__global__ __launch_bounds__(kVoxBlock) void k_vox_validate(Src s, uint32_t* meta) {
+  constexpr int kPer = KIND == kVoxRecords ? kVoxPerThread : 1;
+  unsigned long long pts = 0;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int64_t g = ((int64_t)blockIdx.x * kPer + j) * kVoxBlock + threadIdx.x;
+    vox_items<KIND>(s, g, [&](int64_t p, const VoxelPoint& q, uint32_t n) {
+      if (q.bad) atomicMin(meta, (uint32_t)p);
+      else pts += n;
+    });
+  }
+  if constexpr (KIND == kVoxRecords) {   // every thread of the workgroup is here
+    __shared__ unsigned long long wave_pts[kVoxBlock / 64];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) pts += __shfl_xor(pts, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_pts[threadIdx.x >> 6] = pts;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      unsigned long long total = 0;
+#pragma unroll
+      for (int w = 0; w < kVoxBlock / 64; ++w) total += wave_pts[w];
+      if (total) atomicAdd(reinterpret_cast<unsigned long long*>(meta + 2), total);
+    }
+  }
+}
+
+// one lane per voxel of the cloud: its key out of the old table into the new one (t), keys being distinct
+__global__ __launch_bounds__(kVoxBlock) void k_vox_rehash(const unsigned long long* old_keys, uint32_t* vslot, int64_t M,
+                                                          VoxTable t) {
+  const int64_t v = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
+  if (v >= M) return;
+  const unsigned long long key = old_keys[vslot[v]];
+  uint32_t at = voxel_slot_first(key, t.shift, t.mask);
+  while (atomicCAS(t.keys + at, (unsigned long long)kVoxelEmpty, key) != kVoxelEmpty) at = voxel_slot_next(at, t.mask);
+  t.vid[at] = (uint32_t)v;
+  t.first[at] = 0u;
+  vslot[v] = at;
+}
+
+// k_vox_insert into a table that holds a cloud (the header's invariant); the call's items have passed k_vox_validate
+template <int KIND, typename Src>
+__global__ __launch_bounds__(kVoxBlock) void k_vox_insert_live(Src s, VoxTable t) {
+  const int64_t g = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
+  vox_items<KIND>(s, g, [&](int64_t p, const VoxelPoint& q, uint32_t) {
+    if (q.bad) {
+      t.slot[p] = kVoxNone;
+      return;
+    }
+    const unsigned long long key = voxel_pack(q.k);
+    uint32_t at = voxel_slot_first(key, t.shift, t.mask);
+    for (;;) {   // as k_vox_insert
+      unsigned long long cur = __hip_atomic_load(t.keys + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (cur == kVoxelEmpty) cur = atomicCAS(t.keys + at, (unsigned long long)kVoxelEmpty, key);
+      if (cur == kVoxelEmpty || cur == key) break;
+      at = voxel_slot_next(at, t.mask);
+    }
+    // a voxel of the cloud keeps its first index below kVoxNewBit through the whole call, a key of this call
+    // never gets below it: whichever value the load sees decides the same
+    if (__hip_atomic_load(t.first + at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= kVoxNewBit)
+      atomicMin(t.first + at, kVoxNewBit | (uint32_t)p);
+    t.slot[p] = at;
+  });
+}
+
+template <int KIND, typename Src>
+__global__ __launch_bounds__(kVoxBlock) void k_vox_accumulate_items(Src s, VoxTable t, long long* sums, uint32_t* cnt) {
+  const int64_t g = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
+  vox_items<KIND>(s, g, [&](int64_t p, const VoxelPoint& q, uint32_t n) {
+    const uint32_t at = t.slot[p];
+    if (at == kVoxNone) return;
+    const int64_t vox = t.vid[at];
+    long long* r = sums + kVoxRec * vox;
+    (void)__hip_atomic_fetch_add(r + 0, (long long)q.Q[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(r + 1, (long long)q.Q[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(r + 2, (long long)q.Q[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(r + 3, (long long)q.QI, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(cnt + vox, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   });
 }
 

@@ -87,6 +87,32 @@ MC_CORE_HD uint32_t voxel_slot_first(uint64_t key, int shift, uint32_t mask) {
   return at == kVoxelNoSlot ? 0u : at;
 }
 
+// ---- growing a live cloud (voxel.hpp "insert into a live table") ------------------------------------
+// A cloud holds fewer than 2^31 points in all: the uint32 count, the int32 emit and |S| < 2^63 stay safe.
+constexpr int64_t kVoxelPointsEnd = (int64_t)1 << 31;
+constexpr int kVoxelLog2Min = 6, kVoxelLog2Max = 32;   // a table has 64 .. 2^32 slots
+
+// The table of a cloud of M voxels before a call of n items (log2cap: its slots now, 0: no table yet).
+// Every item may bring a new key, and the table stays at most half full: M + n <= cap / 2 keeps it, else
+// it grows to the power of two >= 2 (M + n), at least 64 slots and at most 2^32.  -> log2 of the slots
+MC_CORE_HD int voxel_table_log2(int64_t M, int64_t n, int log2cap) {
+  const int64_t need = M + n;
+  if (log2cap > 0 && need <= (((int64_t)1 << log2cap) >> 1)) return log2cap;
+  int l = kVoxelLog2Min;
+  while (l < kVoxelLog2Max && ((int64_t)1 << l) < 2 * need) ++l;
+  return l > log2cap ? l : log2cap;
+}
+
+// A voxel record offered to a merge: n points of voxel k arriving together with sums S[3] and SI.
+// What n points can sum to: 0 <= Q <= 2^32 and |QI| <= 2^32 each.
+MC_CORE_HD bool voxel_record_ok(const int32_t k[3], int64_t n, const int64_t S[3], int64_t SI) {
+  if (n < 1 || n >= kVoxelPointsEnd) return false;
+  const int64_t top = n << 32;   // < 2^63
+  for (int c = 0; c < 3; ++c)
+    if (k[c] < kVoxelKeyMin || k[c] >= kVoxelKeyEnd || S[c] < 0 || S[c] > top) return false;
+  return SI >= -top && SI <= top;
+}
+
 // one voxel: out = cx, cy, cz, intensity (n >= 1)
 MC_CORE_HD void voxel_finalise(const int32_t k[3], const int64_t S[3], int64_t SI, int64_t n, double h,
                                 const double o[3], double out[4]) {

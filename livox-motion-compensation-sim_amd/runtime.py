@@ -372,6 +372,10 @@ class Context:
         """Event time (ms) of the voxel filter's phases since the last read (mc_timing_read_voxel)."""
         return self._read_phases("timing_read_voxel", ("insert_ms", "rank_ms", "accumulate_ms", "finalise_ms"))
 
+    def read_timing_voxel_insert(self) -> dict:
+        """Event time (ms) of the phases of VoxelCloud.insert / .merge since the last read (mc_timing_read_voxel_insert)."""
+        return self._read_phases("timing_read_voxel_insert", ("validate_ms", "insert_ms", "rank_ms", "accumulate_ms"))
+
     def read_timing_normals(self) -> dict:
         """Event time (ms) of the phases of VoxelCloud.normals since the last read (mc_timing_read_normals)."""
         return self._read_phases("timing_read_normals", ("centroids_ms", "window_ms", "cap_ms"))

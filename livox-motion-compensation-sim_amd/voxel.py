@@ -3,7 +3,8 @@ csrc/voxel.hpp; include/mcdeskew.h ``mc_voxel_*``): the step after a global desk
 of a drive are accumulated into one cloud and most points re-observe the same surfaces.
 
   voxel_downsample(batch_or_rows, voxel, origin=(0, 0, 0))  -> VoxelCloud
-  VoxelCloud.n_voxels, .batch(), .rows(), .point_counts(), .keys(), .close()
+  VoxelCloud.n_voxels, .n_points, .batch(), .rows(), .point_counts(), .keys(), .close()
+  VoxelCloud.insert(batch_or_rows)  -> int, .state()  -> VoxelSums, .merge(state)  -> int
   VoxelCloud.normals(radius, max_nn=30, viewpoint=None, covariance=False)  -> VoxelNormals
   VoxelCloud.clusters(eps, min_points=10, weighted=False)  -> VoxelClusters
   VoxelCloud.segment_plane(distance_threshold, num_iterations=1000, seed=0, refine=True, among=None)  -> VoxelPlane
@@ -31,6 +32,22 @@ the default origin the grids of different calls coincide.
 Refused, never dropped silently: a coordinate or (v - o) / h that is not finite, a voxel index
 outside [-2^20, 2^20), an intensity that is not finite or beyond +-65536 — ValueError naming the
 lowest refused point (frame and index for a batch, the row for rows), and nothing is returned.
+
+Growing a cloud (csrc/voxel.hpp "growing a live cloud"; ``mc_voxel_insert_*``, ``mc_voxel_emit_sums``,
+``mc_voxel_merge_sums``): a drive is a stream, and a map is longer than one batch.  After any sequence of ``insert`` and
+``merge`` calls the cloud is bit for bit what ``voxel_downsample`` returns for the concatenation of the sources in call
+order: the records are integers, so adding them is exact, and voxels are numbered by first appearance, so a voxel keeps
+its id and new ones follow in the order of the call's items (the points of a source in its index order; the records of
+a VoxelSums in theirs, each standing for its n points arriving together).  Every item is quantised or checked on the
+cloud's own grid.  ``state()`` is the cloud's records (keys, counts, the raw sums Sx, Sy, Sz, SI) and its grid as host
+arrays, to be pickled or sent between ranks; ``merge`` takes one of a grid equal bit for bit.  The cloud of an empty
+source, ``voxel_downsample(np.zeros((0, 4)), h, origin)``, is the way to start a map from nothing.  The cloud holds
+fewer than 2^31 points in all (``n_points``).  The cost of a call is that of its items, apart from the table's growth.
+Arrays returned before a call keep their first rows' identity, not their values; the next analysis sees the grown cloud.
+Refused with ValueError, the cloud left bit for bit as it was: a point the filter refuses, a record with a count below
+1, a key outside [-2^20, 2^20), a coordinate sum outside 0 .. n 2^32 or an intensity sum beyond +-n 2^32 (the message
+names the lowest refused item), a call that would bring the cloud to 2^31 points, a batch of another context, rows that
+are not (N, >= 4), a state of another grid or with arrays of the wrong dtype or shape.
 
 Surface normals (csrc/normals_core.hpp, csrc/normals.hpp; ``mc_voxel_normals``): what the reference's
 viewer computes with open3d on every cloud without normals (read_pointcloud.py:81-84), here from the live
@@ -389,17 +406,146 @@ def plane_score_chunk() -> int:
     return int(load().mc_voxel_plane_chunk())
 
 
+class VoxelSums(NamedTuple):
+    """What :meth:`VoxelCloud.state` returns and :meth:`VoxelCloud.merge` takes: the cloud's exact records as host
+    arrays in the cloud's order, and its grid.  Plain data: it pickles, and travels between ranks as it is."""
+    keys: np.ndarray        # (M, 3) int32 kx, ky, kz
+    counts: np.ndarray      # (M,) int32 the points of each voxel
+    sums: np.ndarray        # (M, 4) int64 Sx, Sy, Sz (2^-32 voxel units inside the voxel), SI (2^-16)
+    voxel: float            # the grid: records merge only into a cloud whose voxel and origin have these bits
+    origin: np.ndarray      # (3,) float64
+
+
+def _insert_arg(ctx, src, room):
+    """(batch, None, n) or (None, rows (N, >= 4) float64, N) for a cloud with room for ``room`` more points,
+    checked before a device is touched."""
+    if isinstance(src, Batch):
+        if src.ctx is not ctx:
+            raise ValueError("the batch belongs to another context")
+        batch, rows, n = src, None, src.n_points
+    else:
+        a = np.asarray(src)
+        if a.ndim != 2 or a.shape[1] < 4:
+            raise ValueError(f"rows must be (N, >= 4) = x, y, z, intensity; got shape {a.shape}")
+        try:
+            batch, rows, n = None, np.ascontiguousarray(a, dtype=np.float64), a.shape[0]
+        except (TypeError, ValueError):
+            raise ValueError(f"rows must be numbers, got dtype {a.dtype}") from None
+    if n > room:
+        raise ValueError(f"the cloud holds {MAX_POINTS - room} points and the call brings {n}: a cloud takes fewer than "
+                         f"2^31 in all")
+    return batch, rows, n
+
+
+def _same_bits(a, b):
+    return np.asarray(a, np.float64).tobytes() == np.asarray(b, np.float64).tobytes()
+
+
+def _sums_arg(state, h, origin):
+    """(keys, counts, sums) of a VoxelSums of this very grid, contiguous, checked before a device is touched."""
+    try:
+        keys, counts, sums, voxel, o = state.keys, state.counts, state.sums, state.voxel, state.origin
+    except AttributeError:
+        raise ValueError(f"merge takes a VoxelSums (keys, counts, sums, voxel, origin), got {type(state).__name__}") from None
+    if h is None or origin is None:
+        raise ValueError("this cloud does not know its grid: merge needs a cloud made by voxel_downsample")
+    if not isinstance(voxel, (float, np.floating)) or not _same_bits(voxel, h):
+        raise ValueError(f"the state's voxel {voxel!r} is not the cloud's {h!r} bit for bit: a different grid")
+    if not isinstance(o, np.ndarray) or o.dtype != np.float64 or o.shape != (3,) or not _same_bits(o, origin):
+        raise ValueError(f"the state's origin {o!r} is not the cloud's {origin!r} bit for bit: a different grid")
+    for a, name, dtype, tail in ((keys, "keys", np.int32, (3,)), (counts, "counts", np.int32, ()), (sums, "sums", np.int64, (4,))):
+        if not isinstance(a, np.ndarray) or a.dtype != dtype or a.shape[1:] != tail or a.ndim != 1 + len(tail):
+            raise ValueError(f"state.{name} must be a {np.dtype(dtype).name} array of shape (M{''.join(f', {t}' for t in tail)}), "
+                             f"got {getattr(a, 'dtype', type(a).__name__)} {getattr(a, 'shape', '')}")
+    if not len(keys) == len(counts) == len(sums):
+        raise ValueError(f"state.keys, .counts and .sums must hold the same M records, got {len(keys)}, {len(counts)}, {len(sums)}")
+    if len(keys) > MAX_POINTS:
+        raise ValueError(f"{len(keys)} records: a merge takes fewer than 2^31")
+    return np.ascontiguousarray(keys), np.ascontiguousarray(counts), np.ascontiguousarray(sums)
+
+
 class VoxelCloud:
     """What the last :func:`voxel_downsample` of a context left on the device.  The outputs are produced
-    on demand from the per-voxel sums, any number of times; the next ``voxel_downsample`` on the same
-    context (or :meth:`close`) ends this object's validity."""
+    on demand from the per-voxel sums, any number of times; :meth:`insert` and :meth:`merge` grow it in place;
+    the next ``voxel_downsample`` on the same context (or :meth:`close`) ends this object's validity."""
 
-    def __init__(self, ctx: Context, n_voxels: int, generation: int, voxel: float | None = None):
+    def __init__(self, ctx: Context, n_voxels: int, generation: int, voxel: float | None = None, origin=None,
+                 n_points: int | None = None):
         self.ctx, self.n_voxels, self._gen, self._h = ctx, int(n_voxels), generation, voxel
+        self._origin = None if origin is None else np.array(origin, np.float64)
+        self.n_points = n_points        # N: the points the cloud holds (None: made by hand, the library knows)
 
     def _live(self):
         if self.ctx._voxel_gen != self._gen:
             raise ValueError("this VoxelCloud is closed or was replaced by a later voxel_downsample on its context")
+
+    def _room(self):
+        return MAX_POINTS - (self.n_points or 0)
+
+    def _grown(self, n_new):
+        """After an insert or a merge: M and N from the call and the library."""
+        self.n_voxels += int(n_new)
+        n = c_int64(0)
+        check(self.ctx.lib.mc_voxel_points(self.ctx.handle, ctypes.byref(n)), "voxel points")
+        self.n_points = n.value
+        return int(n_new)
+
+    def insert(self, src) -> int:
+        """The points of ``src`` — a device Batch of the cloud's context, or host float64 rows (N, >= 4) — into the
+        cloud, on its own grid: afterwards the cloud is bit for bit ``voxel_downsample`` of everything it was given,
+        in call order (module docstring; include/mcdeskew.h ``mc_voxel_insert_*``).  Voxels keep their ids; new ones
+        follow.  -> the number of new voxels.  A refused point raises ValueError naming it and changes nothing."""
+        batch, rows, n = _insert_arg(self.ctx, src, self._room())
+        self._live()
+        if n == 0:
+            return 0
+        ctx = self.ctx
+        m = c_int64(0)
+        if batch is not None:
+            bf, bi = c_int32(-1), c_int64(-1)
+            check(ctx.lib.mc_voxel_insert_batch(ctx.handle, batch.handle, ctypes.byref(m), ctypes.byref(bf), ctypes.byref(bi)),
+                  "insert")
+        else:
+            with _Buffers(ctx) as bufs:
+                d_rows = bufs.take(rows.nbytes)
+                d_rows.from_host(rows)
+                bad = c_int64(-1)
+                check(ctx.lib.mc_voxel_insert_f64(ctx.handle, d_rows.ptr, rows.shape[1], n, ctypes.byref(m), ctypes.byref(bad)),
+                      "insert")
+        return self._grown(m.value)
+
+    def state(self) -> "VoxelSums":
+        """The cloud's exact records and its grid as host arrays (``mc_voxel_emit_sums``): merging them into a cloud
+        of the same grid equals inserting the points they stand for."""
+        self._live()
+        M = self.n_voxels
+        sums = np.zeros((0, 4), np.int64)
+        if M:
+            with _Buffers(self.ctx) as bufs:
+                buf = bufs.take(32 * M)
+                check(self.ctx.lib.mc_voxel_emit_sums(self.ctx.handle, buf.ptr), "state")
+                sums = buf.to_host(np.int64, count=4 * M).reshape(M, 4)
+        return VoxelSums(self.keys(), self.point_counts(), sums, float(self._h), np.array(self._origin, np.float64))
+
+    def merge(self, state) -> int:
+        """The records of ``state`` (a :class:`VoxelSums` of this very grid, voxel and origin equal bit for bit) into
+        the cloud, each as the points it stands for arriving together (module docstring; ``mc_voxel_merge_sums``):
+        afterwards the cloud is ``voxel_downsample`` of this cloud's points followed by the state's.  -> the number of
+        new voxels.  A refused record raises ValueError naming it and changes nothing."""
+        keys, counts, sums = _sums_arg(state, self._h, self._origin)
+        self._live()
+        m = len(keys)
+        if m == 0:
+            return 0
+        ctx = self.ctx
+        with _Buffers(ctx) as bufs:
+            d = [bufs.take(a.nbytes) for a in (keys, counts, sums)]
+            for buf, a in zip(d, (keys, counts, sums)):
+                buf.from_host(a)
+            new, bad = c_int64(0), c_int64(-1)
+            check(ctx.lib.mc_voxel_merge_sums(ctx.handle, d[0].ptr, d[1].ptr, d[2].ptr, m, ctypes.byref(new), ctypes.byref(bad)),
+                  "merge")
+        return self._grown(new.value)
 
     def batch(self, with_pcd_len: bool = False) -> Batch:
         """A one-frame float32 Batch of the voxel points (x, y, z, intensity; no time column), ready for
@@ -667,4 +813,4 @@ def voxel_downsample(src, voxel, origin=(0.0, 0.0, 0.0), context: Context | None
                                              ctypes.byref(m), ctypes.byref(bad)), "voxel_downsample")
     ctx._voxel_serial += 1
     ctx._voxel_gen = ctx._voxel_serial
-    return VoxelCloud(ctx, m.value, ctx._voxel_gen, h)
+    return VoxelCloud(ctx, m.value, ctx._voxel_gen, h, o, src.n_points if isinstance(src, Batch) else a.shape[0])
