@@ -531,6 +531,70 @@ int mc_voxel_table(mc_ctx* ctx, int64_t* slots, int64_t* growths);
  * insert (with the table's growth), rank, accumulate; *launches = timed regions */
 int mc_timing_read_voxel_insert(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 
+/* ---- shrinking a voxel cloud: removing voxels and subtracting exact sums -----------------------------
+ * The way out of the live build, as exact as the way in: the records are integers, so a subtraction undoes
+ * an addition bit for bit.
+ * mc_voxel_remove: d_mask is device (M,) bytes; the voxels whose byte is not 0 leave.  The survivors keep
+ * their relative order and get ids 0 .. M' - 1; *n_removed = M - M'.  Afterwards the cloud is BIT FOR BIT,
+ * in every emit and in N, the cloud mc_voxel_build_* returns for the concatenated sources with the points
+ * of the removed voxels left out (removing whole voxels changes no other voxel's first appearance).
+ * mc_voxel_subtract_*: the items of mc_voxel_insert_* / mc_voxel_merge_sums, leaving.  For a call on a
+ * cloud of M voxels and N points:
+ *   1. every item is quantised, or checked, with the cloud's own voxel size and origin, as an insert's
+ *   2. its Q[3], QI and n (1 for a point) are subtracted from the record of its voxel
+ *   3. a voxel whose count reaches 0 leaves as in mc_voxel_remove; *n_emptied is their number
+ *   4. N falls by the points of the call
+ *   5. insert then subtract of the same source, or merge then subtract of the same records, is the
+ *      identity in every emit, whatever voxels the source shares with the cloud; for the build of A
+ *      followed by B, subtracting A leaves exactly the records of the build of B, in the relative order
+ *      they had (a build of B alone may number them differently: a voxel's first point may have been A's)
+ *   6. a refused call changes nothing and is MC_ERR_INVALID with *why saying which of these it was:
+ *        MC_VOXEL_SUB_ITEM       an item an insert or a merge refuses
+ *        MC_VOXEL_SUB_MISSING    an item whose voxel the cloud does not hold
+ *        MC_VOXEL_SUB_POINTS     the call brings more points than the cloud holds (no item is named)
+ *        MC_VOXEL_SUB_REMAINDER  a voxel would be left with a record that no set of points sums to: a
+ *                                count below 0, a count of 0 with a sum that is not 0, or a count n' >= 1
+ *                                with a coordinate sum outside 0 .. n' * 2^32 or |SI| > n' * 2^32
+ *      The lowest refused item is named (*bad_frame / *bad_index, *bad_row, *bad_record; -1 when none);
+ *      for the last kind it is the lowest item whose voxel ended up invalid, and the message holds that
+ *      voxel's key.  ITEM and MISSING are found together, before anything is written: the lower item of
+ *      either kind is named.  (A failure that is no refusal, once the records have been touched, leaves no
+ *      live build.)
+ *   7. the cloud cannot know whether the subtracted points were ever inserted: that a record which passes
+ *      these checks is the record of the points meant to stay is the caller's contract
+ *   8. the centroids, normals and clustering derived from the cloud are invalidated as by an insert
+ * An empty call, or a mask without a set byte, is MC_OK and touches nothing.  Removing every voxel leaves
+ * an empty live cloud that an insert fills again.  Without a live build: MC_ERR_STATE.
+ * Cost.  A subtraction that empties no voxel costs what its items cost (one pass that validates and looks
+ * the keys up, read-only; one that subtracts; one that checks; two synchronisations): no pass over the
+ * table or the cloud.  A removal, and a subtraction that empties a voxel, cost what the CLOUD costs, not
+ * what leaves: the keep flags and their scan, one pass that moves the survivors' records into fresh arrays
+ * (swapped afterwards), and the table cleared and refilled from the survivors' keys.  The table keeps its
+ * size unless the survivors fill less than an eighth of it; then it shrinks to the power of two >= 4 M',
+ * at least 64 slots (mc_voxel_table reports it; a shrink is no growth).  Not built: tombstones, which
+ * would make a removal cost what leaves but put a compare into every probe loop of the build, the insert
+ * and the window walks; subtracting one frame of a batch; normals kept across a removal. */
+#define MC_VOXEL_SUB_OK 0
+#define MC_VOXEL_SUB_ITEM 1
+#define MC_VOXEL_SUB_MISSING 2
+#define MC_VOXEL_SUB_POINTS 3
+#define MC_VOXEL_SUB_REMAINDER 4
+int mc_voxel_remove(mc_ctx* ctx, const uint8_t* d_mask, int64_t* n_removed);
+/* the arguments of mc_voxel_insert_batch, *n_emptied for *n_new, and *why (may be NULL) */
+int mc_voxel_subtract_batch(mc_ctx* ctx, const mc_batch* in, int64_t* n_emptied, int32_t* bad_frame, int64_t* bad_index,
+                            int32_t* why);
+/* the arguments of mc_voxel_insert_f64, *n_emptied for *n_new, and *why (may be NULL) */
+int mc_voxel_subtract_f64(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t n, int64_t* n_emptied, int64_t* bad_row,
+                          int32_t* why);
+/* the arguments of mc_voxel_merge_sums, *n_emptied for *n_new, and *why (may be NULL): every record stands for
+ * its n points leaving together */
+int mc_voxel_subtract_sums(mc_ctx* ctx, const int32_t* d_keys, const int32_t* d_counts, const int64_t* d_sums, int64_t m,
+                           int64_t* n_emptied, int64_t* bad_record, int32_t* why);
+/* event time (ms) of the phases of the removals and subtractions since the last read: ms_phase[4] = validate,
+ * apply (and its undoing after a refusal), check, compact (keep flags, ids, records, the table's refill);
+ * *launches = timed regions */
+int mc_timing_read_voxel_remove(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* ---- surface normals of the voxel cloud (csrc/normals_core.hpp, normals.hpp) ---------------------
  * The reference's viewer runs, on every cloud without normals (read_pointcloud.py:81-84),
  *   pcd.estimate_normals(search_param=KDTreeSearchParamHybrid(radius=0.1, max_nn=30))

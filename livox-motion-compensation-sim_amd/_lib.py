@@ -149,6 +149,12 @@ _SIGS = {
     "mc_voxel_points": (c_int, [c_void_p, _pi64]),
     "mc_voxel_table": (c_int, [c_void_p, _pi64, _pi64]),
     "mc_timing_read_voxel_insert": (c_int, [c_void_p, _pd, _pi64]),
+    # shrinking the voxel cloud: voxels removed by a mask, points and exact sums subtracted (the last out word: why refused)
+    "mc_voxel_remove": (c_int, [c_void_p, c_void_p, _pi64]),
+    "mc_voxel_subtract_batch": (c_int, [c_void_p, c_void_p, _pi64, _pi32, _pi64, _pi32]),
+    "mc_voxel_subtract_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, _pi64, _pi64, _pi32]),
+    "mc_voxel_subtract_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, _pi64, _pi64, _pi32]),
+    "mc_timing_read_voxel_remove": (c_int, [c_void_p, _pd, _pi64]),
     # the surface normals of the voxel cloud
     "mc_voxel_normals": (c_int, [c_void_p, c_double, c_int32, _pd, c_void_p, c_void_p, c_void_p]),
     "mc_timing_read_normals": (c_int, [c_void_p, _pd, _pi64]),

@@ -37,16 +37,17 @@ enum {
   kRgNormals, kRgCorrespond, kRgLeaves, kRgTree,   // the register's fifth phase, the solve, is the host's: no events
   kRfNormals, kRfStep, kRfTree, kRfSolve,
   kInsValidate, kInsInsert, kInsRank, kInsAccumulate,   // growing the live cloud; the insert's phase holds the table's growth
+  kRmValidate, kRmApply, kRmCheck, kRmCompact,          // shrinking it; the compact phase holds the keep flags and the table's refill
   kAllPhases
 };
 struct PhaseRange { int first, count; };
 constexpr PhaseRange kFilterPhases = {kInsert, 4}, kNormalsPhases = {kNrmCentroids, 3}, kClPhases = {kClDensity, kClusterPhases},
                      kPlanePhases = {kPlCompact, 6}, kRegPhases = {kRgNormals, 4}, kRegFramesPhases = {kRfNormals, 4},
-                     kInsertPhases = {kInsValidate, 4};
+                     kInsertPhases = {kInsValidate, 4}, kRemovePhases = {kRmValidate, 4};
 constexpr int kRgSolve = 4;   // its public index
 constexpr int kVoxMeta = 4;   // the words of VoxTable::meta
 static_assert(kRegPhases.first + kRegPhases.count == kRfNormals && kRegFramesPhases.first + kRegFramesPhases.count == kInsValidate &&
-              kInsertPhases.first + kInsertPhases.count == kAllPhases &&
+              kInsertPhases.first + kInsertPhases.count == kRmValidate && kRemovePhases.first + kRemovePhases.count == kAllPhases &&
               kClPhases.first + kClPhases.count == kPlCompact, "the ranges");
 
 struct VoxState : mcimpl::CtxExt {
@@ -99,6 +100,10 @@ struct VoxState : mcimpl::CtxExt {
   DevBuf<int64_t> rf_map;
   DevBuf<double> rf_tree, rf_history;
   DevBuf<uint32_t> rf_live;
+  // a removal: the keep byte of every voxel, the survivors' packed keys on their way into the cleared table, and
+  // the word that takes their points
+  DevBuf<uint8_t> rm_keep;
+  DevBuf<unsigned long long> rm_keys, rm_points;
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
@@ -469,6 +474,199 @@ int compact(mc_ctx* c, VoxState* s, const uint8_t* d_mask, int phase, int64_t* n
   if ((int64_t)meta[1] > M) return fail(MC_ERR_STATE, "voxel mask: %u set bytes of %lld voxels", meta[1], (long long)M);
   *n = (int64_t)meta[1];
   return MC_OK;
+}
+
+// ---- shrinking the live cloud -----------------------------------------------------------------------------------------
+// The voxels of the live cloud (M > 0) whose byte in rm_keep is set stay, in their order, as voxels 0 .. M' - 1
+// (voxel.hpp "taking voxels and points out"): the survivors' ids, their records and keys compacted into fresh arrays,
+// the table cleared (shrunk by voxel_table_shrink_log2's rule) and refilled.  M' == M: nothing is touched.  Two
+// synchronisations: M', and the survivors' points with the end of the refill, before the old blocks go back.
+int keep_voxels(mc_ctx* c, VoxState* s, int64_t* n_removed) {
+  *n_removed = 0;
+  const int64_t M = s->M;
+  int64_t Mk = 0;
+  if (int r = compact(c, s, s->rm_keep, kRmCompact, &Mk)) return r;
+  if (Mk == M) return MC_OK;
+  const int log2cap = voxel_table_shrink_log2(Mk, s->log2cap);
+  const size_t cap = (size_t)1 << log2cap;
+  DevBuf<long long> sums;
+  DevBuf<uint32_t> cnt;
+  if (int r = sums.alloc(kVoxRec * (size_t)Mk)) return r;
+  if (int r = cnt.alloc((size_t)Mk)) return r;
+  if (int r = ctx_reserve(c, s->rm_keys, (size_t)Mk)) return r;
+  if (!s->rm_points) if (int r = s->rm_points.alloc(1)) return r;
+  DevBuf<unsigned long long> keys;   // of a shrink alone: a table of the same size is refilled in place
+  DevBuf<uint32_t> first, vid;
+  VoxTable t = table_of(s);
+  if (log2cap != s->log2cap) {
+    if (int r = keys.alloc(cap)) return r;
+    if (int r = first.alloc(cap)) return r;
+    if (int r = vid.alloc(cap)) return r;
+    t.keys = keys; t.first = first; t.vid = vid;
+    t.shift = 64 - log2cap;
+    t.mask = (uint32_t)(cap - 1);
+  }
+  s->built = false;   // from here the records and the table change: a failure leaves no live build
+  {
+    TimedRegion tr(c, &s->ev[kRmCompact], c->stream);
+    HIPCHK(hipMemsetAsync(s->rm_points, 0, sizeof(unsigned long long), c->stream));
+    VoxCompact a = {};
+    a.ids = s->pl_ids; a.M_keep = Mk;
+    a.keys = s->keys; a.vslot = s->vslot; a.sums = s->sums; a.cnt = s->cnt;
+    a.sums_out = sums; a.cnt_out = cnt; a.keys_out = s->rm_keys; a.points = s->rm_points;
+    if (Mk > 0) hipLaunchKernelGGL(k_vox_compact, dim3(blocks_of(Mk)), dim3(kVoxBlock), 0, c->stream, a);
+    HIPCHK(hipMemsetAsync(t.keys, 0xFF, cap * sizeof(unsigned long long), c->stream));
+    HIPCHK(hipMemsetAsync(t.first, 0xFF, cap * sizeof(uint32_t), c->stream));
+    if (Mk > 0)
+      hipLaunchKernelGGL(k_vox_refill, dim3(blocks_of(Mk)), dim3(kVoxBlock), 0, c->stream, (const unsigned long long*)s->rm_keys.get(),
+                         s->vslot.get(), Mk, t);
+  }
+  HIPCHK(hipGetLastError());
+  unsigned long long points = 0;
+  if (int r = copy_back(c, &points, s->rm_points, sizeof points)) return r;   // the stream has drained
+  if (points > (unsigned long long)s->N || (int64_t)points < Mk)
+    return fail(MC_ERR_STATE, "voxel remove: %llu points in %lld voxels kept of a cloud of %lld points", points, (long long)Mk,
+                (long long)s->N);
+  s->sums = std::move(sums);
+  s->cnt = std::move(cnt);
+  if (log2cap != s->log2cap) {   // a shrink is no growth: growths stays
+    s->keys = std::move(keys);
+    s->first = std::move(first);
+    s->vid = std::move(vid);
+    s->log2cap = log2cap;
+    s->shift = t.shift;
+    s->mask = t.mask;
+  }
+  s->M = Mk;
+  s->N = (int64_t)points;
+  s->cent_current = false;   // as an insert: the next analysis sees the shrunk cloud
+  s->cl_current = false;
+  s->built = true;
+  *n_removed = M - Mk;
+  return MC_OK;
+}
+
+// the keep bytes of the live cloud (M > 0), queued: d_mask's clear bytes, or (null) the voxels that hold points
+int keep_flags(mc_ctx* c, VoxState* s, const uint8_t* d_mask) {
+  if (int r = ctx_reserve(c, s->rm_keep, (size_t)s->M)) return r;
+  {
+    TimedRegion tr(c, &s->ev[kRmCompact], c->stream);
+    if (d_mask)
+      hipLaunchKernelGGL(k_vox_keep<true>, dim3(blocks_of(s->M)), dim3(kVoxBlock), 0, c->stream, d_mask, (const uint32_t*)nullptr, s->M,
+                         s->rm_keep.get());
+    else
+      hipLaunchKernelGGL(k_vox_keep<false>, dim3(blocks_of(s->M)), dim3(kVoxBlock), 0, c->stream, (const uint8_t*)nullptr,
+                         (const uint32_t*)s->cnt.get(), s->M, s->rm_keep.get());
+  }
+  HIPCHK(hipGetLastError());
+  return MC_OK;
+}
+
+// why a subtraction refused (include/mcdeskew.h MC_VOXEL_SUB_*)
+struct SubRefusal {
+  int64_t item = -1;     // the lowest refused item (-1: none, as for the points)
+  int32_t why = MC_VOXEL_SUB_OK;
+  int32_t key[3] = {0, 0, 0};   // MC_VOXEL_SUB_REMAINDER: the voxel
+};
+
+// The n items of src out of the live cloud s (include/mcdeskew.h "shrinking a voxel cloud").  points: as insert's.
+// *ref: what was refused; a refused call leaves every record as it was
+template <int KIND, typename Src>
+int subtract(mc_ctx* c, VoxState* s, Src src, int64_t n, int64_t lanes, int64_t points, int64_t* n_emptied, SubRefusal* ref) {
+  *ref = SubRefusal();
+  *n_emptied = 0;
+  if (n == 0) return MC_OK;
+  if constexpr (KIND != kVoxRecords) {   // points are quantised on the cloud's own grid
+    src.h = s->h;
+    std::copy_n(s->o, 3, src.o);
+  }
+  if (!s->meta) if (int r = s->meta.alloc(kVoxMeta)) return r;
+  if (int r = ctx_reserve(c, s->slot, (size_t)n)) return r;
+  const int64_t n_chunks = (n + kVoxChunk - 1) / kVoxChunk;
+  const dim3 blk(kVoxBlock), pgrid(blocks_of(lanes)), cgrid((uint32_t)n_chunks), igrid(blocks_of(n));
+  VoxTable t = table_of(s);
+  if (s->log2cap == 0) t.keys = nullptr;   // the cloud of an empty source has no table: it holds no item's voxel
+  uint32_t meta[kVoxMeta] = {0, 0, 0, 0};
+  {
+    TimedRegion tr(c, &s->ev[kRmValidate], c->stream);
+    HIPCHK(hipMemsetAsync(s->meta, 0xFF, 2 * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(s->meta + 2, 0, 2 * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL((k_vox_sub_validate<KIND, Src>), KIND == kVoxRecords ? cgrid : pgrid, blk, 0, c->stream, src, t, s->meta.get());
+  }
+  HIPCHK(hipGetLastError());
+  if (int r = copy_back(c, meta, s->meta, sizeof meta)) return r;
+  if (meta[0] != kVoxNone || meta[1] != kVoxNone) {   // an item is one or the other: the words differ
+    ref->item = (int64_t)std::min(meta[0], meta[1]);
+    ref->why = meta[0] < meta[1] ? MC_VOXEL_SUB_ITEM : MC_VOXEL_SUB_MISSING;
+    return MC_ERR_INVALID;
+  }
+  if (points < 0) points = (int64_t)((uint64_t)meta[2] | (uint64_t)meta[3] << 32);
+  if (points > s->N) {
+    ref->why = MC_VOXEL_SUB_POINTS;
+    return fail(MC_ERR_INVALID, "the call brings %lld points and the cloud holds %lld: more points than it holds cannot leave (the "
+                "cloud is unchanged)", (long long)points, (long long)s->N);
+  }
+  s->built = false;   // from here the records change: a failure that is no refusal leaves no live build
+  {
+    TimedRegion tr(c, &s->ev[kRmApply], c->stream);
+    hipLaunchKernelGGL((k_vox_sub_apply<KIND, Src>), pgrid, blk, 0, c->stream, src, t, s->sums.get(), s->cnt.get(), -1);
+  }
+  {
+    TimedRegion tr(c, &s->ev[kRmCheck], c->stream);
+    HIPCHK(hipMemsetAsync(s->meta, 0xFF, sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(s->meta + 1, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_vox_sub_check, igrid, blk, 0, c->stream, t, n, (const long long*)s->sums.get(), (const uint32_t*)s->cnt.get(),
+                       s->meta.get());
+  }
+  HIPCHK(hipGetLastError());
+  // the call's second synchronisation: whether every record is still a set of points, and whether one is empty
+  if (int r = copy_back(c, meta, s->meta, 2 * sizeof(uint32_t))) return r;
+  if (meta[0] != kVoxNone) {   // the items come back: integers, so every record is what it was
+    if ((int64_t)meta[0] >= n) return fail(MC_ERR_STATE, "voxel subtract: item %u of %lld", meta[0], (long long)n);
+    {
+      TimedRegion tr(c, &s->ev[kRmApply], c->stream);
+      hipLaunchKernelGGL((k_vox_sub_apply<KIND, Src>), pgrid, blk, 0, c->stream, src, t, s->sums.get(), s->cnt.get(), 1);
+    }
+    HIPCHK(hipGetLastError());
+    uint32_t at = 0;
+    unsigned long long key = 0;
+    if (int r = copy_back(c, &at, s->slot + meta[0], sizeof at)) return r;
+    if (at > s->mask) return fail(MC_ERR_STATE, "voxel subtract: slot %u of a table of %u", at, s->mask);
+    if (int r = copy_back(c, &key, s->keys + at, sizeof key)) return r;
+    voxel_unpack(key, ref->key);
+    ref->item = (int64_t)meta[0];
+    ref->why = MC_VOXEL_SUB_REMAINDER;
+    s->built = true;
+    return MC_ERR_INVALID;
+  }
+  s->N -= points;
+  s->cent_current = false;   // as an insert: the next analysis sees the shrunk cloud
+  s->cl_current = false;
+  s->built = true;
+  if (meta[1] == 0) return MC_OK;   // no voxel emptied: no pass over the cloud or the table
+  const int64_t left = s->N;
+  if (int r = keep_flags(c, s, nullptr)) return r;
+  if (int r = keep_voxels(c, s, n_emptied)) return r;
+  if (s->N != left) {
+    s->built = false;
+    return fail(MC_ERR_STATE, "voxel subtract: the voxels kept hold %lld points of %lld", (long long)s->N, (long long)left);
+  }
+  return MC_OK;
+}
+
+// the message of a refused item (`item`: how its source names it; rule: what the filter or the record check refuses)
+int subtract_refused(const char* item, const SubRefusal& ref, const char* rule) {
+  switch (ref.why) {
+    case MC_VOXEL_SUB_ITEM:
+      return fail(MC_ERR_INVALID, "%s (the lowest refused; the cloud is unchanged): %s", item, rule);
+    case MC_VOXEL_SUB_MISSING:
+      return fail(MC_ERR_INVALID, "%s (the lowest refused; the cloud is unchanged): the cloud holds no voxel of this item", item);
+    default:
+      return fail(MC_ERR_INVALID,
+                  "%s (the lowest of its voxel; the cloud is unchanged): voxel (%d, %d, %d) would be left with a record that no set "
+                  "of points sums to: a count below 0, a count of 0 with a sum left over, a coordinate sum outside 0 .. count * 2^32 "
+                  "or an intensity sum beyond +-count * 2^32", item, ref.key[0], ref.key[1], ref.key[2]);
+  }
 }
 
 // pl_mask = the candidates inside (n, d) and their number (one synchronisation)
@@ -1054,6 +1252,101 @@ int mc_voxel_table(mc_ctx* c, int64_t* slots, int64_t* growths) {
 int mc_timing_read_voxel_insert(mc_ctx* c, double* ms_phase, int64_t* launches) {
   CHECK_ARG(c, "ctx is NULL");
   return read_phases(c, kInsertPhases, ms_phase, launches);
+}
+
+int mc_voxel_remove(mc_ctx* c, const uint8_t* d_mask, int64_t* n_removed) {
+  if (n_removed) *n_removed = 0;
+  CHECK_ARG(c && n_removed, "NULL argument");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_remove", &s)) return r;
+  if (s->M == 0) return MC_OK;
+  CHECK_ARG(d_mask, "d_mask is NULL");
+  DeviceGuard g(c->device);
+  if (int r = keep_flags(c, s, d_mask)) return r;
+  return keep_voxels(c, s, n_removed);
+}
+
+int mc_voxel_subtract_batch(mc_ctx* c, const mc_batch* in, int64_t* n_emptied, int32_t* bad_frame, int64_t* bad_index, int32_t* why) {
+  if (bad_frame) *bad_frame = -1;
+  if (bad_index) *bad_index = -1;
+  if (n_emptied) *n_emptied = 0;
+  if (why) *why = MC_VOXEL_SUB_OK;
+  CHECK_ARG(c && in && n_emptied, "NULL argument");
+  CHECK_ARG(in->ctx == c, "batch belongs to another context");
+  CHECK_ARG(in->N < kVoxelPointsEnd, "%lld points: a cloud holds fewer than 2^31 in all", (long long)in->N);
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_subtract_batch", &s)) return r;
+  DeviceGuard g(c->device);
+  SubRefusal ref;
+  const int r = subtract<kVoxBatch>(c, s, batch_source(in), in->N, in->P / 4, in->N, n_emptied, &ref);
+  if (why) *why = ref.why;
+  if (ref.item >= 0) {
+    const int32_t f = frame_of(in, ref.item);
+    if (bad_frame) *bad_frame = f;
+    if (bad_index) *bad_index = ref.item - in->doff[f];
+    char item[64];
+    std::snprintf(item, sizeof item, "frame %d, point %lld", f, (long long)(ref.item - in->doff[f]));
+    return subtract_refused(item, ref, kRefused);
+  }
+  return r;
+}
+
+int mc_voxel_subtract_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n, int64_t* n_emptied, int64_t* bad_row, int32_t* why) {
+  if (bad_row) *bad_row = -1;
+  if (n_emptied) *n_emptied = 0;
+  if (why) *why = MC_VOXEL_SUB_OK;
+  CHECK_ARG(c && n_emptied, "NULL argument");
+  CHECK_ARG(ld >= 4, "voxel rows are x, y, z, intensity: ld >= 4; got %lld", (long long)ld);
+  CHECK_ARG(n >= 0 && n < kVoxelPointsEnd, "%lld points: a cloud holds 0 to 2^31 - 1 in all", (long long)n);
+  CHECK_ARG(n == 0 || d_rows, "d_rows is NULL");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_subtract_f64", &s)) return r;
+  DeviceGuard g(c->device);
+  VoxSrc src = {};
+  src.rows = d_rows; src.ld = ld; src.n = n;
+  SubRefusal ref;
+  const int r = subtract<kVoxRows>(c, s, src, n, n, n, n_emptied, &ref);
+  if (why) *why = ref.why;
+  if (ref.item >= 0) {
+    if (bad_row) *bad_row = ref.item;
+    char item[48];
+    std::snprintf(item, sizeof item, "row %lld", (long long)ref.item);
+    return subtract_refused(item, ref, kRefused);
+  }
+  return r;
+}
+
+int mc_voxel_subtract_sums(mc_ctx* c, const int32_t* d_keys, const int32_t* d_counts, const int64_t* d_sums, int64_t m,
+                           int64_t* n_emptied, int64_t* bad_record, int32_t* why) {
+  if (bad_record) *bad_record = -1;
+  if (n_emptied) *n_emptied = 0;
+  if (why) *why = MC_VOXEL_SUB_OK;
+  CHECK_ARG(c && n_emptied, "NULL argument");
+  CHECK_ARG(m >= 0 && m < kVoxelPointsEnd, "%lld records: a subtraction takes 0 to 2^31 - 1", (long long)m);
+  CHECK_ARG(m == 0 || (d_keys && d_counts && d_sums), "d_keys, d_counts or d_sums is NULL");
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_subtract_sums", &s)) return r;
+  DeviceGuard g(c->device);
+  VoxRecSrc src = {};
+  src.keys = d_keys; src.counts = d_counts; src.sums = reinterpret_cast<const long long*>(d_sums);
+  src.n = m;
+  SubRefusal ref;
+  const int r = subtract<kVoxRecords>(c, s, src, m, m, -1, n_emptied, &ref);
+  if (why) *why = ref.why;
+  if (ref.item >= 0) {
+    if (bad_record) *bad_record = ref.item;
+    char item[48];
+    std::snprintf(item, sizeof item, "record %lld", (long long)ref.item);
+    return subtract_refused(item, ref,
+                            "a count below 1, a key outside [-2^20, 2^20), a coordinate sum outside 0 .. count * 2^32 or an intensity "
+                            "sum beyond +-count * 2^32");
+  }
+  return r;
+}
+
+int mc_timing_read_voxel_remove(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  return read_phases(c, kRemovePhases, ms_phase, launches);
 }
 
 int mc_timing_read_voxel(mc_ctx* c, double* ms_phase, int64_t* launches) {

@@ -27,6 +27,25 @@
 //   rank        the build's flag / scan / rank over the call's items: flag[p] = (first[slot[p]] == kVoxNewBit | p);
 //               the new voxels are M_old + rank, and the flagged lane puts first[slot] below kVoxNewBit again
 //   accumulate  as the build's, a record adding its sums and its n
+//
+// Taking voxels and points out (mc_voxel_remove, mc_voxel_subtract_*).  A removal keeps the survivors' order and
+// gives them ids 0 .. M' - 1; it leaves the invariant above as a growth does, the first index of every survivor 0:
+//   keep        a keep byte per voxel (not mask[v], or cnt[v] != 0), and the ascending survivor ids by the flag /
+//               scan / scatter of the selection (plane.hpp)
+//   compact     one lane per survivor j of old id v: the 32-byte record and the count into fresh arrays at j (a
+//               stable compaction in place is not safe in parallel; the arrays are swapped afterwards), its packed
+//               key, found through vslot, into an 8-byte scratch at j; the points of the survivors into one word
+//   refill      the table cleared (shrunk when the survivors fill less than an eighth of it, voxel_table_shrink_log2)
+//               and filled from the scratch as a growth fills its new one: CAS alone, vid = j, first = 0, vslot[j]
+// so its cost is that of the cloud, not of what leaves.  A subtraction costs what its items cost unless a voxel
+// empties, which ends in the removal of the voxels with cnt == 0:
+//   validate    every item quantised or checked and its key looked up, read-only: atomicMin of the lowest item the
+//               filter refuses (meta[0]) and of the lowest whose voxel the cloud lacks (meta[1]); slot[p] kept
+//   apply       the accumulate with the opposite sign; the count is a uint32 that a subtraction of more than it
+//               holds leaves at 2^31 or above (a call brings at most N < 2^31 points), read as negative
+//   check       per item its voxel's record against voxel_remainder_ok: atomicMin of the lowest item that fails
+//               (meta[0]), a flag where a count is 0 (meta[1]); on a failure apply runs again with the sign of an
+//               insert, which restores every record exactly
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -350,6 +369,152 @@ __global__ __launch_bounds__(kVoxBlock) void k_vox_accumulate_items(Src s, VoxTa
     (void)__hip_atomic_fetch_add(r + 3, (long long)q.QI, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     (void)__hip_atomic_fetch_add(cnt + vox, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   });
+}
+
+// ---- taking voxels and points out ---------------------------------------------------------------------------------------
+typedef long long vox_l2 __attribute__((ext_vector_type(2)));
+
+// *w = min(*w, p).  The word only falls, so a lane whose p is not below what it reads has nothing to add: a call
+// in which many items fail sends few atomics to the one word (~88 per microsecond, MI355X_MICROARCH.md "dequeue")
+__device__ __forceinline__ void vox_lowest(uint32_t* w, int64_t p) {
+  if ((uint32_t)p < __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(w, (uint32_t)p);
+}
+
+// *word += the workgroup's sum of v, one add per workgroup (every thread takes part)
+__device__ __forceinline__ void vox_block_add(unsigned long long v, unsigned long long* word) {
+  __shared__ unsigned long long wave_sum[kVoxBlock / 64];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long total = 0;
+#pragma unroll
+    for (int w = 0; w < kVoxBlock / 64; ++w) total += wave_sum[w];
+    if (total) atomicAdd(word, total);
+  }
+}
+
+// the keep byte of every voxel.  MASK: its mask byte is clear (mc_voxel_remove); else: its count is not 0
+template <bool MASK>
+__global__ __launch_bounds__(kVoxBlock) void k_vox_keep(const uint8_t* mask, const uint32_t* cnt, int64_t M, uint8_t* keep) {
+  const int64_t v = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
+  if (v >= M) return;
+  keep[v] = MASK ? (mask[v] == 0 ? 1 : 0) : (cnt[v] != 0 ? 1 : 0);
+}
+
+struct VoxCompact {
+  const uint32_t* ids;               // the M_keep survivors' old ids, ascending
+  int64_t M_keep;
+  const unsigned long long* keys;    // the table as it is
+  const uint32_t* vslot;
+  const long long* sums;
+  const uint32_t* cnt;
+  long long* sums_out;               // M_keep records (16-byte aligned, as sums)
+  uint32_t* cnt_out;
+  unsigned long long* keys_out;      // M_keep packed keys
+  unsigned long long* points;        // += the survivors' points
+};
+
+// one lane per survivor: its record as two 16-byte words, its count and its key to place j
+__global__ __launch_bounds__(kVoxBlock) void k_vox_compact(VoxCompact a) {
+  const int64_t j = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
+  unsigned long long pts = 0;
+  if (j < a.M_keep) {
+    const int64_t v = a.ids[j];
+    const vox_l2* r = reinterpret_cast<const vox_l2*>(a.sums + kVoxRec * v);
+    const vox_l2 lo = r[0], hi = r[1];
+    vox_l2* w = reinterpret_cast<vox_l2*>(a.sums_out + kVoxRec * j);
+    w[0] = lo;
+    w[1] = hi;
+    const uint32_t n = a.cnt[v];
+    a.cnt_out[j] = n;
+    a.keys_out[j] = a.keys[a.vslot[v]];
+    pts = n;
+  }
+  vox_block_add(pts, a.points);
+}
+
+// one lane per voxel of the compacted cloud: its key out of the scratch into the cleared table t, as k_vox_rehash
+__global__ __launch_bounds__(kVoxBlock) void k_vox_refill(const unsigned long long* keys_in, uint32_t* vslot, int64_t M, VoxTable t) {
+  const int64_t v = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
+  if (v >= M) return;
+  const unsigned long long key = keys_in[v];
+  uint32_t at = voxel_slot_first(key, t.shift, t.mask);
+  while (atomicCAS(t.keys + at, (unsigned long long)kVoxelEmpty, key) != kVoxelEmpty) at = voxel_slot_next(at, t.mask);
+  t.vid[at] = (uint32_t)v;
+  t.first[at] = 0u;
+  vslot[v] = at;
+}
+
+// meta[0] = the lowest item the filter refuses, meta[1] = the lowest whose voxel the cloud does not hold (kVoxNone:
+// none); slot[p] = the slot of the item's voxel; records: meta[2..3] += the points of the items found, as
+// k_vox_validate adds them.  The table (t.keys null: a cloud without one) is read and not written
+template <int KIND, typename Src>
+__global__ __launch_bounds__(kVoxBlock) void k_vox_sub_validate(Src s, VoxTable t, uint32_t* meta) {
+  constexpr int kPer = KIND == kVoxRecords ? kVoxPerThread : 1;
+  unsigned long long pts = 0;
+#pragma unroll
+  for (int j = 0; j < kPer; ++j) {
+    const int64_t g = ((int64_t)blockIdx.x * kPer + j) * kVoxBlock + threadIdx.x;
+    vox_items<KIND>(s, g, [&](int64_t p, const VoxelPoint& q, uint32_t n) {
+      if (q.bad) {
+        vox_lowest(meta, p);
+        t.slot[p] = kVoxNone;
+        return;
+      }
+      uint32_t at = kVoxNone;
+      if (t.keys) {   // at most half full, so the probe ends at the key or at an empty slot
+        const unsigned long long key = voxel_pack(q.k);
+        at = voxel_slot_first(key, t.shift, t.mask);
+        for (;;) {
+          const unsigned long long cur = t.keys[at];
+          if (cur == key) break;
+          if (cur == kVoxelEmpty) { at = kVoxNone; break; }
+          at = voxel_slot_next(at, t.mask);
+        }
+      }
+      if (at == kVoxNone) vox_lowest(meta + 1, p);
+      else pts += n;
+      t.slot[p] = at;
+    });
+  }
+  if constexpr (KIND == kVoxRecords) vox_block_add(pts, reinterpret_cast<unsigned long long*>(meta + 2));
+}
+
+// k_vox_accumulate_items times sign (-1: the items leave; +1: a refused call's items come back)
+template <int KIND, typename Src>
+__global__ __launch_bounds__(kVoxBlock) void k_vox_sub_apply(Src s, VoxTable t, long long* sums, uint32_t* cnt, int sign) {
+  const int64_t g = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
+  vox_items<KIND>(s, g, [&](int64_t p, const VoxelPoint& q, uint32_t n) {
+    const uint32_t at = t.slot[p];
+    if (at == kVoxNone) return;
+    const int64_t vox = t.vid[at];
+    const long long sg = sign;
+    long long* r = sums + kVoxRec * vox;
+    (void)__hip_atomic_fetch_add(r + 0, sg * (long long)q.Q[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(r + 1, sg * (long long)q.Q[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(r + 2, sg * (long long)q.Q[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(r + 3, sg * (long long)q.QI, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    (void)__hip_atomic_fetch_add(cnt + vox, sign < 0 ? 0u - n : n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  });
+}
+
+// one lane per item p < n: meta[0] = the lowest item whose voxel's record is no set of points any more, meta[1] = 1
+// where a voxel is left without points
+__global__ __launch_bounds__(kVoxBlock) void k_vox_sub_check(VoxTable t, int64_t n, const long long* sums, const uint32_t* cnt,
+                                                             uint32_t* meta) {
+  const int64_t p = (int64_t)blockIdx.x * kVoxBlock + threadIdx.x;
+  if (p >= n) return;
+  const uint32_t at = t.slot[p];
+  if (at == kVoxNone) return;
+  const int64_t vox = t.vid[at];
+  const long long* r = sums + kVoxRec * vox;
+  const int64_t S[3] = {r[0], r[1], r[2]};
+  const int64_t left = (int64_t)(int32_t)cnt[vox];   // below zero: more points taken than the voxel held
+  if (!voxel_remainder_ok(left, S, r[3])) vox_lowest(meta, p);
+  else if (left == 0 && __hip_atomic_load(meta + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+    __hip_atomic_store(meta + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 struct VoxOut {

@@ -113,6 +113,30 @@ MC_CORE_HD bool voxel_record_ok(const int32_t k[3], int64_t n, const int64_t S[3
   return SI >= -top && SI <= top;
 }
 
+// ---- shrinking a live cloud (voxel.hpp "taking voxels and points out") --------------------------------
+// The table of a cloud that a removal leaves with M_keep voxels (log2cap: its slots now, 0: no table).  It stays
+// unless the survivors fill less than an eighth of it; then it shrinks to the power of two >= 4 M_keep, at least
+// 64 slots: a quarter full at most, so the next inserts find the room a build would have left them.  Never
+// larger than it was.  -> log2 of the slots
+MC_CORE_HD int voxel_table_shrink_log2(int64_t M_keep, int log2cap) {
+  if (log2cap <= 0 || M_keep >= (((int64_t)1 << log2cap) >> 3)) return log2cap;
+  int l = kVoxelLog2Min;
+  while (l < log2cap && ((int64_t)1 << l) < 4 * M_keep) ++l;
+  return l;
+}
+
+// What a subtraction leaves of a voxel's record: n points with sums S[3] and SI.  n = 0 with every sum 0 is a
+// voxel that leaves; n >= 1 is held to what n points can sum to (voxel_record_ok's rule); anything else (n < 0,
+// n = 0 with a sum left over, a sum outside its range) is no set of points.
+MC_CORE_HD bool voxel_remainder_ok(int64_t n, const int64_t S[3], int64_t SI) {
+  if (n < 0 || n >= kVoxelPointsEnd) return false;
+  if (n == 0) return S[0] == 0 && S[1] == 0 && S[2] == 0 && SI == 0;
+  const int64_t top = n << 32;   // < 2^63
+  for (int c = 0; c < 3; ++c)
+    if (S[c] < 0 || S[c] > top) return false;
+  return SI >= -top && SI <= top;
+}
+
 // one voxel: out = cx, cy, cz, intensity (n >= 1)
 MC_CORE_HD void voxel_finalise(const int32_t k[3], const int64_t S[3], int64_t SI, int64_t n, double h,
                                 const double o[3], double out[4]) {

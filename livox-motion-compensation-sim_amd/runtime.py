@@ -376,6 +376,11 @@ class Context:
         """Event time (ms) of the phases of VoxelCloud.insert / .merge since the last read (mc_timing_read_voxel_insert)."""
         return self._read_phases("timing_read_voxel_insert", ("validate_ms", "insert_ms", "rank_ms", "accumulate_ms"))
 
+    def read_timing_voxel_remove(self) -> dict:
+        """Event time (ms) of the phases of VoxelCloud.remove / .subtract since the last read (mc_timing_read_voxel_remove);
+        a removal is all compact: the keep flags, the survivors' ids and records, the table's refill."""
+        return self._read_phases("timing_read_voxel_remove", ("validate_ms", "apply_ms", "check_ms", "compact_ms"))
+
     def read_timing_normals(self) -> dict:
         """Event time (ms) of the phases of VoxelCloud.normals since the last read (mc_timing_read_normals)."""
         return self._read_phases("timing_read_normals", ("centroids_ms", "window_ms", "cap_ms"))

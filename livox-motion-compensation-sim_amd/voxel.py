@@ -5,6 +5,7 @@ of a drive are accumulated into one cloud and most points re-observe the same su
   voxel_downsample(batch_or_rows, voxel, origin=(0, 0, 0))  -> VoxelCloud
   VoxelCloud.n_voxels, .n_points, .batch(), .rows(), .point_counts(), .keys(), .close()
   VoxelCloud.insert(batch_or_rows)  -> int, .state()  -> VoxelSums, .merge(state)  -> int
+  VoxelCloud.remove(mask)  -> int, .subtract(batch_or_rows_or_state)  -> int
   VoxelCloud.normals(radius, max_nn=30, viewpoint=None, covariance=False)  -> VoxelNormals
   VoxelCloud.clusters(eps, min_points=10, weighted=False)  -> VoxelClusters
   VoxelCloud.segment_plane(distance_threshold, num_iterations=1000, seed=0, refine=True, among=None)  -> VoxelPlane
@@ -48,6 +49,26 @@ Refused with ValueError, the cloud left bit for bit as it was: a point the filte
 1, a key outside [-2^20, 2^20), a coordinate sum outside 0 .. n 2^32 or an intensity sum beyond +-n 2^32 (the message
 names the lowest refused item), a call that would bring the cloud to 2^31 points, a batch of another context, rows that
 are not (N, >= 4), a state of another grid or with arrays of the wrong dtype or shape.
+
+Shrinking a cloud (csrc/voxel.hpp "taking voxels and points out"; ``mc_voxel_remove``, ``mc_voxel_subtract_*``): the way
+out is as exact as the way in.  ``remove(mask)`` takes whole voxels out — ``remove(plane.inliers)`` is the cloud without
+its ground, ``remove(labels < 0)`` the cloud without its noise — and the survivors keep their order with ids 0 .. M' - 1:
+the cloud is then bit for bit ``voxel_downsample`` of its sources without the removed voxels' points.  ``subtract(src)``
+takes points out: every item is quantised or checked on the cloud's grid as an insert's, its Q, QI and n leave its voxel's
+record, and a voxel whose count reaches 0 leaves as in ``remove``.  ``insert(B); subtract(B)`` and ``merge(s); subtract(s)``
+are the identity in every field, whatever voxels B shares with the cloud; for ``voxel_downsample(A ++ B)``, ``subtract(A)``
+leaves exactly the records of ``voxel_downsample(B)``, in the relative order they had (a one-shot build may number them
+differently: a voxel's first point may have been one of A's).  A frame that was corrected leaves before its correction
+enters; a sliding window forgets what it inserted first.  The cloud cannot know whether the subtracted points were ever
+inserted: that is the caller's contract.  Refused with ValueError, the cloud left bit for bit as it was: what ``insert`` /
+``merge`` refuse of an item, an item whose voxel the cloud does not hold (the lowest item of either kind is named), a call
+that brings more points than the cloud holds, and a voxel left with a record that no set of points can sum to — a count
+below 0, a count of 0 with a sum that is not 0, a count n' >= 1 with a coordinate sum outside 0 .. n' 2^32 or an intensity
+sum beyond +-n' 2^32 (the lowest item of such a voxel and the voxel's key are named); a mask that is not (M,) bool.  A
+``subtract`` that empties no voxel costs what its items cost; ``remove``, and a ``subtract`` that empties one, cost what
+the cloud costs (one pass over the survivors' records, the key table cleared and refilled; it shrinks when the survivors
+fill less than an eighth of it).  Not built: tombstones (a removal that costs what leaves, at a compare in every probe
+loop), ``subtract(batch, frame=f)``, normals kept across a removal.
 
 Surface normals (csrc/normals_core.hpp, csrc/normals.hpp; ``mc_voxel_normals``): what the reference's
 viewer computes with open3d on every cloud without normals (read_pointcloud.py:81-84), here from the live
@@ -546,6 +567,74 @@ class VoxelCloud:
             check(ctx.lib.mc_voxel_merge_sums(ctx.handle, d[0].ptr, d[1].ptr, d[2].ptr, m, ctypes.byref(new), ctypes.byref(bad)),
                   "merge")
         return self._grown(new.value)
+
+    def _shrunk(self, n_gone):
+        """After a remove or a subtract: M and N from the call and the library."""
+        self.n_voxels -= int(n_gone)
+        n = c_int64(0)
+        check(self.ctx.lib.mc_voxel_points(self.ctx.handle, ctypes.byref(n)), "voxel points")
+        self.n_points = n.value
+        return int(n_gone)
+
+    def remove(self, mask) -> int:
+        """The voxels whose ``mask`` entry is True — a (M,) bool in the cloud's order, as ``segment_plane(...).inliers``
+        or ``clusters(...).labels < 0`` — out of the cloud (module docstring; include/mcdeskew.h ``mc_voxel_remove``).
+        The survivors keep their order and get ids 0 .. M' - 1: afterwards the cloud is bit for bit
+        ``voxel_downsample`` of its sources without the removed voxels' points.  -> the number of voxels removed.
+        An all-False mask touches nothing.  The cost is that of the cloud, not of what leaves."""
+        m = _mask_arg(mask, self.n_voxels, "mask")
+        self._live()
+        if len(m) == 0:
+            return 0
+        ctx = self.ctx
+        with _Buffers(ctx) as bufs:
+            buf = bufs.take(len(m))
+            buf.from_host(m)
+            gone = c_int64(0)
+            check(ctx.lib.mc_voxel_remove(ctx.handle, buf.ptr, ctypes.byref(gone)), "remove")
+        return self._shrunk(gone.value)
+
+    def subtract(self, src) -> int:
+        """The points of ``src`` — a device Batch of the cloud's context, host float64 rows (N, >= 4), or a
+        :class:`VoxelSums` of this very grid, each record standing for its n points — out of the cloud, on its own
+        grid (module docstring; include/mcdeskew.h ``mc_voxel_subtract_*``).  ``insert(src)`` then ``subtract(src)``
+        is the identity, bit for bit; a voxel whose count reaches 0 leaves as in :meth:`remove`.  -> the number of
+        voxels that became empty and left.  The cloud cannot know whether the points were ever inserted: that they
+        were is the caller's contract, and only what cannot be true is refused — a point the filter refuses, a voxel
+        the cloud does not hold, more points than the cloud or a voxel holds, a sum no remaining points can have —
+        with ValueError naming the lowest such item, the cloud left bit for bit as it was."""
+        why = c_int32(0)
+        ctx = self.ctx
+        gone = c_int64(0)
+        if hasattr(src, "sums") and hasattr(src, "voxel"):
+            keys, counts, sums = _sums_arg(src, self._h, self._origin)
+            self._live()
+            if len(keys) == 0:
+                return 0
+            with _Buffers(ctx) as bufs:
+                d = [bufs.take(a.nbytes) for a in (keys, counts, sums)]
+                for buf, a in zip(d, (keys, counts, sums)):
+                    buf.from_host(a)
+                bad = c_int64(-1)
+                check(ctx.lib.mc_voxel_subtract_sums(ctx.handle, d[0].ptr, d[1].ptr, d[2].ptr, len(keys), ctypes.byref(gone),
+                                                     ctypes.byref(bad), ctypes.byref(why)), "subtract")
+            return self._shrunk(gone.value)
+        batch, rows, n = _insert_arg(ctx, src, MAX_POINTS)
+        self._live()
+        if n == 0:
+            return 0
+        if batch is not None:
+            bf, bi = c_int32(-1), c_int64(-1)
+            check(ctx.lib.mc_voxel_subtract_batch(ctx.handle, batch.handle, ctypes.byref(gone), ctypes.byref(bf), ctypes.byref(bi),
+                                                  ctypes.byref(why)), "subtract")
+        else:
+            with _Buffers(ctx) as bufs:
+                d_rows = bufs.take(rows.nbytes)
+                d_rows.from_host(rows)
+                bad = c_int64(-1)
+                check(ctx.lib.mc_voxel_subtract_f64(ctx.handle, d_rows.ptr, rows.shape[1], n, ctypes.byref(gone), ctypes.byref(bad),
+                                                    ctypes.byref(why)), "subtract")
+        return self._shrunk(gone.value)
 
     def batch(self, with_pcd_len: bool = False) -> Batch:
         """A one-frame float32 Batch of the voxel points (x, y, z, intensity; no time column), ready for
