@@ -832,6 +832,57 @@ int mc_voxel_register_frames(mc_ctx* ctx, const mc_batch* src, const mc_register
  * and the records, on the device); *launches = timed regions */
 int mc_timing_read_register_frames(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 
+/* ---- rays through the voxel cloud (csrc/rays_core.hpp, rays.hpp) --------------------------------------------------
+ * Which voxels of the map a new scan contradicts: the ray of every source point, from the sensor position to the
+ * point, walked through the grid of the live build, and per voxel the number of rays that passed through it and the
+ * number that ended in it.  A voxel many beams pass and none ends in is free space the map still believes occupied (a
+ * parked wagon that has left, a person who walked through, a ghost from a bad pose): mc_voxel_remove of
+ * (passed >= k and ended == 0) carves it.  The build is read and never changed.  The source is as the registration's
+ * (a batch: its float32 x, y, z read as float64, padding slots no points, frame -1: every frame; or device float64
+ * rows, ld >= 3); the sensor positions are in the cloud's frame.  With h and o the build's voxel size and origin;
+ * every float64 line ONE IEEE operation, no contraction:
+ *   grid     per axis a, for the sensor position s and the point e, the voxel filter's own lines:
+ *              as = s - o   gs = as / h   ks = floor(gs)        ae = e - o   ge = ae / h   ke = floor(ge)
+ *            so ke is exactly the cell an insert puts the point in
+ *   skipped  a ray whose s or e the filter refuses with the intensity taken as 0.0 (a coordinate or g that is not
+ *            finite, a key outside [-2^20, 2^20)), or whose walk has more than max_steps steps.  It counts nowhere,
+ *            its `through` is -1, and it is counted in stats[1]: not an error, as a point without a cell is none to
+ *            mc_voxel_nearest_*
+ *   walk     d_a = ge_a - gs_a;  dir_a = +1 when ke_a > ks_a, -1 when ke_a < ks_a, else 0;  n_a = |ke_a - ks_a|;
+ *            steps = n_x + n_y + n_z: the walk has exactly that many transitions and always ends in ke.  The j-th
+ *            crossing on axis a (j = 0 .. n_a - 1) has
+ *              b = double(ks_a + j * dir_a + (dir_a > 0 ? 1 : 0));  u = b - gs_a;  t_a(j) = u / d_a
+ *            computed from j, never accumulated; an axis with its n_a crossings done has t_a = +inf.  Each
+ *            transition takes the axis of smallest current t_a, ties to the lowest axis, and moves one cell along it.
+ *            No comparison sees a NaN: n_a > 0 implies d_a != 0
+ *   cells    position 0 is ks, position `steps` is ke; the cells of one walk are distinct, so a ray adds at most 1 to
+ *            a voxel
+ *            ended   the voxel of ke, when the cloud holds one, gets +1
+ *            passed  the voxels of positions 0 .. steps - 1 - guard, where the cloud holds them, get +1 each; a guard
+ *                    larger than the walk leaves none.  guard is a number of cells, integer and exact: it keeps a
+ *                    beam that grazes the surface it ends on from carving that surface
+ * d_passed, d_ended (M,) int32 in the cloud's order (NULL allowed when M = 0); d_through (N,) int32 in the source's
+ * point order: the occupied voxels the ray was counted as passing, -1 for a skipped ray (which points lie behind
+ * surfaces the map believes in); stats[4] = rays, skipped, steps (the transitions of every walked ray), 0.  The counts
+ * are 32-bit integer atomic adds and a call takes fewer than 2^31 rays, so they do not depend on the order the atomics
+ * arrive in: the same bits on every run.  One launch and one synchronisation per call.
+ * mc_voxel_rays_batch: origins is HOST memory, n_origins rows of 3: 1 (every frame) or F (one per frame; with a
+ * frame given, that frame's row is used).  mc_voxel_rays_f64: d_origins is DEVICE memory, 1 or n rows of 3; the host
+ * does not read them, and a row that is not finite has its ray skipped.
+ * MC_ERR_INVALID before any launch: a NULL ctx, stats, source, origins or d_through, d_passed or d_ended NULL with
+ * M > 0, a batch of another context, a frame outside the batch, an empty source, 2^31 points or more, ld < 3, a count
+ * of origins that is neither 1 nor F (n), host origins that are not finite, guard outside 0 .. 255, max_steps outside
+ * 1 .. 2^22.  No successful build: MC_ERR_STATE.  An empty cloud (M = 0) still walks: through is 0 or -1. */
+int mc_voxel_rays_batch(mc_ctx* ctx, const mc_batch* src, int32_t frame, const double* origins, int64_t n_origins,
+                        int32_t guard, int32_t max_steps, int32_t* d_passed, int32_t* d_ended, int32_t* d_through,
+                        int64_t* stats);
+int mc_voxel_rays_f64(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t n, const double* d_origins, int64_t n_origins,
+                      int32_t guard, int32_t max_steps, int32_t* d_passed, int32_t* d_ended, int32_t* d_through,
+                      int64_t* stats);
+/* event time (ms) of the phases since the last read: ms_phase[2] = clear (passed, ended and the counters zeroed),
+ * walk; *launches = timed regions */
+int mc_timing_read_voxel_rays(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

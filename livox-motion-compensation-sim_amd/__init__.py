@@ -37,7 +37,10 @@ Drop-in surface (reference file:line in each docstring):
                          VoxelCloud.register(src, max_distance, init, ...) -> VoxelRegistration, a scan registered
                          against the cloud by point-to-plane ICP, the whole iteration history the same on every run;
                          VoxelCloud.register_frames(batch, max_distance, init, ...) -> VoxelFrameRegistrations, every
-                         frame of a batch registered on its own in one call, row f bit for bit register(..., frame=f)
+                         frame of a batch registered on its own in one call, row f bit for bit register(..., frame=f);
+                         VoxelCloud.rays(src, origins, guard=1, max_steps=4096, frame) -> VoxelRays, the rays of a scan
+                         walked through the cloud: per voxel the beams that passed it and that ended in it (free-space
+                         carving: remove((passed >= k) & (ended == 0))), integer counts, the same on every run
 Device layer: Context, Batch (blocked-CSR float32 columns in HBM); multi-GPU: dist.
 """
 from . import _lib, codecs, config, coords, csim_export, dist, ingest, las, raymarch, runtime, trajectory, voxel  # noqa: F401
@@ -53,6 +56,6 @@ from .raymarch import LiDARSimulator  # noqa: F401
 from .runtime import Batch, Context, default_context  # noqa: F401
 from .simulator import LiDARMotionSimulator  # noqa: F401
 from .voxel import (VoxelCloud, VoxelClusters, VoxelFrameRegistrations, VoxelNearest, VoxelNormals, VoxelPlane,  # noqa: F401
-                    VoxelRegistration, VoxelSums, voxel_downsample)  # noqa: F401
+                    VoxelRays, VoxelRegistration, VoxelSums, voxel_downsample)  # noqa: F401
 
 __version__ = "0.1.0"

@@ -173,6 +173,11 @@ _SIGS = {
     "mc_voxel_register_batch": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, _pd, _pd, _pi64]),
     "mc_voxel_register_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, _pd, _pd, _pi64]),
     "mc_timing_read_register": (c_int, [c_void_p, _pd, _pi64]),
+    # the rays of a source through the voxel cloud (batch: host origins; rows: device origins)
+    "mc_voxel_rays_batch": (c_int, [c_void_p, c_void_p, c_int32, _pd, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p, _pi64]),
+    "mc_voxel_rays_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                  c_void_p, _pi64]),
+    "mc_timing_read_voxel_rays": (c_int, [c_void_p, _pd, _pi64]),
     # every frame of a batch registered in one call (inits: F x 16 or NULL)
     "mc_voxel_register_frames": (c_int, [c_void_p, c_void_p, c_void_p, _pd, _pd, _pd, _pi64]),
     "mc_timing_read_register_frames": (c_int, [c_void_p, _pd, _pi64]),

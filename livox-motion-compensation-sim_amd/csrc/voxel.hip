@@ -7,13 +7,15 @@
 // (mc_voxel_clusters; kernels in cluster.hpp) read that state and keep theirs in it; so do its plane segmentation
 // and the selection of a subset into a batch (mc_voxel_plane, mc_voxel_emit_selected; kernels in plane.hpp), and the
 // registration of a source against the cloud (mc_voxel_nearest_*, mc_voxel_register_*, and every frame of a batch
-// on its own in one call, mc_voxel_register_frames; kernels in register.hpp).
+// on its own in one call, mc_voxel_register_frames; kernels in register.hpp), and the walk of a scan's rays through the
+// cloud (mc_voxel_rays_*; kernel in rays.hpp).
 #include "../../include/mcdeskew.h"
 #include "voxel.hpp"
 #include "normals.hpp"
 #include "cluster.hpp"
 #include "plane.hpp"
 #include "register.hpp"
+#include "rays.hpp"
 #include "internal.hpp"
 #include "hostutil.hpp"
 
@@ -38,16 +40,18 @@ enum {
   kRfNormals, kRfStep, kRfTree, kRfSolve,
   kInsValidate, kInsInsert, kInsRank, kInsAccumulate,   // growing the live cloud; the insert's phase holds the table's growth
   kRmValidate, kRmApply, kRmCheck, kRmCompact,          // shrinking it; the compact phase holds the keep flags and the table's refill
+  kRyClear, kRyWalk,                                    // the rays through it
   kAllPhases
 };
 struct PhaseRange { int first, count; };
 constexpr PhaseRange kFilterPhases = {kInsert, 4}, kNormalsPhases = {kNrmCentroids, 3}, kClPhases = {kClDensity, kClusterPhases},
                      kPlanePhases = {kPlCompact, 6}, kRegPhases = {kRgNormals, 4}, kRegFramesPhases = {kRfNormals, 4},
-                     kInsertPhases = {kInsValidate, 4}, kRemovePhases = {kRmValidate, 4};
+                     kInsertPhases = {kInsValidate, 4}, kRemovePhases = {kRmValidate, 4}, kRaysPhases = {kRyClear, 2};
 constexpr int kRgSolve = 4;   // its public index
 constexpr int kVoxMeta = 4;   // the words of VoxTable::meta
 static_assert(kRegPhases.first + kRegPhases.count == kRfNormals && kRegFramesPhases.first + kRegFramesPhases.count == kInsValidate &&
-              kInsertPhases.first + kInsertPhases.count == kRmValidate && kRemovePhases.first + kRemovePhases.count == kAllPhases &&
+              kInsertPhases.first + kInsertPhases.count == kRmValidate && kRemovePhases.first + kRemovePhases.count == kRyClear &&
+              kRaysPhases.first + kRaysPhases.count == kAllPhases &&
               kClPhases.first + kClPhases.count == kPlCompact, "the ranges");
 
 struct VoxState : mcimpl::CtxExt {
@@ -104,6 +108,9 @@ struct VoxState : mcimpl::CtxExt {
   // the word that takes their points
   DevBuf<uint8_t> rm_keep;
   DevBuf<unsigned long long> rm_keys, rm_points;
+  // the rays of a call: the sensor positions of a batch's frames, and the skipped rays and the transitions walked
+  DevBuf<double> ry_origins;
+  DevBuf<unsigned long long> ry_meta;
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
@@ -1076,6 +1083,59 @@ int register_frames_run(mc_ctx* c, const mc_batch* in, const mc_register_params*
   return MC_OK;
 }
 
+// ---- the rays of a source through the cloud ---------------------------------------------------------------------------
+// a: the source and the sensor positions set; the walk of every ray (include/mcdeskew.h mc_voxel_rays_*): one clear,
+// one launch, one synchronisation with the two counters copied
+template <bool BATCH>
+int rays_run(mc_ctx* c, VoxState* s, RaysArgs a, int64_t n, int64_t lanes, int32_t guard, int32_t max_steps, int32_t* d_passed,
+             int32_t* d_ended, int32_t* d_through, int64_t* stats) {
+  const int64_t M = s->M;
+  a.G = {};
+  a.G.M = M;
+  a.G.h = s->h;
+  std::copy_n(s->o, 3, a.G.o);
+  if (M > 0) a.G.g = grid_of(s);   // the centroids are not read
+  a.guard = guard;
+  a.max_steps = max_steps;
+  a.passed = d_passed; a.ended = d_ended; a.through = d_through;
+  if (int r = ctx_reserve(c, s->ry_meta, (size_t)kRaysMeta)) return r;
+  a.meta = s->ry_meta;
+  {
+    TimedRegion tr(c, &s->ev[kRyClear], c->stream);
+    if (M > 0) {
+      HIPCHK(hipMemsetAsync(d_passed, 0, (size_t)M * sizeof(int32_t), c->stream));
+      HIPCHK(hipMemsetAsync(d_ended, 0, (size_t)M * sizeof(int32_t), c->stream));
+    }
+    HIPCHK(hipMemsetAsync(s->ry_meta, 0, kRaysMeta * sizeof(unsigned long long), c->stream));
+  }
+  {
+    TimedRegion tr(c, &s->ev[kRyWalk], c->stream);
+    hipLaunchKernelGGL(k_rays_walk<BATCH>, dim3(blocks_of(lanes)), dim3(kVoxBlock), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  unsigned long long meta[kRaysMeta] = {0, 0};
+  if (int r = copy_back(c, meta, s->ry_meta, sizeof meta)) return r;
+  if ((int64_t)meta[kRaysMetaSkipped] > n || meta[kRaysMetaSteps] > (unsigned long long)n * (unsigned long long)max_steps)
+    return fail(MC_ERR_STATE, "voxel rays: %llu skipped and %llu steps of %lld rays of at most %d steps", meta[kRaysMetaSkipped],
+                meta[kRaysMetaSteps], (long long)n, max_steps);
+  stats[0] = n;
+  stats[1] = (int64_t)meta[kRaysMetaSkipped];
+  stats[2] = (int64_t)meta[kRaysMetaSteps];
+  stats[3] = 0;
+  return MC_OK;
+}
+
+// what both entry points check of their plain arguments, and the state of the live build
+int rays_checks(mc_ctx* c, int32_t guard, int32_t max_steps, const int32_t* d_passed, const int32_t* d_ended,
+                const int32_t* d_through, const char* who, VoxState** s) {
+  CHECK_ARG(guard >= 0 && guard <= kRaysMaxGuard, "guard must be in 0..%d (got %d)", kRaysMaxGuard, guard);
+  CHECK_ARG(max_steps >= 1 && max_steps <= kRaysMaxSteps, "max_steps must be in 1..%d (got %d)", kRaysMaxSteps, max_steps);
+  CHECK_ARG(d_through, "d_through is NULL");
+  if (int r = live_build(c, who, s)) return r;
+  CHECK_ARG((*s)->M == 0 || (d_passed && d_ended), "d_passed or d_ended is NULL");
+  return MC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1641,6 +1701,60 @@ int mc_timing_read_register(mc_ctx* c, double* ms_phase, int64_t* launches) {
     s->rg_solve_n = 0;
   }
   return MC_OK;
+}
+
+static void rays_clear(int64_t* stats) {
+  if (stats) std::fill_n(stats, 4, (int64_t)0);
+}
+
+int mc_voxel_rays_batch(mc_ctx* c, const mc_batch* src, int32_t frame, const double* origins, int64_t n_origins, int32_t guard,
+                        int32_t max_steps, int32_t* d_passed, int32_t* d_ended, int32_t* d_through, int64_t* stats) {
+  rays_clear(stats);
+  CHECK_ARG(c && stats, "ctx or stats is NULL");
+  RegSrc rs;   // the checks of a source, and its first point and their number
+  if (int r = reg_source_batch(c, src, frame, &rs)) return r;
+  CHECK_ARG(origins, "origins is NULL");
+  CHECK_ARG(n_origins == 1 || n_origins == src->F, "origins must be 1 or %d (one per frame) rows of 3, got %lld", src->F,
+            (long long)n_origins);
+  for (int64_t k = 0; k < 3 * n_origins; ++k)
+    CHECK_ARG(std::isfinite(origins[k]), "origins must be finite (row %lld, axis %d: %g)", (long long)(k / 3), (int)(k % 3), origins[k]);
+  VoxState* s;
+  if (int r = rays_checks(c, guard, max_steps, d_passed, d_ended, d_through, "mc_voxel_rays_batch", &s)) return r;
+  DeviceGuard g(c->device);
+  if (int r = ctx_reserve(c, s->ry_origins, (size_t)(3 * n_origins))) return r;
+  HIPCHK(hipMemcpyAsync(s->ry_origins, origins, (size_t)(3 * n_origins) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  RaysArgs a = {};
+  a.src = batch_source(src);
+  a.slot0 = frame < 0 ? 0 : src->poff[frame];
+  a.slots = frame < 0 ? src->P : src->poff[frame + 1] - src->poff[frame];
+  a.first = rs.first;
+  a.origins = s->ry_origins;
+  a.n_origins = n_origins;
+  return rays_run<true>(c, s, a, rs.n, a.slots, guard, max_steps, d_passed, d_ended, d_through, stats);
+}
+
+int mc_voxel_rays_f64(mc_ctx* c, const double* d_rows, int64_t ld, int64_t n, const double* d_origins, int64_t n_origins,
+                      int32_t guard, int32_t max_steps, int32_t* d_passed, int32_t* d_ended, int32_t* d_through, int64_t* stats) {
+  rays_clear(stats);
+  CHECK_ARG(c && stats, "ctx or stats is NULL");
+  RegSrc rs;
+  if (int r = reg_source_rows(d_rows, ld, n, &rs)) return r;
+  CHECK_ARG(d_origins, "d_origins is NULL");
+  CHECK_ARG(n_origins == 1 || n_origins == n, "origins must be 1 or %lld (one per row) rows of 3, got %lld", (long long)n,
+            (long long)n_origins);
+  VoxState* s;
+  if (int r = rays_checks(c, guard, max_steps, d_passed, d_ended, d_through, "mc_voxel_rays_f64", &s)) return r;
+  DeviceGuard g(c->device);
+  RaysArgs a = {};
+  a.src.rows = d_rows; a.src.ld = ld; a.src.n = n;
+  a.origins = d_origins;
+  a.n_origins = n_origins;
+  return rays_run<false>(c, s, a, n, n, guard, max_steps, d_passed, d_ended, d_through, stats);
+}
+
+int mc_timing_read_voxel_rays(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  return read_phases(c, kRaysPhases, ms_phase, launches);
 }
 
 int mc_voxel_release(mc_ctx* c) {

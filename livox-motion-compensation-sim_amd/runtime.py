@@ -400,6 +400,11 @@ class Context:
         (mc_timing_read_register); the solve is the host's, by its clock."""
         return self._read_phases("timing_read_register", ("normals_ms", "correspond_ms", "leaves_ms", "tree_ms", "solve_ms"))
 
+    def read_timing_voxel_rays(self) -> dict:
+        """Event time (ms) of the phases of VoxelCloud.rays since the last read (mc_timing_read_voxel_rays): the clear of
+        the counts, then the walk of every ray."""
+        return self._read_phases("timing_read_voxel_rays", ("clear_ms", "walk_ms"))
+
     def read_timing_register_frames(self) -> dict:
         """Event time (ms) of the phases of VoxelCloud.register_frames since the last read
         (mc_timing_read_register_frames): the normals once per call, then per iteration the step over the live

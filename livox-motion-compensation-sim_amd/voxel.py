@@ -15,6 +15,7 @@ of a drive are accumulated into one cloud and most points re-observe the same su
                       tol_rotation=1e-6, tol_translation=1e-6, frame=None)  -> VoxelRegistration
   VoxelCloud.register_frames(batch, max_distance, init=None, max_iterations=30, normals_radius=None, max_nn=30,
                              tol_rotation=1e-6, tol_translation=1e-6)  -> VoxelFrameRegistrations
+  VoxelCloud.rays(src, origins, guard=1, max_steps=4096, frame=None)  -> VoxelRays
 
 One output point per occupied voxel: the mean of the voxel's points and of their intensities.  The
 per-voxel sums are integers (the coordinate inside its voxel in 2^-32 voxel units, the intensity in
@@ -164,6 +165,38 @@ the others go on.  An empty frame is not an error: status "empty", its init as t
 ``ctx.transform_affine(batch, mats=r.transformations)`` is the corrected batch.  Refused with ValueError: what
 ``register`` refuses, a source that is not a Batch of this context, an init that is not None, one 4 x 4 or (F, 4, 4)
 (the message names the frame), and F x max_iterations above 2^22 history rows.
+
+Seeing through the cloud (csrc/rays_core.hpp, csrc/rays.hpp; ``mc_voxel_rays_*``): which voxels of the map a new scan
+contradicts.  ``rays`` walks the ray of every source point, from the sensor position to the point, through the cloud's
+grid and counts per voxel the rays that passed through it and the rays that ended in it; the cloud is read and never
+changed.  A parked wagon that has left, a person who walked through, a ghost from a bad pose: voxels that later beams
+pass and none ends in, and ``cloud.remove((r.passed >= k) & (r.ended == 0))`` carves them out.  ``through`` tells which
+new points lie behind surfaces the map believes in.  The counts are integer atomic adds, the same bits on every run,
+and equal to the restatement of tests/rays.py.  With h and o the cloud's; every float64 line is one IEEE operation:
+
+  grid     per axis a, for the origin s and the endpoint e, the filter's own lines:
+             as = s - o;  gs = as / h;  ks = floor(gs)        ae = e - o;  ge = ae / h;  ke = floor(ge)
+           so ke is exactly the cell insert would put the point in
+  skipped  a ray whose origin or endpoint the filter refuses (intensity taken as 0.0: not finite, or a key outside
+           [-2^20, 2^20)), or whose walk has more than max_steps steps.  It counts nowhere, its ``through`` is -1, and it
+           is counted in n_skipped: not an error, as ``nearest`` treats a point without a cell
+  walk     d_a = ge_a - gs_a;  dir_a = +1 if ke_a > ks_a, -1 if ke_a < ks_a, 0 if equal;  n_a = |ke_a - ks_a|;
+           steps = n_x + n_y + n_z: the walk has exactly that many transitions and always ends in ke.  The j-th crossing
+           on axis a (j = 0 .. n_a - 1) has
+             b = double(ks_a + j * dir_a + (dir_a > 0 ? 1 : 0));  u = b - gs_a;  t_a(j) = u / d_a
+           computed afresh from j, never accumulated; an axis with all its n_a crossings done has t_a = +inf.  Each
+           transition takes the axis with the smallest current t_a, ties to the lowest axis, and moves one cell along
+           it.  A comparison involving a NaN cannot occur: n_a > 0 implies d_a != 0
+  cells    position 0 is the origin's cell ks, position ``steps`` is ke
+           ended: the voxel of ke, if the cloud holds one, gets +1
+           passed: the voxels of positions 0 .. steps - 1 - guard, where the cloud holds them, get +1 each; a guard
+           larger than the walk leaves none.  The cells of one walk are distinct: a ray adds at most 1 to any voxel
+
+``guard`` is a number of cells, integer and exact: it keeps a beam that grazes the surface it ends on from carving that
+surface.  Refused with ValueError: a batch of another context, rows that are not (N, >= 3), an empty source, 2^31 points
+or more, a frame outside the batch or given with rows, origins that are not finite float64 of shape (3,) or (F, 3) for
+a Batch, (3,) or (N, 3) for rows (the message names the shape), guard not an integer in 0..255, max_steps not an
+integer in 1..2^22.  Not built: a per-point origin inside a frame of a Batch, beam divergence, occupancy probabilities.
 """
 from __future__ import annotations
 
@@ -397,6 +430,38 @@ def _source_arg(ctx, src, frame):
     if a.shape[0] > MAX_POINTS:
         raise ValueError(f"{a.shape[0]} points: a source takes fewer than 2^31")
     return None, -1, np.ascontiguousarray(a, dtype=np.float64), a.shape[0]
+
+
+MAX_RAY_GUARD = 255
+MAX_RAY_STEPS = 2 ** 22
+
+
+class VoxelRays(NamedTuple):
+    """What :meth:`VoxelCloud.rays` returns: per voxel in the cloud's order, then per ray in the source's point order."""
+    passed: np.ndarray      # (M,) int32 the rays that crossed the voxel before their end (the guard cells left out)
+    ended: np.ndarray       # (M,) int32 the rays whose endpoint lies in the voxel
+    through: np.ndarray     # (N,) int32 the occupied voxels the ray was counted as passing; -1: the ray was skipped
+    n_rays: int             # N
+    n_skipped: int          # rays with an end the filter refuses, or a walk of more than max_steps steps
+    steps: int              # the cell transitions of every walked ray together
+
+
+def _origins_arg(origins, per, kind):
+    """The sensor positions as contiguous float64 (1, 3) or (per, 3), from (3,) or (per, 3) — ``kind`` names what ``per``
+    counts: the frames of a Batch or the rows — checked before a device is touched."""
+    allowed = f"(3,) or ({per}, 3), one per {kind}"
+    try:
+        o = np.asarray(origins)
+        if o.dtype.kind not in "fiu":
+            raise TypeError
+        o = np.ascontiguousarray(o, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"origins must be finite float64 of shape {allowed}; got {origins!r}") from None
+    if o.shape != (3,) and o.shape != (per, 3):
+        raise ValueError(f"origins must be finite float64 of shape {allowed}; got shape {o.shape}")
+    if not np.isfinite(o).all():
+        raise ValueError(f"origins must be finite float64 of shape {allowed}; got a value that is not finite")
+    return o.reshape(-1, 3)
 
 
 def _frame_poses_arg(init, F):
@@ -860,6 +925,39 @@ class VoxelCloud:
         rmse = np.array([math.sqrt(float(s) / int(p)) if p else 0.0 for s, p in zip(last, pairs)], np.float64)
         history = np.ascontiguousarray(history[:, :int(done.max()) if F else 0])
         return VoxelFrameRegistrations(out, fitness, rmse, pairs, done, stats[:, 2].astype(np.int8), history)
+
+    def rays(self, src, origins, guard: int = 1, max_steps: int = 4096, frame=None) -> "VoxelRays":
+        """The ray of every point of ``src``, from its sensor position to the point, walked through the cloud's grid:
+        per voxel the rays that passed through it and the rays that ended in it, per ray the occupied voxels it passed
+        (module docstring "Seeing through the cloud"; include/mcdeskew.h ``mc_voxel_rays_*``).  ``src``: a device Batch
+        (``frame=f``: that frame alone) or host float64 rows (N, >= 3).  ``origins``: the sensor positions, already in
+        the cloud's frame: (3,) for all, or (F, 3), one per frame of a Batch, or (N, 3), one per row.  ``guard``: the
+        last cells before a ray's end that do not count as passed, so a beam that grazes the surface it ends on does
+        not carve it.  A ray with an end outside the grid, or of more than ``max_steps`` cells, is skipped: its
+        ``through`` is -1.  The intended use is ``cloud.remove((r.passed >= k) & (r.ended == 0))``: the voxels that k
+        beams saw through and none stopped in.  The cloud is not changed; any number of calls on one live cloud."""
+        batch, f, rows, n = _source_arg(self.ctx, src, frame)
+        o = _origins_arg(origins, batch.n_frames, "frame") if batch is not None else _origins_arg(origins, n, "row")
+        g = _integer(guard, "guard", 0, MAX_RAY_GUARD, f"an integer in 0..{MAX_RAY_GUARD}")
+        ms = _integer(max_steps, "max_steps", 1, MAX_RAY_STEPS, f"an integer in 1..{MAX_RAY_STEPS}")
+        self._live()
+        ctx, M = self.ctx, self.n_voxels
+        stats = np.zeros(4, np.int64)
+        with _Buffers(ctx) as bufs:
+            d_passed, d_ended, d_through = bufs.take(4 * max(M, 1)), bufs.take(4 * max(M, 1)), bufs.take(4 * n)
+            tail = (g, ms, d_passed.ptr, d_ended.ptr, d_through.ptr, ptr(stats, c_int64))
+            if batch is not None:
+                rc = ctx.lib.mc_voxel_rays_batch(ctx.handle, batch.handle, f, ptr(o, c_double), len(o), *tail)
+            else:
+                d_rows, d_origins = bufs.take(rows.nbytes), bufs.take(o.nbytes)
+                d_rows.from_host(rows)
+                d_origins.from_host(o)
+                rc = ctx.lib.mc_voxel_rays_f64(ctx.handle, d_rows.ptr, rows.shape[1], n, d_origins.ptr, len(o), *tail)
+            check(rc, "rays")
+            empty = np.zeros(0, np.int32)
+            return VoxelRays(d_passed.to_host(np.int32, count=M) if M else empty,
+                             d_ended.to_host(np.int32, count=M) if M else empty.copy(),
+                             d_through.to_host(np.int32, count=n), int(stats[0]), int(stats[1]), int(stats[2]))
 
     def close(self):
         """Give the filter's device scratch back (a later call allocates it again)."""
