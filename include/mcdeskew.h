@@ -883,6 +883,55 @@ int mc_voxel_rays_f64(mc_ctx* ctx, const double* d_rows, int64_t ld, int64_t n, 
  * walk; *launches = timed regions */
 int mc_timing_read_voxel_rays(mc_ctx* ctx, double* ms_phase, int64_t* launches);
 
+/* ---- kept normals: the cloud's normals carried across its edits (csrc/normals_core.hpp, normals.hpp) ---------------
+ * mc_voxel_register_* compute the normals of the whole cloud on every call, and a frame changes a small part of a map.
+ * A voxel's row of mc_voxel_normals is a function of the occupied cells in the (2R + 1)^3 cell window of its cell and
+ * of their centroids, R = ceil(radius / h), and of nothing else: not of ids, of arrival order or of atomics.  So a
+ * cloud can keep its rows for one (radius, max_nn), without a viewpoint, and an edit recomputes those it can change.
+ *
+ *   touched voxels T of an edit
+ *     mc_voxel_insert_*, mc_voxel_merge_sums   every voxel that received at least one item, new voxels included
+ *     mc_voxel_subtract_*                      every voxel that lost at least one item, emptied ones included
+ *     mc_voxel_remove                          the removed voxels
+ *     (a voxel is touched because an item landed in it, whether or not its centroid's bits moved)
+ *   dirty set D   the voxels present after the edit whose cell k has max_axis |k - k_t| <= R for the cell k_t of some
+ *                 t in T: the cell window alone, without a radius test, since the centroids before and after both
+ *                 matter.  The relation is symmetric, so D is found by walking the window of every touched cell; cells
+ *                 outside [-2^20, 2^20) do not exist, as in mc_voxel_normals
+ *   contract      after a successful edit the kept rows of D are computed again by mc_voxel_normals's definition on the
+ *                 edited cloud (radius, max_nn as kept, viewpoint NULL); the rows of every other voxel are carried over
+ *                 unchanged, on a removal to the voxel's new id (the survivors' order is stable).  The kept normals and
+ *                 counts are then bit for bit mc_voxel_normals(radius, max_nn, NULL) of the edited cloud, and the rows
+ *                 the edit recomputed number exactly |D|, which mc_voxel_kept_info reports
+ *   refusals      a refused edit (a bad item, a missing voxel, a bad remainder, 2^31 points) leaves the kept rows bit
+ *                 for bit as they were and recomputes 0 rows, as does a call without items and a mc_voxel_remove whose
+ *                 mask removes nothing.  An edit that fails after the cloud stopped being live leaves none kept either
+ *
+ * While normals are kept the centroids stay current too: an edit rewrites those of its touched voxels (a removal all
+ * of them, being a pass over the cloud anyway), and no analysis after it writes them again.  An insert or a
+ * subtraction that empties no voxel still makes no pass over the cloud or the table; it synchronises twice more than
+ * without kept normals: for the dirty count, and (max_nn != 0) for the number of dirty voxels the cap applies to.
+ * Device memory: 48 bytes per voxel (32 + 4 of rows and counts, two 4-byte stamps, 4 of the dirty list).
+ *
+ * mc_voxel_keep_normals computes all rows now (one full pass, timed as mc_voxel_normals's phases) and keeps them;
+ * called again it replaces them.  It refuses what mc_voxel_normals refuses of radius and max_nn.  A cloud of no
+ * voxels may keep normals: a later insert refreshes every new voxel.  A new mc_voxel_build_* on the context,
+ * mc_voxel_release and mc_voxel_drop_normals end them, and each gives their memory back.  mc_voxel_register_* and
+ * mc_voxel_register_frames read the kept rows, and launch no normals kernel, when the call's normals_radius and max_nn
+ * equal the kept ones (the radius compared as bits); otherwise they run as without, and the kept rows stay as they are.
+ * mc_voxel_normals is always the full, fresh computation. */
+int mc_voxel_keep_normals(mc_ctx* ctx, double radius, int32_t max_nn);
+/* copies of the kept rows (M, 4) = nx, ny, nz, curvature and counts (M,) into device memory (either may be NULL);
+ * MC_ERR_STATE when none are kept */
+int mc_voxel_kept_normals(mc_ctx* ctx, double* d_normals, int32_t* d_counts);
+/* the kept parameters, and counters[3] since the build: full passes run, rows recomputed by the last edit (|D|), rows
+ * recomputed by all edits; any may be NULL; MC_ERR_STATE when none are kept */
+int mc_voxel_kept_info(mc_ctx* ctx, double* radius, int32_t* max_nn, int64_t* counters);
+int mc_voxel_drop_normals(mc_ctx* ctx);
+/* event time (ms) of the refresh phases since the last read: ms_phase[4] = mark (claim, centroid, window marking),
+ * window, cap, carry (a removal's compaction of the kept rows); *launches = timed regions */
+int mc_timing_read_kept_normals(mc_ctx* ctx, double* ms_phase, int64_t* launches);
+
 /* Synthetic Mid-70 frames generated on the device (counter-hash RNG, bit-identical to
  * oracle/synth.py): frame f uses seed  seed + frame_id_base + f. */
 int mc_batch_synth(mc_batch* b, uint64_t seed, int64_t frame_id_base);

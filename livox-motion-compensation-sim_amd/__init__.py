@@ -38,6 +38,9 @@ Drop-in surface (reference file:line in each docstring):
                          against the cloud by point-to-plane ICP, the whole iteration history the same on every run;
                          VoxelCloud.register_frames(batch, max_distance, init, ...) -> VoxelFrameRegistrations, every
                          frame of a batch registered on its own in one call, row f bit for bit register(..., frame=f);
+                         VoxelCloud.keep_normals(radius=None, max_nn=30), .kept_normals() -> VoxelNormals, .kept ->
+                         VoxelKept, .drop_normals(): the normals kept across insert / merge / subtract / remove, only the
+                         rows an edit can change computed again, bit for bit a fresh normals(); register* read them;
                          VoxelCloud.rays(src, origins, guard=1, max_steps=4096, frame) -> VoxelRays, the rays of a scan
                          walked through the cloud: per voxel the beams that passed it and that ended in it (free-space
                          carving: remove((passed >= k) & (ended == 0))), integer counts, the same on every run
@@ -55,7 +58,7 @@ from .config import default_config, validate_config  # noqa: F401
 from .raymarch import LiDARSimulator  # noqa: F401
 from .runtime import Batch, Context, default_context  # noqa: F401
 from .simulator import LiDARMotionSimulator  # noqa: F401
-from .voxel import (VoxelCloud, VoxelClusters, VoxelFrameRegistrations, VoxelNearest, VoxelNormals, VoxelPlane,  # noqa: F401
-                    VoxelRays, VoxelRegistration, VoxelSums, voxel_downsample)  # noqa: F401
+from .voxel import (VoxelCloud, VoxelClusters, VoxelFrameRegistrations, VoxelKept, VoxelNearest, VoxelNormals,  # noqa: F401
+                    VoxelPlane, VoxelRays, VoxelRegistration, VoxelSums, voxel_downsample)  # noqa: F401
 
 __version__ = "0.1.0"

@@ -181,6 +181,12 @@ _SIGS = {
     # every frame of a batch registered in one call (inits: F x 16 or NULL)
     "mc_voxel_register_frames": (c_int, [c_void_p, c_void_p, c_void_p, _pd, _pd, _pd, _pi64]),
     "mc_timing_read_register_frames": (c_int, [c_void_p, _pd, _pi64]),
+    # the normals a voxel cloud keeps across its edits
+    "mc_voxel_keep_normals": (c_int, [c_void_p, c_double, c_int32]),
+    "mc_voxel_kept_normals": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "mc_voxel_kept_info": (c_int, [c_void_p, _pd, _pi32, _pi64]),
+    "mc_voxel_drop_normals": (c_int, [c_void_p]),
+    "mc_timing_read_kept_normals": (c_int, [c_void_p, _pd, _pi64]),
     "mc_batch_synth": (c_int, [c_void_p, c_uint64, c_int64]),
     "mc_batch_checksum": (c_int, [c_void_p, _pd]),
     "mc_deskew": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),

@@ -385,4 +385,47 @@ MC_CORE_HD void normals_finish(const double C[6], int32_t n, const double ci[3],
   out[3] = tr > 0.0 ? top / tr : 0.0;
 }
 
+// ---- kept normals: the voxels an edit of the cloud makes stale (include/mcdeskew.h "kept normals") -------------------
+// The estimate of a voxel reads the occupied cells of its window and their centroids and nothing else, and the window
+// relation is symmetric: the rows an edit can change are those of the voxels in the window of a touched cell.  Every
+// voxel carries a 32-bit stamp; an edit has an epoch, and the first lane that exchanges the epoch into a voxel's stamp
+// has claimed the voxel for this edit.  Nothing is cleared per edit: an older stamp is simply not the epoch.  0 is never
+// an epoch (fresh stamps are 0), and the edit after epoch 2^32 - 1 clears the stamps and starts again at 1.
+constexpr uint32_t kNormalsEpochLast = 0xFFFFFFFFu;
+
+// the epoch of the edit after the one of `epoch` (0: none yet); *clear: the stamps go back to 0 first
+MC_CORE_HD uint32_t normals_next_epoch(uint32_t epoch, bool* clear) {
+  *clear = epoch == kNormalsEpochLast;
+  return *clear ? 1u : epoch + 1u;
+}
+
+// whether this is the edit's first claim of voxel v.  Stamps: exchange(v, epoch) -> the word before (the device's
+// atomicExch; a harness's plain swap)
+template <typename Stamps>
+MC_CORE_HD bool normals_claim(Stamps& stamps, uint32_t v, uint32_t epoch) {
+  return stamps.exchange(v, epoch) != epoch;
+}
+
+// fn(v) for every voxel in the (2R + 1)^3 window of cell ki that this edit claims here first, in walk order; cells
+// outside the key range do not exist, as in normals_neighbours_v.  The centroids of g are not read
+template <typename Stamps, typename Fn>
+MC_CORE_HD void normals_mark_window(const NormalsGrid& g, const int32_t ki[3], int32_t R, uint32_t epoch, Stamps& dirty,
+                                     Fn&& fn) {
+  for (int32_t dx = -R; dx <= R; ++dx) {
+    int32_t k[3];
+    k[0] = ki[0] + dx;
+    if (k[0] < kVoxelKeyMin || k[0] >= kVoxelKeyEnd) continue;
+    for (int32_t dy = -R; dy <= R; ++dy) {
+      k[1] = ki[1] + dy;
+      if (k[1] < kVoxelKeyMin || k[1] >= kVoxelKeyEnd) continue;
+      for (int32_t dz = -R; dz <= R; ++dz) {
+        k[2] = ki[2] + dz;
+        if (k[2] < kVoxelKeyMin || k[2] >= kVoxelKeyEnd) continue;
+        uint32_t v;
+        if (normals_find(g, voxel_pack(k), &v) && normals_claim(dirty, v, epoch)) fn(v);
+      }
+    }
+  }
+}
+
 }  // namespace mc

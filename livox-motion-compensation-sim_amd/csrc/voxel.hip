@@ -41,17 +41,19 @@ enum {
   kInsValidate, kInsInsert, kInsRank, kInsAccumulate,   // growing the live cloud; the insert's phase holds the table's growth
   kRmValidate, kRmApply, kRmCheck, kRmCompact,          // shrinking it; the compact phase holds the keep flags and the table's refill
   kRyClear, kRyWalk,                                    // the rays through it
+  kKnMark, kKnWindow, kKnCap, kKnCarry,                 // the refresh of kept normals after an edit
   kAllPhases
 };
 struct PhaseRange { int first, count; };
 constexpr PhaseRange kFilterPhases = {kInsert, 4}, kNormalsPhases = {kNrmCentroids, 3}, kClPhases = {kClDensity, kClusterPhases},
                      kPlanePhases = {kPlCompact, 6}, kRegPhases = {kRgNormals, 4}, kRegFramesPhases = {kRfNormals, 4},
-                     kInsertPhases = {kInsValidate, 4}, kRemovePhases = {kRmValidate, 4}, kRaysPhases = {kRyClear, 2};
+                     kInsertPhases = {kInsValidate, 4}, kRemovePhases = {kRmValidate, 4}, kRaysPhases = {kRyClear, 2},
+                     kKeptPhases = {kKnMark, 4};
 constexpr int kRgSolve = 4;   // its public index
 constexpr int kVoxMeta = 4;   // the words of VoxTable::meta
 static_assert(kRegPhases.first + kRegPhases.count == kRfNormals && kRegFramesPhases.first + kRegFramesPhases.count == kInsValidate &&
               kInsertPhases.first + kInsertPhases.count == kRmValidate && kRemovePhases.first + kRemovePhases.count == kRyClear &&
-              kRaysPhases.first + kRaysPhases.count == kAllPhases &&
+              kRaysPhases.first + kRaysPhases.count == kKnMark && kKeptPhases.first + kKeptPhases.count == kAllPhases &&
               kClPhases.first + kClPhases.count == kPlCompact, "the ranges");
 
 struct VoxState : mcimpl::CtxExt {
@@ -111,6 +113,18 @@ struct VoxState : mcimpl::CtxExt {
   // the rays of a call: the sensor positions of a batch's frames, and the skipped rays and the transitions walked
   DevBuf<double> ry_origins;
   DevBuf<unsigned long long> ry_meta;
+  // the normals the cloud keeps across its edits (mc_voxel_keep_normals): their own rows and counts by voxel id (rg_normals
+  // and rg_counts stay the scratch of a registration with other parameters), the two stamps of every voxel and the epoch of
+  // the last edit (normals_core.hpp "kept normals"), the dirty list with its counter, and what the edits have recomputed.
+  // 48 B per voxel: 36 of rows, 8 of stamps, 4 of list.  While kn_on, every edit leaves cent current
+  DevBuf<double> kn_normals;
+  DevBuf<int32_t> kn_counts;
+  DevBuf<uint32_t> kn_touched, kn_dirty, kn_list, kn_meta;
+  bool kn_on = false;
+  double kn_radius = 0.0;
+  int32_t kn_max_nn = 0;
+  uint32_t kn_epoch = 0;
+  int64_t kn_full = 0, kn_last = 0, kn_total = 0;   // since the build: full passes, rows of the last edit, rows of all edits
 
   // with the context (mc_voxel_release has recycled the pairs into the context's pool before)
   ~VoxState() override {
@@ -212,6 +226,26 @@ int check_grid(double voxel, const double* origin) {
   return MC_OK;
 }
 
+// ---- the normals a cloud keeps across its edits (defined behind normals_run) --------------------------------------------
+// An edit of a cloud with kept normals (s->kn_on), in this order: kept_reserve when it adds voxels, kept_begin_edit,
+// its mark (kept_mark_items once the records are in; a removal marks and carries in keep_voxels), and kept_refresh
+// once s->M and the table are the edited cloud's and every centroid is current.
+int kept_reserve(mc_ctx* c, VoxState* s, int64_t keep, int64_t M);
+int kept_begin_edit(mc_ctx* c, VoxState* s, int64_t M);
+int kept_mark_items(mc_ctx* c, VoxState* s, int64_t M, int64_t n);
+int kept_refresh(mc_ctx* c, VoxState* s);
+
+// no normals kept any more, their blocks given back (the stream has drained, or nothing queued reads them)
+void kept_free(VoxState* s) {
+  s->kn_on = false;
+  s->kn_normals.reset();
+  s->kn_counts.reset();
+  s->kn_touched.reset();
+  s->kn_dirty.reset();
+  s->kn_list.reset();
+  s->kn_meta.reset();
+}
+
 // the build over n points of src; *bad: the lowest refused point (-1: none)
 template <bool BATCH>
 int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, int64_t* bad) {
@@ -221,6 +255,12 @@ int build(mc_ctx* c, VoxSrc src, int64_t n, int64_t lanes, int64_t* n_voxels, in
   s->built = false;
   s->cent_current = false;
   s->cl_current = false;
+  if (s->kn_normals) {   // a new build keeps no normals, and does not carry their 48 B per voxel along
+    HIPCHK(hipStreamSynchronize(c->stream));
+    kept_free(s);
+  }
+  s->kn_on = false;
+  s->kn_full = s->kn_last = s->kn_total = 0;
   s->M = 0;
   s->N = 0;
   s->log2cap = 0;
@@ -337,6 +377,7 @@ template <int KIND, typename Src>
 int insert(mc_ctx* c, VoxState* s, Src src, int64_t n, int64_t lanes, int64_t points, int64_t* n_new, int64_t* bad) {
   *bad = -1;
   *n_new = 0;
+  s->kn_last = 0;   // a refused call and one without items recompute no kept row
   if (n == 0) return MC_OK;
   if constexpr (KIND != kVoxRecords) {   // points are quantised on the cloud's own grid
     src.h = s->h;
@@ -403,14 +444,19 @@ int insert(mc_ctx* c, VoxState* s, Src src, int64_t n, int64_t lanes, int64_t po
     hipLaunchKernelGGL((k_vox_accumulate_items<KIND, Src>), pgrid, blk, 0, c->stream, src, t, s->sums.get(), s->cnt.get());
   }
   HIPCHK(hipGetLastError());
+  if (s->kn_on) {   // the records are in: the touched voxels' centroids and the dirty set (its refresh below)
+    if (int r = kept_reserve(c, s, M, Mn)) return r;
+    if (int r = kept_begin_edit(c, s, Mn)) return r;
+    if (int r = kept_mark_items(c, s, Mn, n)) return r;
+  }
   HIPCHK(hipStreamSynchronize(c->stream));
   s->M = Mn;
   s->N += points;
   s->built = true;
-  s->cent_current = false;   // as a new build: the next analysis sees the grown cloud
+  s->cent_current = s->kn_on;   // as a new build: the next analysis sees the grown cloud (kept normals: the mark has)
   s->cl_current = false;
   *n_new = fresh;
-  return MC_OK;
+  return s->kn_on ? kept_refresh(c, s) : MC_OK;
 }
 
 // the frame of dense point p of a batch: the last one starting at or before it (empty frames start where the next
@@ -488,7 +534,10 @@ int compact(mc_ctx* c, VoxState* s, const uint8_t* d_mask, int phase, int64_t* n
 // (voxel.hpp "taking voxels and points out"): the survivors' ids, their records and keys compacted into fresh arrays,
 // the table cleared (shrunk by voxel_table_shrink_log2's rule) and refilled.  M' == M: nothing is touched.  Two
 // synchronisations: M', and the survivors' points with the end of the refill, before the old blocks go back.
-int keep_voxels(mc_ctx* c, VoxState* s, int64_t* n_removed) {
+// Kept normals: the windows of the removed cells are stamped on the old ids before the refill (marked: a subtraction's
+// items have done it), the kept rows go to the survivors' new ids with the records, every centroid is written again (a
+// removal is a pass over the cloud anyway) and the stamped survivors are refreshed.
+int keep_voxels(mc_ctx* c, VoxState* s, int64_t* n_removed, bool marked = false) {
   *n_removed = 0;
   const int64_t M = s->M;
   int64_t Mk = 0;
@@ -513,7 +562,41 @@ int keep_voxels(mc_ctx* c, VoxState* s, int64_t* n_removed) {
     t.shift = 64 - log2cap;
     t.mask = (uint32_t)(cap - 1);
   }
+  DevBuf<double> kn_normals;
+  DevBuf<int32_t> kn_counts;
+  DevBuf<uint32_t> kn_touched, kn_dirty;
+  if (s->kn_on) {
+    if (int r = kn_normals.alloc(4 * (size_t)Mk)) return r;
+    if (int r = kn_counts.alloc((size_t)Mk)) return r;
+    if (int r = kn_touched.alloc((size_t)Mk)) return r;
+    if (int r = kn_dirty.alloc((size_t)Mk)) return r;
+    if (!marked) if (int r = kept_begin_edit(c, s, M)) return r;
+  }
   s->built = false;   // from here the records and the table change: a failure leaves no live build
+  if (s->kn_on) {
+    if (!marked) {
+      NrmMarkArgs m = {};
+      m.g = grid_of(s);
+      m.rec = out_of(s);
+      m.keep = s->rm_keep; m.n = M;
+      m.R = window_cells(s, s->kn_radius);
+      m.epoch = s->kn_epoch;
+      m.dirty = s->kn_dirty;
+      TimedRegion tr(c, &s->ev[kKnMark], c->stream);
+      hipLaunchKernelGGL(k_nrm_mark<true>, dim3(blocks_of(M)), dim3(kVoxBlock), 0, c->stream, m);
+    }
+    NrmCarryArgs a = {};
+    a.ids = s->pl_ids; a.M_keep = Mk;
+    a.normals = s->kn_normals; a.counts = s->kn_counts; a.dirty = s->kn_dirty;
+    a.epoch = s->kn_epoch;
+    a.normals_out = kn_normals; a.counts_out = kn_counts;
+    a.list = s->kn_list; a.n_list = s->kn_meta;
+    TimedRegion tr(c, &s->ev[kKnCarry], c->stream);
+    HIPCHK(hipMemsetAsync(s->kn_meta, 0, sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(kn_touched, 0, (size_t)std::max<int64_t>(Mk, 1) * sizeof(uint32_t), c->stream));   // no stamp is an epoch to come
+    HIPCHK(hipMemsetAsync(kn_dirty, 0, (size_t)std::max<int64_t>(Mk, 1) * sizeof(uint32_t), c->stream));
+    if (Mk > 0) hipLaunchKernelGGL(k_nrm_carry, dim3(blocks_of(Mk)), dim3(kVoxBlock), 0, c->stream, a);
+  }
   {
     TimedRegion tr(c, &s->ev[kRmCompact], c->stream);
     HIPCHK(hipMemsetAsync(s->rm_points, 0, sizeof(unsigned long long), c->stream));
@@ -550,7 +633,17 @@ int keep_voxels(mc_ctx* c, VoxState* s, int64_t* n_removed) {
   s->cl_current = false;
   s->built = true;
   *n_removed = M - Mk;
-  return MC_OK;
+  if (!s->kn_on) return MC_OK;
+  s->kn_normals = std::move(kn_normals);
+  s->kn_counts = std::move(kn_counts);
+  s->kn_touched = std::move(kn_touched);
+  s->kn_dirty = std::move(kn_dirty);
+  if (Mk == 0) {   // nothing is left to refresh; the cloud of no voxels keeps no rows
+    s->cent_current = true;
+    return MC_OK;
+  }
+  if (int r = centroids(c, s)) { s->kn_on = false; return r; }
+  return kept_refresh(c, s);
 }
 
 // the keep bytes of the live cloud (M > 0), queued: d_mask's clear bytes, or (null) the voxels that hold points
@@ -582,6 +675,7 @@ template <int KIND, typename Src>
 int subtract(mc_ctx* c, VoxState* s, Src src, int64_t n, int64_t lanes, int64_t points, int64_t* n_emptied, SubRefusal* ref) {
   *ref = SubRefusal();
   *n_emptied = 0;
+  s->kn_last = 0;   // as an insert's
   if (n == 0) return MC_OK;
   if constexpr (KIND != kVoxRecords) {   // points are quantised on the cloud's own grid
     src.h = s->h;
@@ -646,14 +740,20 @@ int subtract(mc_ctx* c, VoxState* s, Src src, int64_t n, int64_t lanes, int64_t 
     s->built = true;
     return MC_ERR_INVALID;
   }
+  if (s->kn_on) {   // the records are what they will be: the touched voxels (the emptied ones too) mark their windows
+    if (int r = kept_begin_edit(c, s, s->M)) return r;
+    if (int r = kept_mark_items(c, s, s->M, n)) return r;
+  }
   s->N -= points;
-  s->cent_current = false;   // as an insert: the next analysis sees the shrunk cloud
+  s->cent_current = s->kn_on;   // as an insert: the next analysis sees the shrunk cloud
   s->cl_current = false;
   s->built = true;
-  if (meta[1] == 0) return MC_OK;   // no voxel emptied: no pass over the cloud or the table
+  if (meta[1] == 0) return s->kn_on ? kept_refresh(c, s) : MC_OK;   // no voxel emptied: no pass over the cloud or the table
   const int64_t left = s->N;
-  if (int r = keep_flags(c, s, nullptr)) return r;
-  if (int r = keep_voxels(c, s, n_emptied)) return r;
+  // a failure from here leaves the cloud live or not, but never with kept rows its marked items have not refreshed,
+  // nor with the emptied voxels' centroids taken for current
+  if (int r = keep_flags(c, s, nullptr)) { s->kn_on = false; s->cent_current = false; return r; }
+  if (int r = keep_voxels(c, s, n_emptied, true)) { s->kn_on = false; s->cent_current = false; return r; }
   if (s->N != left) {
     s->built = false;
     return fail(MC_ERR_STATE, "voxel subtract: the voxels kept hold %lld points of %lld", (long long)s->N, (long long)left);
@@ -745,16 +845,22 @@ int plane_moments(mc_ctx* c, VoxState* s, const double p0[3], double sums[kPlane
   return MC_OK;
 }
 
-// The normals of the live build (include/mcdeskew.h mc_voxel_normals) for `who`; for_register: the window and cap
-// phases are timed as the registration's normals phase, not as the normals' own; as_phase >= 0: as that phase
-int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoint, double* d_normals, int32_t* d_counts,
-                double* d_cov, const char* who, bool for_register, int as_phase = -1) {
+// what mc_voxel_normals refuses of its plain arguments
+int normals_checks(double radius, int32_t max_nn, const double* viewpoint) {
   CHECK_ARG(std::isfinite(radius) && radius > 0.0, "radius must be finite and > 0 (got %g)", radius);
   CHECK_ARG(max_nn == 0 || (max_nn >= kNormalsMinNN && max_nn <= kNormalsMaxNN),
             "max_nn must be 0 (no cap) or in %d..%d (got %d)", kNormalsMinNN, kNormalsMaxNN, max_nn);
   if (viewpoint)
     for (int k = 0; k < 3; ++k)
       CHECK_ARG(std::isfinite(viewpoint[k]), "viewpoint must be finite (axis %d: %g)", k, viewpoint[k]);
+  return MC_OK;
+}
+
+// The normals of the live build (include/mcdeskew.h mc_voxel_normals) for `who`; for_register: the window and cap
+// phases are timed as the registration's normals phase, not as the normals' own; as_phase >= 0: as that phase
+int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoint, double* d_normals, int32_t* d_counts,
+                double* d_cov, const char* who, bool for_register, int as_phase = -1) {
+  if (int r = normals_checks(radius, max_nn, viewpoint)) return r;
   CHECK_ARG(((uintptr_t)d_normals & 15) == 0 && ((uintptr_t)d_cov & 15) == 0, "d_normals and d_cov must be 16-byte aligned");
   VoxState* s;
   if (int r = live_build(c, who, &s)) return r;
@@ -780,7 +886,7 @@ int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoin
   {
     TimedRegion tr(c, window, c->stream);
     HIPCHK(hipMemsetAsync(s->n_capped, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(k_nrm_window, dim3(blocks_of(M)), dim3(kVoxBlock), 0, c->stream, a);
+    hipLaunchKernelGGL(k_nrm_window<false>, dim3(blocks_of(M)), dim3(kVoxBlock), 0, c->stream, a);
   }
   HIPCHK(hipGetLastError());
   // the one synchronisation: how many voxels the cap applies to (none: no third launch)
@@ -795,6 +901,109 @@ int normals_run(mc_ctx* c, double radius, int32_t max_nn, const double* viewpoin
     HIPCHK(hipGetLastError());
   }
   return MC_OK;
+}
+
+// ---- the normals a cloud keeps across its edits -------------------------------------------------------------------------
+// The kept buffers (and the centroids, which stay current while normals are kept) for M voxels, the first `keep`
+// voxels' contents kept; the stamps of the others start at 0, which is no epoch
+int kept_reserve(mc_ctx* c, VoxState* s, int64_t keep, int64_t M) {
+  const size_t k = (size_t)keep, m = (size_t)std::max<int64_t>(M, 1);
+  if (int r = ctx_reserve_keep(c, s->kn_normals, 4 * k, 4 * m)) return r;
+  if (int r = ctx_reserve_keep(c, s->kn_counts, k, m)) return r;
+  if (int r = ctx_reserve_keep(c, s->kn_touched, k, m)) return r;
+  if (int r = ctx_reserve_keep(c, s->kn_dirty, k, m)) return r;
+  if (int r = ctx_reserve_keep(c, s->cent, kNormalsCent * k, kNormalsCent * m)) return r;
+  if (int r = ctx_reserve(c, s->kn_list, m)) return r;
+  if (!s->kn_meta) if (int r = s->kn_meta.alloc(1)) return r;
+  if (M > keep) {
+    HIPCHK(hipMemsetAsync(s->kn_touched + keep, 0, (size_t)(M - keep) * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(s->kn_dirty + keep, 0, (size_t)(M - keep) * sizeof(uint32_t), c->stream));
+  }
+  return MC_OK;
+}
+
+// the epoch of the edit that begins, over the M voxels that carry stamps (queued)
+int kept_begin_edit(mc_ctx* c, VoxState* s, int64_t M) {
+  bool clear = false;
+  s->kn_epoch = normals_next_epoch(s->kn_epoch, &clear);
+  if (clear && M > 0) {
+    HIPCHK(hipMemsetAsync(s->kn_touched, 0, (size_t)M * sizeof(uint32_t), c->stream));
+    HIPCHK(hipMemsetAsync(s->kn_dirty, 0, (size_t)M * sizeof(uint32_t), c->stream));
+  }
+  return MC_OK;
+}
+
+// The mark of an insert's or a subtraction's n items (slot[i] filled, the records final) in the cloud of M voxels,
+// queued: the touched voxels' centroids and the dirty list
+int kept_mark_items(mc_ctx* c, VoxState* s, int64_t M, int64_t n) {
+  NrmMarkArgs m = {};
+  m.g = grid_of(s);
+  m.rec = out_of(s);
+  m.rec.M = M;
+  m.slot = s->slot; m.n = n;
+  m.R = window_cells(s, s->kn_radius);
+  m.epoch = s->kn_epoch;
+  m.touched = s->kn_touched; m.dirty = s->kn_dirty;
+  m.list = s->kn_list; m.n_list = s->kn_meta;
+  m.cent = s->cent;
+  {
+    TimedRegion tr(c, &s->ev[kKnMark], c->stream);
+    HIPCHK(hipMemsetAsync(s->kn_meta, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_nrm_mark<false>, dim3(blocks_of(n)), dim3(kVoxBlock), 0, c->stream, m);
+  }
+  HIPCHK(hipGetLastError());
+  return MC_OK;
+}
+
+// The rows of the dirty list estimated again on the edited cloud (s->M, the table and every centroid are its own).  Two
+// synchronisations: the dirty count, and with a cap the capped count.  A failure leaves no kept normals
+int kept_refresh_run(mc_ctx* c, VoxState* s) {
+  const int64_t M = s->M;
+  uint32_t n_dirty = 0;
+  if (int r = copy_back(c, &n_dirty, s->kn_meta, sizeof n_dirty)) return r;
+  if ((int64_t)n_dirty > M) return fail(MC_ERR_STATE, "kept normals: %u dirty voxels of %lld", n_dirty, (long long)M);
+  s->kn_last = (int64_t)n_dirty;
+  s->kn_total += (int64_t)n_dirty;
+  if (n_dirty == 0) return MC_OK;
+  if (int r = ctx_reserve(c, s->capped, (size_t)n_dirty)) return r;
+  if (!s->n_capped) if (int r = s->n_capped.alloc(1)) return r;
+  NrmArgs a = {};
+  a.g = grid_of(s);
+  a.vslot = s->vslot;
+  a.M = M;
+  a.q = query_of(s, s->kn_radius, s->kn_max_nn);
+  a.normals = s->kn_normals; a.counts = s->kn_counts;
+  a.capped = s->capped; a.n_capped = s->n_capped;
+  a.list = s->kn_list; a.n_list = (int64_t)n_dirty;
+  {
+    TimedRegion tr(c, &s->ev[kKnWindow], c->stream);
+    HIPCHK(hipMemsetAsync(s->n_capped, 0, sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_nrm_window<true>, dim3(blocks_of(n_dirty)), dim3(kVoxBlock), 0, c->stream, a);
+  }
+  HIPCHK(hipGetLastError());
+  if (s->kn_max_nn == 0) return MC_OK;
+  uint32_t n_capped = 0;
+  if (int r = copy_back(c, &n_capped, s->n_capped, sizeof n_capped)) return r;
+  if (n_capped > n_dirty) return fail(MC_ERR_STATE, "kept normals: %u capped voxels of %u dirty ones", n_capped, n_dirty);
+  if (n_capped) {
+    {
+      TimedRegion tr(c, &s->ev[kKnCap], c->stream);
+      hipLaunchKernelGGL(k_nrm_cap, dim3((n_capped + kNrmCapBlock - 1) / kNrmCapBlock), dim3(kNrmCapBlock), 0, c->stream, a);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  return MC_OK;
+}
+
+int kept_refresh(mc_ctx* c, VoxState* s) {
+  const int r = kept_refresh_run(c, s);
+  if (r) s->kn_on = false;
+  return r;
+}
+
+// whether the cloud keeps the normals of these parameters, compared as bits
+bool kept_matches(const VoxState* s, double radius, int32_t max_nn) {
+  return s->kn_on && s->M > 0 && std::memcmp(&s->kn_radius, &radius, sizeof radius) == 0 && s->kn_max_nn == max_nn;
 }
 
 // ---- the registration of a source against the cloud ------------------------------------------------------------------
@@ -900,9 +1109,13 @@ int register_run(mc_ctx* c, const RegSrc& src, const mc_register_params* p, doub
   stats[3] = N;
   DeviceGuard g(c->device);
   // the normals of the call, into the state's scratch (their own checks of the radius and of max_nn)
-  if (int r = ctx_reserve(c, s->rg_normals, 4 * (size_t)std::max<int64_t>(M, 1))) return r;
-  if (int r = ctx_reserve(c, s->rg_counts, (size_t)std::max<int64_t>(M, 1))) return r;
-  if (int r = normals_run(c, p->normals_radius, p->max_nn, nullptr, s->rg_normals, s->rg_counts, nullptr, who, true)) return r;
+  // (kept normals of these very parameters are read where they are: no normals kernel runs)
+  const bool kept = kept_matches(s, p->normals_radius, p->max_nn);
+  if (!kept) {
+    if (int r = ctx_reserve(c, s->rg_normals, 4 * (size_t)std::max<int64_t>(M, 1))) return r;
+    if (int r = ctx_reserve(c, s->rg_counts, (size_t)std::max<int64_t>(M, 1))) return r;
+    if (int r = normals_run(c, p->normals_radius, p->max_nn, nullptr, s->rg_normals, s->rg_counts, nullptr, who, true)) return r;
+  }
   const int64_t L = plane_leaves(N);
   const size_t words = tree_words(kRegSums, L);
   if (int r = ctx_reserve(c, s->rg_ids, (size_t)N)) return r;
@@ -911,7 +1124,8 @@ int register_run(mc_ctx* c, const RegSrc& src, const mc_register_params* p, doub
   if (int r = reg_args(c, s, src, p->max_distance, &a)) return r;
   a.T = T;
   a.ids = s->rg_ids;
-  a.normals = s->rg_normals; a.counts = s->rg_counts;
+  a.normals = kept ? s->kn_normals : s->rg_normals;
+  a.counts = kept ? s->kn_counts : s->rg_counts;
   a.out = s->rg_tree;
   a.pairs = reinterpret_cast<unsigned long long*>(s->rg_tree.get() + words);
   int64_t last = L / kVoxBlock;
@@ -1004,9 +1218,12 @@ int register_frames_run(mc_ctx* c, const mc_batch* in, const mc_register_params*
   const int64_t M = s->M;
   DeviceGuard g(c->device);
   // the normals of the call, once for all frames
-  if (int r = ctx_reserve(c, s->rg_normals, 4 * (size_t)std::max<int64_t>(M, 1))) return r;
-  if (int r = ctx_reserve(c, s->rg_counts, (size_t)std::max<int64_t>(M, 1))) return r;
-  if (int r = normals_run(c, p->normals_radius, p->max_nn, nullptr, s->rg_normals, s->rg_counts, nullptr, who, true, kRfNormals)) return r;
+  const bool kept = kept_matches(s, p->normals_radius, p->max_nn);   // as register_run
+  if (!kept) {
+    if (int r = ctx_reserve(c, s->rg_normals, 4 * (size_t)std::max<int64_t>(M, 1))) return r;
+    if (int r = ctx_reserve(c, s->rg_counts, (size_t)std::max<int64_t>(M, 1))) return r;
+    if (int r = normals_run(c, p->normals_radius, p->max_nn, nullptr, s->rg_normals, s->rg_counts, nullptr, who, true, kRfNormals)) return r;
+  }
   const size_t rows = (size_t)F * p->max_iterations;
   int32_t live = 0;
   for (int32_t f = 0; f < F; ++f) live += fr[f].status == kRegGoOn;
@@ -1028,7 +1245,8 @@ int register_frames_run(mc_ctx* c, const mc_batch* in, const mc_register_params*
       if (int r = centroids(c, s)) return r;
       a.g = grid_of(s);
     }
-    a.normals = s->rg_normals; a.counts = s->rg_counts;
+    a.normals = kept ? s->kn_normals : s->rg_normals;
+    a.counts = kept ? s->kn_counts : s->rg_counts;
     a.tree = s->rf_tree;
     a.max_iterations = p->max_iterations;
     a.tol_rotation = p->tol_rotation; a.tol_translation = p->tol_translation;
@@ -1319,6 +1537,7 @@ int mc_voxel_remove(mc_ctx* c, const uint8_t* d_mask, int64_t* n_removed) {
   CHECK_ARG(c && n_removed, "NULL argument");
   VoxState* s;
   if (int r = live_build(c, "mc_voxel_remove", &s)) return r;
+  s->kn_last = 0;   // an all-False mask recomputes no kept row
   if (s->M == 0) return MC_OK;
   CHECK_ARG(d_mask, "d_mask is NULL");
   DeviceGuard g(c->device);
@@ -1423,6 +1642,73 @@ int mc_voxel_normals(mc_ctx* c, double radius, int32_t max_nn, const double* vie
 int mc_timing_read_normals(mc_ctx* c, double* ms_phase, int64_t* launches) {
   CHECK_ARG(c, "ctx is NULL");
   return read_phases(c, kNormalsPhases, ms_phase, launches);
+}
+
+int mc_voxel_keep_normals(mc_ctx* c, double radius, int32_t max_nn) {
+  CHECK_ARG(c, "ctx is NULL");
+  if (int r = normals_checks(radius, max_nn, nullptr)) return r;
+  VoxState* s;
+  if (int r = live_build(c, "mc_voxel_keep_normals", &s)) return r;
+  if (int r = check_window(s, radius, "radius")) return r;
+  DeviceGuard g(c->device);
+  s->kn_on = false;   // what was kept is replaced; a failure from here leaves none kept
+  s->kn_last = 0;
+  if (int r = kept_reserve(c, s, 0, s->M)) return r;
+  s->kn_epoch = 0;    // every stamp is 0 again
+  if (int r = normals_run(c, radius, max_nn, nullptr, s->kn_normals, s->kn_counts, nullptr, "mc_voxel_keep_normals", false)) return r;
+  s->cent_current = true;   // of a cloud without voxels too
+  s->kn_radius = radius;
+  s->kn_max_nn = max_nn;
+  ++s->kn_full;
+  s->kn_on = true;
+  return MC_OK;
+}
+
+// the state of a live build that keeps normals, for the entry point `who`
+static int kept_state(mc_ctx* c, const char* who, VoxState** s) {
+  if (int r = live_build(c, who, s)) return r;
+  if (!(*s)->kn_on) return fail(MC_ERR_STATE, "%s: the cloud keeps no normals (mc_voxel_keep_normals)", who);
+  return MC_OK;
+}
+
+int mc_voxel_kept_normals(mc_ctx* c, double* d_normals, int32_t* d_counts) {
+  CHECK_ARG(c, "ctx is NULL");
+  VoxState* s;
+  if (int r = kept_state(c, "mc_voxel_kept_normals", &s)) return r;
+  if (s->M == 0) return MC_OK;
+  DeviceGuard g(c->device);
+  if (d_normals) HIPCHK(hipMemcpyAsync(d_normals, s->kn_normals, 4 * (size_t)s->M * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  if (d_counts) HIPCHK(hipMemcpyAsync(d_counts, s->kn_counts, (size_t)s->M * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+  return MC_OK;
+}
+
+int mc_voxel_kept_info(mc_ctx* c, double* radius, int32_t* max_nn, int64_t* counters) {
+  CHECK_ARG(c, "ctx is NULL");
+  VoxState* s;
+  if (int r = kept_state(c, "mc_voxel_kept_info", &s)) return r;
+  if (radius) *radius = s->kn_radius;
+  if (max_nn) *max_nn = s->kn_max_nn;
+  if (counters) {
+    counters[0] = s->kn_full;
+    counters[1] = s->kn_last;
+    counters[2] = s->kn_total;
+  }
+  return MC_OK;
+}
+
+int mc_voxel_drop_normals(mc_ctx* c) {
+  CHECK_ARG(c, "ctx is NULL");
+  VoxState* s = state_of(c, false);
+  if (!s) return MC_OK;
+  DeviceGuard g(c->device);
+  HIPCHK(hipStreamSynchronize(c->stream));   // the blocks are idle when they go back
+  kept_free(s);
+  return MC_OK;
+}
+
+int mc_timing_read_kept_normals(mc_ctx* c, double* ms_phase, int64_t* launches) {
+  CHECK_ARG(c, "ctx is NULL");
+  return read_phases(c, kKeptPhases, ms_phase, launches);
 }
 
 int mc_voxel_clusters(mc_ctx* c, double eps, int32_t min_points, int32_t weighted, int32_t* d_labels, int32_t* d_density,

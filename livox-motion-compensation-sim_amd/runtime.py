@@ -405,6 +405,12 @@ class Context:
         the counts, then the walk of every ray."""
         return self._read_phases("timing_read_voxel_rays", ("clear_ms", "walk_ms"))
 
+    def read_timing_kept_normals(self) -> dict:
+        """Event time (ms) of the phases that refresh a cloud's kept normals after an edit, since the last read
+        (mc_timing_read_kept_normals): the mark (claim, centroid, window marking), the window and cap phases over the
+        dirty voxels, and a removal's carry of the kept rows to the survivors' new ids."""
+        return self._read_phases("timing_read_kept_normals", ("mark_ms", "window_ms", "cap_ms", "carry_ms"))
+
     def read_timing_register_frames(self) -> dict:
         """Event time (ms) of the phases of VoxelCloud.register_frames since the last read
         (mc_timing_read_register_frames): the normals once per call, then per iteration the step over the live

@@ -7,6 +7,7 @@ of a drive are accumulated into one cloud and most points re-observe the same su
   VoxelCloud.insert(batch_or_rows)  -> int, .state()  -> VoxelSums, .merge(state)  -> int
   VoxelCloud.remove(mask)  -> int, .subtract(batch_or_rows_or_state)  -> int
   VoxelCloud.normals(radius, max_nn=30, viewpoint=None, covariance=False)  -> VoxelNormals
+  VoxelCloud.keep_normals(radius=None, max_nn=30), .kept_normals()  -> VoxelNormals, .kept  -> VoxelKept, .drop_normals()
   VoxelCloud.clusters(eps, min_points=10, weighted=False)  -> VoxelClusters
   VoxelCloud.segment_plane(distance_threshold, num_iterations=1000, seed=0, refine=True, among=None)  -> VoxelPlane
   VoxelCloud.select(mask, with_pcd_len=False)  -> Batch
@@ -69,7 +70,7 @@ sum beyond +-n' 2^32 (the lowest item of such a voxel and the voxel's key are na
 ``subtract`` that empties no voxel costs what its items cost; ``remove``, and a ``subtract`` that empties one, cost what
 the cloud costs (one pass over the survivors' records, the key table cleared and refilled; it shrinks when the survivors
 fill less than an eighth of it).  Not built: tombstones (a removal that costs what leaves, at a compare in every probe
-loop), ``subtract(batch, frame=f)``, normals kept across a removal.
+loop), ``subtract(batch, frame=f)``.
 
 Surface normals (csrc/normals_core.hpp, csrc/normals.hpp; ``mc_voxel_normals``): what the reference's
 viewer computes with open3d on every cloud without normals (read_pointcloud.py:81-84), here from the live
@@ -80,6 +81,19 @@ in ascending key order, the covariance C = E[u u^T] - E[u] E[u]^T; the normal is
 for its smallest eigenvalue, the curvature its Rayleigh quotient over the trace.  Refused with ValueError:
 a radius that is not finite and > 0 or exceeds 4 h, max_nn not 0 and not in 3..64, a viewpoint that is not
 three finite numbers.
+
+Kept normals (csrc/normals_core.hpp "kept normals", csrc/normals.hpp ``k_nrm_mark``; ``mc_voxel_keep_normals``): a map
+changes by a frame at a time, and its normals need not be computed again as a whole for every registration.  A voxel's
+row is a function of the occupied cells in the (2R + 1)^3 cell window of its cell and of their centroids, so after
+``keep_normals(radius, max_nn)`` every ``insert``, ``merge``, ``subtract`` and ``remove`` computes again exactly the dirty
+set D — the voxels present afterwards whose cell is within R cells, on every axis, of a touched cell: one that received
+or lost an item, or was removed — and carries every other row over, on a removal to the voxel's new id.
+``kept_normals()`` is then bit for bit ``normals(radius, max_nn)`` of the edited cloud, and ``kept.refreshed_last`` is
+|D|.  A refused edit leaves the kept rows as they were and refreshes none.  ``register`` and ``register_frames`` read the
+kept rows, and run no normals kernel, when their ``normals_radius`` (None: 2 h) and ``max_nn`` are the kept ones; with
+other parameters they run as on a cloud that keeps none, and the kept rows stay.  ``normals()`` is always the full, fresh
+computation.  48 bytes of device memory per voxel; ``drop_normals()`` gives them back, and a new ``voxel_downsample`` on
+the context ends them.  Not built: a kept covariance or viewpoint, kept clusters.
 
 Density clustering (csrc/cluster_core.hpp, csrc/cluster.hpp; ``mc_voxel_clusters``): DBSCAN over the live
 build, the noise filtering and outlier removal of the reference's processing list (docs/Comprehensive
@@ -208,7 +222,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from ._lib import RegisterParams, check, load, ptr
+from ._lib import MC_ERR_STATE, RegisterParams, check, load, ptr
 from .runtime import Batch, Context, default_context
 
 MAX_POINTS = 2 ** 31 - 1
@@ -281,6 +295,15 @@ class VoxelNormals(NamedTuple):
     curvature: np.ndarray           # (M,) float64 surface variation l0 / (l0 + l1 + l2)
     counts: np.ndarray              # (M,) int32 neighbours used, the voxel itself included
     covariance: np.ndarray | None   # (M, 6) float64 xx, xy, xz, yy, yz, zz, when asked for
+
+
+class VoxelKept(NamedTuple):
+    """What :attr:`VoxelCloud.kept` returns: the parameters of the kept normals and, since the build, the work done."""
+    radius: float
+    max_nn: int
+    full_passes: int        # the times every row was computed (keep_normals)
+    refreshed_last: int     # the rows the last edit computed again: its dirty set
+    refreshed_total: int    # the rows all edits computed again
 
 
 def _normals_args(radius, max_nn, viewpoint, h):
@@ -756,6 +779,57 @@ class VoxelCloud:
             counts = d_counts.to_host(np.int32, count=M)
             cov = d_cov.to_host(np.float64, count=6 * M).reshape(M, 6) if covariance else None
         return VoxelNormals(np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]), counts, cov)
+
+    def keep_normals(self, radius=None, max_nn: int = 30) -> None:
+        """Compute ``normals(radius, max_nn)`` now, once, and keep the rows on the device across every later
+        :meth:`insert`, :meth:`merge`, :meth:`subtract` and :meth:`remove` (module docstring "Kept normals";
+        include/mcdeskew.h ``mc_voxel_keep_normals``): an edit computes again only the rows it can change, and
+        :meth:`kept_normals` stays bit for bit a fresh :meth:`normals`.  ``radius`` None: 2 h, the default of
+        :meth:`register`, which reads the kept rows when its ``normals_radius`` and ``max_nn`` are these.  Called
+        again, it replaces what was kept."""
+        if radius is None:
+            if self._h is None:
+                raise ValueError("radius=None means twice the voxel size, which this cloud does not know")
+            radius = 2 * self._h
+        r, nn, _ = _normals_args(radius, max_nn, None, self._h)
+        self._live()
+        check(self.ctx.lib.mc_voxel_keep_normals(self.ctx.handle, r, nn), "keep_normals")
+
+    def kept_normals(self) -> "VoxelNormals":
+        """The kept rows as :meth:`normals` returns them (covariance None): no normals kernel runs.  ValueError when the
+        cloud keeps none."""
+        self._live()
+        if self.kept is None:
+            raise ValueError("this cloud keeps no normals: call keep_normals first")
+        M = self.n_voxels
+        if M == 0:
+            return VoxelNormals(np.zeros((0, 3)), np.zeros(0), np.zeros(0, np.int32), None)
+        ctx = self.ctx
+        with _Buffers(ctx) as bufs:
+            d_out, d_counts = bufs.take(M * 32), bufs.take(M * 4)
+            check(ctx.lib.mc_voxel_kept_normals(ctx.handle, d_out.ptr, d_counts.ptr), "kept_normals")
+            out = d_out.to_host(np.float64, count=4 * M).reshape(M, 4)
+            counts = d_counts.to_host(np.int32, count=M)
+        return VoxelNormals(np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]), counts, None)
+
+    @property
+    def kept(self) -> "VoxelKept | None":
+        """What the cloud keeps (``mc_voxel_kept_info``): the parameters and the counters, or None when it keeps no
+        normals.  A cloud that an edit left without a live build (a failure that was no refusal) keeps none either and
+        reads as None here; its next use raises."""
+        self._live()
+        radius, nn, counters = c_double(0.0), c_int32(0), (c_int64 * 3)()
+        rc = self.ctx.lib.mc_voxel_kept_info(self.ctx.handle, ctypes.byref(radius), ctypes.byref(nn), counters)
+        if rc == MC_ERR_STATE:
+            return None
+        check(rc, "kept")
+        return VoxelKept(radius.value, nn.value, int(counters[0]), int(counters[1]), int(counters[2]))
+
+    def drop_normals(self) -> None:
+        """Keep no normals any more and give their device memory back (``mc_voxel_drop_normals``); the edits and
+        :meth:`register` then behave as on a cloud that never kept any."""
+        self._live()
+        check(self.ctx.lib.mc_voxel_drop_normals(self.ctx.handle), "drop_normals")
 
     def clusters(self, eps, min_points: int = 10, weighted: bool = False) -> "VoxelClusters":
         """DBSCAN over the voxel points (module docstring; include/mcdeskew.h ``mc_voxel_clusters``): labels
